@@ -24,11 +24,17 @@ N > 1   : one process per GPU (torch.distributed.run).  The data path is inside 
           their owner rank, every rank aligns the pairs it owns, edges go to rank 0 for the host set cover.  torch.distributed (gloo) only carries the 128-byte RCCL id, the
           barriers and the max-over-ranks of the timing.  Total work is fixed -> "strong".
 
-          `python bench.py --gpus N` with WORLD_SIZE unset re-executes itself under torch.distributed.run with N ranks.
-          N > 1 keeps configs[1] as the headline (the N = 1 point of a scaling run then equals the single-GPU bench) and adds
-          `configs.c3`: ONE warm pass of configs[2] — the configuration BASELINE names for the 8-GPU node — over all N ranks, with
+          `python bench.py --gpus N` with WORLD_SIZE unset starts itself under torch.distributed.run with N ranks, as a child process.
+          N > 1 keeps configs[1] as the headline (the N = 1 point of a scaling run then equals the single-GPU bench) and adds, with
+          --full, `configs.c3`: ONE warm pass of configs[2] — the configuration BASELINE names for the 8-GPU node — over all N ranks, with
           per-phase maxima over ranks, rccl_ranks and exchange bytes.
-also (N = 1, default config): `configs` — sub-records measured in the same run: c3 (BASELINE configs[2] = north_star's quoted
+--full  : a plain run sets up, warms up, times the --steps steps and prints the line (its rooflines come from the counters of those
+          steps).  Everything measured beyond the headline runs only with --full: the CPU baselines, the disk-to-TSV, default-workflow and
+          one-shot-process legs, the sub-records below and the configs[2] leg of N > 1.
+--dump-outputs DIR: after the timed steps, what the last step returned to its caller goes to DIR/<name>.npy (float32 / float64, at most
+          64 MB in all; a larger array keeps a fixed, seeded sample of its elements).  The inputs are seeded, so two builds run with the same
+          arguments can be compared output for output.
+also (N = 1, default config, --full): `configs` — sub-records measured in the same run: c3 (BASELINE configs[2] = north_star's quoted
           1-GPU target size, 500 proteomes: ONE timed pass after one warm-up pass, with its own roofline block and CPU baseline sample), c5-mini
           (the ProstT5 encoder's MFMA fraction on one synthetic proteome) and c4 (BASELINE configs[3] at its NOMINAL 2000 proteomes: one
           uc_cluster call through the default workflow with its rooflines, rounds and round-by-round CPU leg; --no-c4 skips it); `value_one_shot_processes` — what an unmodified
@@ -69,6 +75,34 @@ CONFIGS = {
     # default workflow (pre-step + 3-step cascade, the deep rounds on representatives only): `--config c4` therefore implies `--workflow default`
     "c4": (2000, 6000, 1.0, 0x5EED0004, "-c 0.8 --min-seq-id 0.3 -s 7.5", "BASELINE configs[3]"),
 }
+
+
+DUMP_BYTES = 64 << 20             # --dump-outputs: at most this much in all
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: arrays (name -> array) as d/<name>.npy, 8- and 16-bit integers as float32, everything else as float64 (both exact for
+    the values written here).  An array larger than its equal share of DUMP_BYTES keeps a fixed, seeded sample of its elements, in order."""
+    os.makedirs(d, exist_ok=True)
+    share = (DUMP_BYTES - 4096 * len(arrays)) // max(len(arrays), 1)         # 4 kB per file for the .npy header, generously
+    for name, a in arrays.items():
+        a = np.asarray(a).ravel()
+        dt = np.float32 if a.dtype.kind in "iub" and a.dtype.itemsize <= 2 else np.float64
+        keep = share // np.dtype(dt).itemsize
+        if a.size > keep:
+            a = a[np.sort(np.random.default_rng(0x5EED).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(d, name + ".npy"), a.astype(dt))
+
+
+def read_cluster_db(prefix):
+    """cluster DB -> representative key of every member key (the keys of a generated DB are 0 .. n-1)"""
+    ix = np.loadtxt(prefix + ".index", dtype=np.int64, ndmin=2)
+    ix = ix[np.argsort(ix[:, 1], kind="stable")]                            # entries in file order
+    ents = open(prefix, "rb").read().split(b"\0")[:-1]
+    mem = np.array(b"".join(ents).split(), np.int64)
+    assign = np.empty(len(mem), np.uint32)
+    assign[mem] = np.repeat(ix[:, 0], [e.count(b"\n") for e in ents])
+    return assign
 
 
 def pmc_json(name):
@@ -303,10 +337,10 @@ def bench_c5(args, world=1, rank=0, local_rank=0, multi=False):
     mine = order[rank::world]                              # every N-th sequence of the length-sorted order: equal residue counts AND equal length mixes per rank
     t_enc = t_gather = t_clu = 0.0
     n_aln = 0
-    assign = None
+    assign = s3_last = a_last = None
 
     def step(timed):
-        nonlocal t_enc, t_gather, t_clu, n_aln, assign
+        nonlocal t_enc, t_gather, t_clu, n_aln, assign, s3_last, a_last
         t0 = time.perf_counter()
         codes = enc.encode([aa[i] for i in mine])
         torch.cuda.synchronize()
@@ -331,6 +365,7 @@ def bench_c5(args, world=1, rank=0, local_rank=0, multi=False):
         t3 = time.perf_counter()
         if timed:
             t_enc += t1 - t0; t_gather += t2 - t1; t_clu += t3 - t2; n_aln += a
+            s3_last, a_last = s3, a
     for _ in range(args.warmup):
         step(False)
     s0 = enc.stats()
@@ -347,10 +382,12 @@ def bench_c5(args, world=1, rank=0, local_rank=0, multi=False):
         v = torch.tensor([dt, t_enc, t_gather, t_clu, ms], dtype=torch.float64)
         dist.all_reduce(v, op=dist.ReduceOp.MAX)
         dt, t_enc, t_gather, t_clu, ms = [float(x) for x in v]
-        c = torch.tensor([float(n_aln), fl], dtype=torch.float64)
+        c = torch.tensor([float(n_aln), fl, float(a_last or 0)], dtype=torch.float64)
         dist.all_reduce(c, op=dist.ReduceOp.SUM)
-        n_aln, fl = int(c[0].item()), float(c[1].item())
+        n_aln, fl, a_last = int(c[0].item()), float(c[1].item()), int(c[2].item())
     tf = fl / (ms * 1e-3) / 1e12 if ms > 0 else 0.0            # all replicas together: summed FLOPs over the slowest replica's GPU time
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"codes_3di": s3_last, "cluster_assignment": assign, "n_alignments": [a_last]})
     if rank == 0:
         print(json.dumps({
             "metric": "3Di alignments/sec (createdb ProstT5 AA->3Di encoder + cluster path, end to end)", "value": n_aln / dt, "unit": "alignments/s",
@@ -443,7 +480,7 @@ def cpu_baseline_workflow(prefix, options, rounds, total_alignments, seconds_per
             "rounds": per_round}
 
 
-def bench_workflow(args, proteomes, families, len_scale, seed, options, label, custom, steps=None, warmup=None, cpu_seconds=None):
+def bench_workflow(args, proteomes, families, len_scale, seed, options, label, custom, steps=None, warmup=None, cpu_seconds=None, dump=False):
     """-> the line as a dict.  `--workflow default`: one step = one `uc_cluster(db, options)` call — the call of cluster.rs:45-49, which forwards the option string
     WITHOUT --single-step-clustering — i.e. the linear-time pre-step + the 3-step cascade, one C entry point, from the DB files (page cache
     warm) to the cluster DB.  `value` excludes the host-side read + encode of the DB files (uc_stats.stage_seconds[load]; the contract's
@@ -528,7 +565,9 @@ def bench_workflow(args, proteomes, families, len_scale, seed, options, label, c
                                                                          "n_gapped_alignments", "n_start_alignments", "n_pk_reruns", "n_sw_runs")},
     }
     U.lib().uc_release_scratch()
-    if not args.no_cpu_baseline:
+    if dump and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"cluster_assignment": read_cluster_db(outp + "_cluster"), "n_alignments": [st["n_gapped_alignments"]]})
+    if args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline_workflow(prefix, options, rounds, st["n_gapped_alignments"],
                                                     seconds_per_round=max(2.0, (args.cpu_seconds if cpu_seconds is None else cpu_seconds) / 2.5))
     return out
@@ -681,7 +720,12 @@ def main():
     ap.add_argument("--full-line", action="store_true", help="print the full record (every sub-record with its prose, ~20 kB) instead of the slim line + detail file")
     ap.add_argument("--workflow", choices=["plain", "default"], help="plain = the all-vs-all step (--single-step-clustering semantics; default for c2/c3/c4-lite); "
                     "default = what cluster.rs:45-49 triggers: pre-step + 3-step cascade through one uc_cluster call (default for c4)")
+    ap.add_argument("--full", action="store_true", help="also measure everything beyond the headline: CPU baselines, disk-to-TSV / default-workflow / one-shot legs, "
+                    "sub-records (a plain run only times the steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step returned as DIR/<name>.npy (at most 64 MB in all)")
     args = ap.parse_args()
+    if args.dump_outputs and args.steps < 1:
+        ap.error("--dump-outputs needs --steps >= 1")
     for kv in filter(None, os.environ.get("UC_BENCH_PROTEOMES", "").split(",")):      # test hook, e.g. "c2=5,c3=5": the named configs at a toy size
         k, v = kv.split("=")
         CONFIGS[k] = (int(v),) + CONFIGS[k][1:]
@@ -694,7 +738,7 @@ def main():
     if args.config != "c5" and (args.workflow or ("default" if args.config == "c4" else "plain")) == "default":
         if args.gpus != 1:
             raise SystemExit("--workflow default is a single-process line (uc_cluster spreads over GPUs itself with '--gpus N' in --options)")
-        print(json.dumps(slim_line(bench_workflow(args, proteomes, families, len_scale, seed, options, label, custom), args)))
+        print(json.dumps(slim_line(bench_workflow(args, proteomes, families, len_scale, seed, options, label, custom, dump=True), args)))
         return
 
     import torch
@@ -708,7 +752,7 @@ def main():
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        # plain `python bench.py --gpus N`: become the launcher (one process per GPU, rendezvous on 127.0.0.1)
+        # plain `python bench.py --gpus N`: start the launcher as a child (one process per GPU, rendezvous on 127.0.0.1) and pass on its exit status
         import socket
         with socket.socket() as sk:
             sk.bind(("127.0.0.1", 0))
@@ -716,7 +760,7 @@ def main():
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus), "--master-addr", "127.0.0.1",
                "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
         sys.stdout.flush()
-        os.execv(sys.executable, cmd)
+        sys.exit(subprocess.call(cmd))
     if world != args.gpus:
         raise SystemExit("--gpus %d but WORLD_SIZE=%d" % (args.gpus, world))
     if not torch.cuda.is_available():
@@ -742,7 +786,7 @@ def main():
 
     threads = max(1, (os.cpu_count() or 1) // world)
 
-    def run_config(proteomes, families, len_scale, seed, options, label, custom, steps, warmup):
+    def run_config(proteomes, families, len_scale, seed, options, label, custom, steps, warmup, dump=False):
         """K timed passes of one workload; returns (the line as a dict on rank 0 / None elsewhere, DB prefix, n, workdir)"""
         workdir = os.path.join(args.workdir, "p%d_f%d_s%g_%x" % (proteomes, families, len_scale, seed))
         if rank == 0:
@@ -759,7 +803,7 @@ def main():
         eng.reset_stats()
         barrier()
         t0 = time.perf_counter()
-        n_aln = 0
+        n_aln = a = 0
         for _ in range(steps):
             assign, a = eng.cluster_step(comm, args.target_shards)
             n_aln += a
@@ -772,14 +816,16 @@ def main():
             v = torch.tensor([dt], dtype=torch.float64)
             dist.all_reduce(v, op=dist.ReduceOp.MAX)
             dt = float(v.item())
-            c = torch.tensor([n_aln, st["exchange_bytes"]], dtype=torch.int64)
+            c = torch.tensor([n_aln, st["exchange_bytes"], a], dtype=torch.int64)
             dist.all_reduce(c, op=dist.ReduceOp.SUM)
-            n_aln, xbytes = int(c[0].item()), int(c[1].item())
+            n_aln, xbytes, a = int(c[0].item()), int(c[1].item()), int(c[2].item())
             ph = torch.tensor(st["phase_seconds"], dtype=torch.float64)
             dist.all_reduce(ph, op=dist.ReduceOp.MAX)
             st["phase_seconds"] = ph.tolist()
         if rank != 0:
             return None, prefix, n, workdir
+        if dump and args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"cluster_assignment": assign, "n_alignments": [a]})
         steps_ = max(steps, 1)
         sw_s = st["sw_kernel_ms"] / 1e3
         pre_s = st["prefilter_kernel_ms"] / 1e3
@@ -855,9 +901,9 @@ def main():
             out["phases_max_over_ranks_s_per_step"] = {k: v / steps_ for k, v in zip(U.PHASES, st["phase_seconds"])}
         return out, prefix, n, workdir
 
-    out, prefix, n, workdir = run_config(proteomes, families, len_scale, seed, options, label, custom, args.steps, args.warmup)
+    out, prefix, n, workdir = run_config(proteomes, families, len_scale, seed, options, label, custom, args.steps, args.warmup, dump=True)
 
-    if rank == 0:
+    if rank == 0 and args.full:
         if not multi and not args.no_extra_legs:
             # uc_cluster + uc_createtsv, DB on disk (page cache warm) -> clust.tsv
             outp = os.path.join(workdir, "bench_clust")
@@ -890,7 +936,7 @@ def main():
             best = max(cb, key=lambda d: d["value"])
             out["cpu_baseline"] = best                       # the faster CPU leg is THE baseline ...
             out["cpu_baselines"] = cb                        # ... both are reported
-    if not multi and args.config == "c2" and not custom and not args.no_sub_records and not args.no_extra_legs:
+    if not multi and args.full and args.config == "c2" and not custom and not args.no_sub_records and not args.no_extra_legs:
         # every sub-record is guarded on its own: an exception, an out-of-memory or a missing tool in one leg leaves {"error": ...} in its
         # place and the headline, the other records and the line itself stand
         subs = {}
@@ -953,7 +999,7 @@ def main():
                                             "alignments_per_step": og["config"]["alignments_per_step"], "listed_pairs_per_step": out["config"]["alignments_per_step"],
                                             "clusters": og["config"]["clusters"], "sw_kernel_ms_per_step": og["roofline"]["kernel_ms_per_step"],
                                             "cells_run_per_step": og["roofline"]["cells_run_per_step"]}}
-    if multi and args.config == "c2" and not custom and not args.no_sub_records:
+    if multi and args.full and args.config == "c2" and not custom and not args.no_sub_records:
         # the configuration BASELINE names for the 8-GPU node (configs[2]: 500 proteomes, target DB sharded across the ranks): ONE timed pass
         # after one warm-up pass with all N ranks; the headline above stays configs[1] so that the N = 1 point of a scaling run agrees with BENCH
         U.lib().uc_release_scratch()

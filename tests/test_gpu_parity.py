@@ -718,7 +718,7 @@ def test_bench_line_contract(tmp_path):
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--proteomes", "3", "--families", "60", "--steps", "2", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--proteomes", "3", "--families", "60", "--steps", "2", "--warmup", "1", "--full",
                         "--cpu-seconds", "1", "--workdir", str(tmp_path), "--detail-dir", str(tmp_path / "detail")], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -773,18 +773,29 @@ def test_bench_line_contract(tmp_path):
 def test_bench_line_does_not_depend_on_the_step_count(tmp_path):
     """r2's line added 8 B x the CUMULATIVE similar-k-mer counter once per step, so roofline_prefilter.frac grew with --steps
     (0.06 at one step, 0.15 at twenty).  Per-step algorithmic bytes, counts and everything derived from them alone must be
-    identical for --steps 1 and --steps 4."""
+    identical for --steps 1 and --steps 4, and so must the outputs of the last step (--dump-outputs).  A plain run (no --full)
+    times the steps and nothing else."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    res = []
+    res, dumps = [], []
     for steps in (1, 4):
+        dump = tmp_path / ("out%d" % steps)
         r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--proteomes", "3", "--families", "60", "--steps", str(steps), "--warmup", "1",
-                            "--no-cpu-baseline", "--no-extra-legs", "--full-line", "--workdir", str(tmp_path)], capture_output=True, text=True, timeout=600)
+                            "--full-line", "--workdir", str(tmp_path), "--dump-outputs", str(dump)], capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, r.stderr[-2000:]
         res.append(json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1]))
+        dumps.append({k: np.load(dump / (k + ".npy")) for k in ("cluster_assignment", "n_alignments")})
     a, b = res
+    assert a["steps"] == 1 and b["steps"] == 4 and b["ms_per_step"] > 0
+    for k in ("cpu_baseline", "value_disk_to_tsv", "workflow_default", "value_one_shot_processes", "configs"):
+        assert k not in a and k not in b, k
+    da, db_ = dumps
+    assert da["cluster_assignment"].dtype == np.float64 and len(da["cluster_assignment"]) == int(a["config"]["workload"].split(" seqs")[0].split()[-1])
+    assert np.array_equal(da["cluster_assignment"], db_["cluster_assignment"]) and np.array_equal(da["n_alignments"], db_["n_alignments"])
+    assert int((da["cluster_assignment"] == np.arange(len(da["cluster_assignment"]))).sum()) == a["config"]["clusters"]
+    assert da["n_alignments"][0] == a["config"]["alignments_per_step"] == b["config"]["alignments_per_step"]
     assert a["algorithmic_bytes_per_step"] == b["algorithmic_bytes_per_step"]
     assert a["counts_rank0_per_step"] == b["counts_rank0_per_step"]
     for blk, key in (("roofline_prefilter", "algorithmic_bytes_per_step"), ("roofline_end_to_end", "algorithmic_bytes_per_step"), ("roofline_end_to_end", "bytes_per_alignment"),

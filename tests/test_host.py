@@ -323,3 +323,27 @@ def test_bench_slim_line_of_a_committed_full_record():
         broken = dict(full, configs=dict(full["configs"], c4={"error": "RuntimeError: out of memory"}))
         l2 = b.slim_line(broken, types.SimpleNamespace(full_line=False, workdir=d, detail_dir=d, config="c2"))
         assert l2["errors"] == {"c4": "RuntimeError: out of memory"} and "c4_value" not in l2 and l2["value"] == line["value"] and "c3_value" in l2
+
+
+def test_bench_dump_outputs_stays_in_budget_and_reads_cluster_dbs_back(tmp_path):
+    """bench.py --dump-outputs (pure host logic): exact float32 / float64 copies, an over-budget array cut to a fixed seeded sample in
+    order, under DUMP_BYTES in all; the cluster DB the default-workflow path leaves is read back into the assignment that was written."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    b.DUMP_BYTES = 1 << 16
+    big, codes = np.arange(100_000, dtype=np.uint32) * 7, np.arange(1000, dtype=np.uint8) % 21
+    for d in ("a", "b"):
+        b.dump_outputs(str(tmp_path / d), {"big": big, "codes": codes, "n": [12345678901]})
+    got = {k: np.load(tmp_path / "a" / (k + ".npy")) for k in ("big", "codes", "n")}
+    assert sum(os.path.getsize(tmp_path / "a" / (k + ".npy")) for k in got) <= b.DUMP_BYTES
+    assert got["codes"].dtype == np.float32 and np.array_equal(got["codes"], codes)
+    assert got["n"].dtype == np.float64 and got["n"][0] == 12345678901
+    s = got["big"]
+    assert s.dtype == np.float64 and 0 < len(s) < len(big) and np.all(np.diff(s) > 0) and np.all(s % 7 == 0)
+    assert np.array_equal(s, np.load(tmp_path / "b" / "big.npy"))
+    assign = np.array([0, 0, 2, 2, 0, 5, 5, 7, 2, 9], np.uint32)
+    out = str(tmp_path / "clu")
+    assert U.lib().uc_write_cluster_db(out.encode(), len(assign), assign.ctypes.data) == 0
+    assert np.array_equal(b.read_cluster_db(out), assign)

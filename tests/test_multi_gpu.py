@@ -156,8 +156,8 @@ def test_bench_n_gt_1_code_path_with_one_real_rccl_rank(tmp_path):
     r1 = subprocess.run([sys.executable] + tail + ["--no-extra-legs", "--no-sub-records"], env=env, capture_output=True, text=True, timeout=800)
     assert r1.returncode == 0, r1.stderr[-3000:]
     one = json.loads([l for l in r1.stdout.splitlines() if l.startswith("{")][-1])
-    r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1", "--master-port", str(port)] + tail,
-                       env=dict(env, UC_BENCH_FORCE_MULTI="1"), capture_output=True, text=True, timeout=800)
+    r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1", "--master-port", str(port)] + tail
+                       + ["--full"], env=dict(env, UC_BENCH_FORCE_MULTI="1"), capture_output=True, text=True, timeout=800)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 1 and line["rccl_ranks"] == 1 and line["scaling"] == "strong"
