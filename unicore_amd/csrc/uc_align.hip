@@ -29,14 +29,33 @@ constexpr int SW_PK_OVF_HOST = 0x7C00 - 256;   // == SW_PK_OVF of uc_sw_pk_impl.
 // whenever the box's memory is not warm for this process (one 108 GiB buffer: 4.2 s of a 14 s call at 500 proteomes in the first process on a fresh box,
 // profiles/r06/c4_p500_alloc.txt), while the batches a smaller buffer adds cost a launch tail each (r05: halving the batches of nominal configs[3] cost 3 %
 // of the pass)
-static unsigned long long tb_budget_bytes(size_t already_held) {
-    if (const char *e = getenv("UC_TB_BUDGET_MB")) return std::max<unsigned long long>(1, strtoull(e, nullptr, 10)) << 20;
-    size_t free_b = 0, total_b = 0;
-    unsigned long long cap = 64ull << 30;
-    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess)
-        cap = std::min<unsigned long long>(cap, (unsigned long long)((free_b + already_held) * 0.55));
-    return std::max<unsigned long long>(cap, 256ull << 20);
-}
+// The plan of a MODE 7 call costs ~110 B per pair beside the matrices: the flagged list is worked off in segments of 32 M pairs (nominal
+// configs[3]: 170 M flagged pairs per 256 M-pair batch of the stage), each planned and cut into matrix batches on its own; a segment
+// still holds ~1.5 TB of matrices, i.e. dozens of one-class batches.  (Tests: a forced matrix budget also forces 1000-pair segments.)
+struct TbBudget {
+    unsigned long long forced = 0;   // UC_TB_BUDGET_MB in bytes, 0 if unset
+    TbBudget() {
+        if (const char *e = getenv("UC_TB_BUDGET_MB")) forced = std::max<unsigned long long>(1, strtoull(e, nullptr, 10)) << 20;
+    }
+    uint32_t segment_pairs() const { return forced ? 1000u : (32u << 20); }
+    // matrix bytes of one batch, for a segment whose matrices take `total` bytes and a buffer that holds `held` already
+    unsigned long long batch_bytes(unsigned long long total, size_t held) const {
+        if (forced) return forced;
+        size_t free_b = 0, total_b = 0;
+        unsigned long long cap = 64ull << 30;
+        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess)
+            cap = std::min<unsigned long long>(cap, (unsigned long long)((free_b + held) * 0.55));
+        const unsigned long long budget = std::max<unsigned long long>(cap, 256ull << 20);
+        // Fresh device memory is not free: 25-60 ms per GiB on a box whose memory has been used before (tools/ubench/alloc_cost.hip,
+        // profiles/r04/alloc_*.log), so a call whose matrices would fit a few times over takes a third of them at a time, at least
+        // 16 GiB (about the buffer r04 took for an eighth of its whole-box matrices).  What the buffer already holds is free to use.
+        // A buffer of a useful size that is there already IS the budget: a segment whose batches would be a little larger than
+        // the last one's must not take a new block (r06)
+        if (held >= ((size_t)8 << 30)) return (unsigned long long)held - 64;
+        const unsigned long long want = std::max<unsigned long long>(16ull << 30, total / 3);
+        return std::min(budget, std::max<unsigned long long>(want, (unsigned long long)held));
+    }
+};
 
 namespace {
 
@@ -98,11 +117,6 @@ __device__ __forceinline__ int class_of(int lq, int tab) {
     return c;
 }
 __device__ __forceinline__ uint32_t task_cap(int c, int tab) { return c < c_tab[tab].n ? c_tab[tab].tcap[c] : SW_LONG_TASK_PAIRS; }   // long queries: one pair per wave (uc_sw_long.hip)
-
-inline dim3 grid_for(uint64_t n, uint32_t cap = 16384) {
-    const uint64_t b = (n + 255) / 256;
-    return dim3((uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(b, cap)));
-}
 
 // key = [ class : 5 | query : 24 | 65535 - effective target length : 16 ]
 __global__ void __launch_bounds__(256) plan_key_kernel(uint32_t n, const uint32_t *q, const uint32_t *t, const int32_t *qe,
@@ -704,27 +718,35 @@ struct SwPlan {
     }
 };
 
-static void scan_u32(Engine &E, DevBuf<char> &tmp, const uint32_t *in, uint32_t *out, uint32_t n, bool inclusive_max) {
+// running maximum (inclusive) of a u32 array
+static void max_scan_u32(Engine &E, DevBuf<char> &tmp, const uint32_t *in, uint32_t *out, uint32_t n) {
     size_t tb = 0;
-    if (inclusive_max) {
-        UC_HIP(rocprim::inclusive_scan(nullptr, tb, in, out, (size_t)n, MaxU32(), E.stream));
-        tmp.reserve(tb + 256);
-        UC_HIP(rocprim::inclusive_scan(tmp.p, tb, in, out, (size_t)n, MaxU32(), E.stream));
-    } else {
-        UC_HIP(rocprim::exclusive_scan(nullptr, tb, in, out, 0u, (size_t)n, rocprim::plus<uint32_t>(), E.stream));
-        tmp.reserve(tb + 256);
-        UC_HIP(rocprim::exclusive_scan(tmp.p, tb, in, out, 0u, (size_t)n, rocprim::plus<uint32_t>(), E.stream));
-    }
+    UC_HIP(rocprim::inclusive_scan(nullptr, tb, in, out, (size_t)n, MaxU32(), E.stream));
+    tmp.reserve(tb + 256);
+    UC_HIP(rocprim::inclusive_scan(tmp.p, tb, in, out, (size_t)n, MaxU32(), E.stream));
 }
 
-// total of a 0/1 flag array given its exclusive scan
-static uint32_t scan_total(Engine &E, const uint32_t *flag, const uint32_t *pos, uint32_t n) {
+// a 0/1 flag array -> its exclusive scan in pos (where each flagged entry goes) -> the number of flagged entries (one host synchronisation)
+static uint32_t compact(Engine &E, DevBuf<char> &tmp, const uint32_t *flag, uint32_t *pos, uint32_t n) {
+    size_t tb = 0;
+    UC_HIP(rocprim::exclusive_scan(nullptr, tb, flag, pos, 0u, (size_t)n, rocprim::plus<uint32_t>(), E.stream));
+    tmp.reserve(tb + 256);
+    UC_HIP(rocprim::exclusive_scan(tmp.p, tb, flag, pos, 0u, (size_t)n, rocprim::plus<uint32_t>(), E.stream));
     if (!n) return 0;
     uint32_t a = 0, b = 0;
     UC_HIP(hipMemcpyAsync(&a, pos + (n - 1), 4, hipMemcpyDeviceToHost, E.stream));
     UC_HIP(hipMemcpyAsync(&b, flag + (n - 1), 4, hipMemcpyDeviceToHost, E.stream));
     UC_HIP(hipStreamSynchronize(E.stream));
     return a + b;
+}
+
+// the packed classes form a prefix of a plan's sorted pair list, and their tasks a prefix of its task list
+struct PackedPrefix { uint32_t pairs, tasks; };
+static PackedPrefix packed_prefix(const SwPlan &P) {
+    const ClassTable &tab = h_tab[P.tab];
+    int c = 0;
+    while (c < tab.n && tab.pk[c]) c++;
+    return {P.pair_base[c], P.task_base[c]};
 }
 
 static void build_plan(Engine &E, SwPlan &P, DevBuf<char> &tmp, uint32_t n, const uint32_t *q, const uint32_t *t,
@@ -764,10 +786,9 @@ static void build_plan(Engine &E, SwPlan &P, DevBuf<char> &tmp, uint32_t n, cons
         P.saux.reserve(n);
         hipLaunchKernelGGL(plan_aux_kernel, grid_for(n), dim3(256), 0, s, n, P.idx.p, aux, P.saux.p);
     }
-    scan_u32(E, tmp, P.head.p, P.segstart.p, n, true);
+    max_scan_u32(E, tmp, P.head.p, P.segstart.p, n);
     hipLaunchKernelGGL(plan_taskflag_kernel, grid_for(n), dim3(256), 0, s, n, P.key2.p, P.segstart.p, tab, P.flag.p);
-    scan_u32(E, tmp, P.flag.p, P.tpos.p, n, false);
-    P.ntasks = scan_total(E, P.flag.p, P.tpos.p, n);
+    P.ntasks = compact(E, tmp, P.flag.p, P.tpos.p, n);
     P.tasks.reserve(P.ntasks); P.tcls.reserve(P.ntasks);
     hipLaunchKernelGGL(plan_taskfill_kernel, grid_for(n), dim3(256), 0, s, n, P.key2.p, P.flag.p, P.tpos.p, P.tasks.p, P.tcls.p);
     // longest-processing-time-first inside each class: the big tasks start first, the small ones fill the tail
@@ -928,7 +949,7 @@ struct AlignScratch {
     DevBuf<char> sc_tmp;
 };
 static AlignScratch &scratch_of(Engine &E) {
-    if (!E.aln) E.aln = take_align_scratch(E.device);
+    if (!E.aln) E.aln = ParkedScratch<AlignScratch>::take_or_new(E.device);
     return *E.aln;
 }
 
@@ -939,18 +960,14 @@ static void run_plan(Engine &E, SwPlan &P, int mode, int32_t *os, int32_t *oqe, 
     E.timed_ms_begin();
     uint64_t launches = launch_plan(E, P, mode, os, oqe, ote, work);
     double ms = E.timed_ms_end();
-    const ClassTable &tab = h_tab[P.tab];
-    int npk = 0;
-    while (npk < tab.n && tab.pk[npk]) npk++;
-    const uint32_t n_pk = P.pair_base[npk];   // packed classes form a prefix of the sorted pair list
+    const uint32_t n_pk = packed_prefix(P).pairs;
     if (n_pk) {
         RerunBufs &B = scratch_of(E).rr_B;
         SwPlan &P2 = scratch_of(E).rr_P2;
         hipStream_t s = E.stream;
         B.flag.reserve(n_pk); B.pos.reserve(n_pk);
         hipLaunchKernelGGL(pk_flag_kernel, grid_for(n_pk), dim3(256), 0, s, n_pk, os, oqe, SW_PK_OVF_HOST, ovf_only ? 1 : 0, B.flag.p);
-        scan_u32(E, tmp, B.flag.p, B.pos.p, n_pk, false);
-        const uint32_t n2 = scan_total(E, B.flag.p, B.pos.p, n_pk);
+        const uint32_t n2 = compact(E, tmp, B.flag.p, B.pos.p, n_pk);
         E.stats.n_pk_reruns += n2;
         if (n2) {
             B.q2.reserve(n2); B.t2.reserve(n2); B.link.reserve(n2); B.s.reserve(n2);
@@ -974,11 +991,9 @@ static void run_plan(Engine &E, SwPlan &P, int mode, int32_t *os, int32_t *oqe, 
     E.stats.sw_algorithmic_bytes += P.alg_bytes;
     E.stats.cells_run += P.cells;
     E.stats.n_sw_runs += P.n;
-    const bool timing = getenv("UC_TIMING") != nullptr;
-    if (timing) fprintf(stderr, "unicore-cluster[timing]: sw pass mode %d: %u pairs, %llu cells, %.2f ms (%llu launches)\n", mode, P.n, (unsigned long long)P.cells, ms, (unsigned long long)launches);
+    if (getenv("UC_TIMING")) fprintf(stderr, "unicore-cluster[timing]: sw pass mode %d: %u pairs, %llu cells, %.2f ms (%llu launches)\n", mode, P.n, (unsigned long long)P.cells, ms, (unsigned long long)launches);
 }
 
-// exact (qEnd, tEnd) by the int32 forward kernel for the gate-passing pairs the packed kernel left ambiguous
 // exact (qEnd, tEnd) for the gate-passing pairs whose end is still unknown (ambiguous end row of the packed kernel, or a
 // mirror that could not take its representative's end): a second forward pass that KNOWS the optimum score (packed
 // MODE 4; int32 kernel for --sw-kernel i32 and for queries beyond the systolic classes)
@@ -990,8 +1005,7 @@ static void fix_ambiguous_ends(Engine &E, uint32_t n2, const uint32_t *q2, const
     hipStream_t s = E.stream;
     B.flag.reserve(n2); B.pos.reserve(n2);
     hipLaunchKernelGGL(amb_flag_kernel, grid_for(n2), dim3(256), 0, s, n2, qe2, B.flag.p);
-    scan_u32(E, tmp, B.flag.p, B.pos.p, n2, false);
-    const uint32_t n3 = scan_total(E, B.flag.p, B.pos.p, n2);
+    const uint32_t n3 = compact(E, tmp, B.flag.p, B.pos.p, n2);
     E.stats.n_pk_reruns += n3;
     if (!n3) return;
     B.q2.reserve(n3); B.t2.reserve(n3); B.link.reserve(n3); B.s.reserve(n3); B.qe.reserve(n3); B.te.reserve(n3); B.sin.reserve(n3);
@@ -1003,7 +1017,7 @@ static void fix_ambiguous_ends(Engine &E, uint32_t n2, const uint32_t *q2, const
     UC_HIP(hipGetLastError());
 }
 
-void free_align_scratch(AlignScratch *p) { delete p; }
+void free_scratch(AlignScratch *p) { delete p; }
 
 // memory pressure inside the gapped stage: the traceback-byte buffer (up to 144 GiB, kept between calls because fresh memory is slow) is dead weight
 // outside the batch loop of a MODE 7 call - the engine's out-of-memory handler gives it back before it gives up
@@ -1011,35 +1025,6 @@ bool release_tb_matrices(AlignScratch *p) {
     if (!p || p->tb_tbm_live || !p->tb_tbm.cap) return false;
     p->tb_tbm.release();
     return true;
-}
-
-// parked between engines like the prefilter's work buffers (uc_prefilter.hip)
-namespace {
-std::mutex g_park_mutex_aln;
-AlignScratch *g_parked_aln[16] = {};
-}  // namespace
-void park_align_scratch(AlignScratch *p, int device) {
-    if (!p) return;
-    const char *e = getenv("UC_KEEP_SCRATCH");
-    if (!(e && e[0] == '0') && device >= 0 && device < 16) {
-        std::lock_guard<std::mutex> g(g_park_mutex_aln);
-        if (!g_parked_aln[device]) { g_parked_aln[device] = p; return; }
-    }
-    delete p;
-}
-AlignScratch *take_parked_align_scratch(int device) {   // nullptr if nothing is parked (uc_release_scratch)
-    if (device < 0 || device >= 16) return nullptr;
-    std::lock_guard<std::mutex> g(g_park_mutex_aln);
-    AlignScratch *p = g_parked_aln[device];
-    g_parked_aln[device] = nullptr;
-    return p;
-}
-AlignScratch *take_align_scratch(int device) {
-    if (device >= 0 && device < 16) {
-        std::lock_guard<std::mutex> g(g_park_mutex_aln);
-        if (AlignScratch *p = g_parked_aln[device]) { g_parked_aln[device] = nullptr; return p; }
-    }
-    return new AlignScratch;
 }
 
 // ---- kernel-level entry point: arbitrary pair list from the host -----------------------------------
@@ -1086,6 +1071,412 @@ void Engine::sw_batch(int mode, const std::vector<PairIn> &pairs, int32_t *score
 }
 
 // ---- stage E5 + E6 for queries [qbegin, qend) of the device-resident hit lists ----------------------
+// one device batch of Engine::align: the queries [qa, qb) and the pair list its passes work on
+struct AlignBatch {
+    uint32_t qbegin, qa, qb;          // qbegin: first query of the call (d_ms is indexed from it)
+    uint32_t n;                       // pairs of the batch (after the length gate)
+    const uint32_t *dq, *dt;
+    uc_aln *alns_b;                   // where record i of the batch's pair list goes
+    uc_aln *alns_list;                // the batch's records in the hit lists (== alns_b unless the length gate compacted the list)
+    bool dedup;
+    int tab;
+    // the directed pair list the gates work on: sorted (query, target) + position in the hit list
+    const uint32_t *Lsq = nullptr, *Lst = nullptr, *Lidx = nullptr;
+    uint32_t n2 = 0;                  // pairs that passed the E-value gate
+};
+
+// rule UC-1/L (optional): the stage works on the pairs the length gate lets through - a compacted copy of the batch's pair list with its own
+// record array; the records return to their places in the hit-list order at the end of the batch, the gated pairs keep all-zero records
+static void length_gate(Engine &E, AlignBatch &B) {
+    AlignScratch &A = scratch_of(E);
+    hipStream_t s = E.stream;
+    const uint32_t n = B.n;
+    A.lg_flag.reserve(n); A.lg_pos.reserve(n);
+    hipLaunchKernelGGL(len_gate_kernel, grid_for(n), dim3(256), 0, s, n, B.dq, B.dt, E.ddb.len, E.p.cov, E.p.cov_mode, A.lg_flag.p);
+    const uint32_t nc = compact(E, A.tmp, A.lg_flag.p, A.lg_pos.p, n);
+    A.lg_q.reserve(std::max<uint32_t>(nc, 1)); A.lg_t.reserve(std::max<uint32_t>(nc, 1)); A.lg_map.reserve(std::max<uint32_t>(nc, 1));
+    A.lg_alns.reserve(std::max<uint32_t>(nc, 1));
+    hipLaunchKernelGGL(len_gate_gather_kernel, grid_for(n), dim3(256), 0, s, n, A.lg_flag.p, A.lg_pos.p, B.dq, B.dt, A.lg_q.p, A.lg_t.p, A.lg_map.p);
+    if (nc) UC_HIP(hipMemsetAsync(A.lg_alns.p, 0, (size_t)nc * sizeof(uc_aln), s));
+    UC_HIP(hipMemsetAsync(B.alns_list, 0, (size_t)n * sizeof(uc_aln), s));
+    B.dq = A.lg_q.p; B.dt = A.lg_t.p; B.alns_b = A.lg_alns.p; B.n = nc;
+}
+
+// forward pass: s0 / qe0 / te0 of every pair, and the directed pair list (Lsq, Lst, Lidx)
+static void forward_pass(Engine &E, AlignBatch &B) {
+    AlignScratch &A = scratch_of(E);
+    hipStream_t s = E.stream;
+    const uint32_t n = B.n;
+    A.s0.reserve(n); A.qe0.reserve(n); A.te0.reserve(n); A.gflag.reserve(n); A.gpos.reserve(n);
+    UC_HIP(hipMemsetAsync(A.d_cells.p, 0, 16, s));
+    if (!B.dedup) {
+        build_plan(E, A.P0, A.tmp, n, B.dq, B.dt, nullptr, nullptr, B.tab);
+        run_plan(E, A.P0, 0, A.s0.p, A.qe0.p, A.te0.p, A.work, A.tmp, /*ovf_only=*/true);
+        E.stats.cells_fwd += A.P0.cells;
+        B.Lsq = A.P0.sq.p; B.Lst = A.P0.st.p; B.Lidx = A.P0.idx.p;
+        return;
+    }
+    // mutual hits share one forward DP, computed in the orientation with the shorter query
+    A.ukey.reserve(n); A.ukey2.reserve(n); A.uidx_in.reserve(n); A.uidx.reserve(n);
+    A.fq.reserve(n); A.ft.reserve(n); A.mirror.reserve(n); A.rep.reserve(n); A.rpos.reserve(n);
+    hipLaunchKernelGGL(ukey_kernel, grid_for(n), dim3(256), 0, s, n, B.dq, B.dt, E.ddb.len, A.ukey.p, A.uidx_in.p);
+    size_t tb = 0;
+    UC_HIP(rocprim::radix_sort_pairs(nullptr, tb, A.ukey.p, A.ukey2.p, A.uidx_in.p, A.uidx.p, (size_t)n, 0u, 49u, s));
+    A.tmp.reserve(tb + 256);
+    UC_HIP(rocprim::radix_sort_pairs(A.tmp.p, tb, A.ukey.p, A.ukey2.p, A.uidx_in.p, A.uidx.p, (size_t)n, 0u, 49u, s));
+    hipLaunchKernelGGL(umark_kernel, grid_for(n), dim3(256), 0, s, n, A.ukey2.p, A.uidx.p, B.dq, B.dt, A.fq.p, A.ft.p, A.mirror.p, A.rep.p);
+    const uint32_t nu = compact(E, A.tmp, A.rep.p, A.rpos.p, n);
+    A.qr.reserve(nu); A.tr.reserve(nu); A.jrep.reserve(nu); A.su.reserve(nu); A.qeu.reserve(nu); A.teu.reserve(nu);
+    hipLaunchKernelGGL(ugather_kernel, grid_for(n), dim3(256), 0, s, n, A.rep.p, A.rpos.p, A.fq.p, A.ft.p, A.qr.p, A.tr.p, A.jrep.p);
+    build_plan(E, A.P0, A.tmp, nu, A.qr.p, A.tr.p, nullptr, nullptr, B.tab);
+    run_plan(E, A.P0, 0, A.su.p, A.qeu.p, A.teu.p, A.work, A.tmp, /*ovf_only=*/true);
+    hipLaunchKernelGGL(uscatter_kernel, grid_for(nu), dim3(256), 0, s, nu, n, A.P0.idx.p, A.jrep.p, A.mirror.p, A.su.p, A.qeu.p, A.teu.p,
+                       packed_prefix(A.P0).pairs, SW_PK_OVF_HOST, A.s0.p, A.qe0.p, A.te0.p);
+    hipLaunchKernelGGL(cells_kernel, grid_for(n), dim3(256), 0, s, n, A.fq.p, A.ft.p, (const uint32_t *)nullptr, E.ddb.len, A.d_cells.p);
+    B.Lsq = A.fq.p; B.Lst = A.ft.p; B.Lidx = A.uidx.p;
+}
+
+// spec UC-1.1: the reversed-query pass only runs for pairs whose forward score reaches the E-value
+// threshold (corrected <= score, so the others cannot pass); their score_rev is reported as 0
+static void rev_correction_pass(Engine &E, AlignBatch &B) {
+    AlignScratch &A = scratch_of(E);
+    hipStream_t s = E.stream;
+    const uint32_t n = B.n;
+    A.s1.reserve(n);
+    UC_HIP(hipMemsetAsync(A.s1.p, 0, (size_t)n * 4, s));
+    hipLaunchKernelGGL(gate_kernel, grid_for(n), dim3(256), 0, s, n, B.Lsq, A.s0.p, (const int32_t *)nullptr, A.d_ms.p, B.qbegin, A.gflag.p);
+    if (B.dedup) {
+        A.rcopy.reserve(n);
+        hipLaunchKernelGGL(cells_kernel, grid_for(n), dim3(256), 0, s, n, B.Lsq, B.Lst, A.gflag.p, E.ddb.len, A.d_cells.p + 1);
+        hipLaunchKernelGGL(rev_dedup_kernel, grid_for(n), dim3(256), 0, s, n, A.mirror.p, A.gflag.p, A.rcopy.p);
+        hipLaunchKernelGGL(rev_unflag_kernel, grid_for(n), dim3(256), 0, s, n, A.rcopy.p, A.gflag.p);
+    }
+    const uint32_t n1 = compact(E, A.tmp, A.gflag.p, A.gpos.p, n);
+    if (n1) {
+        A.q1.reserve(n1); A.t1.reserve(n1); A.link1.reserve(n1); A.s1c.reserve(n1);
+        hipLaunchKernelGGL(pair_gather_kernel, grid_for(n), dim3(256), 0, s, n, A.gflag.p, A.gpos.p, B.Lsq, B.Lst, A.q1.p, A.t1.p, A.link1.p);
+        build_plan(E, A.P1, A.tmp, n1, A.q1.p, A.t1.p, nullptr, nullptr, B.tab);
+        run_plan(E, A.P1, 1, A.s1c.p, nullptr, nullptr, A.work, A.tmp);
+        hipLaunchKernelGGL(rev_putback_kernel, grid_for(n1), dim3(256), 0, s, n1, A.P1.idx.p, A.link1.p, A.s1c.p, A.s1.p);
+        if (!B.dedup) E.stats.cells_rev += A.P1.cells;
+    }
+    if (B.dedup) hipLaunchKernelGGL(rev_copy_kernel, grid_for(n), dim3(256), 0, s, n, A.rcopy.p, A.s1.p);
+}
+
+// E-value gate on the corrected score: the gate passers (q2, t2, qe2, te2, link) with their exact end rows, and the records of every pair
+static void evalue_gate(Engine &E, AlignBatch &B) {
+    AlignScratch &A = scratch_of(E);
+    hipStream_t s = E.stream;
+    const uint32_t n = B.n;
+    const int32_t *s1p = E.p.rev_correction ? A.s1.p : nullptr;
+    hipLaunchKernelGGL(gate_kernel, grid_for(n), dim3(256), 0, s, n, B.Lsq, A.s0.p, s1p, A.d_ms.p, B.qbegin, A.gflag.p);
+    const uint32_t n2 = B.n2 = compact(E, A.tmp, A.gflag.p, A.gpos.p, n);
+    if (n2) {
+        A.q2.reserve(n2); A.t2.reserve(n2); A.qe2.reserve(n2); A.te2.reserve(n2); A.link.reserve(n2);
+        A.s2.reserve(n2); A.q2o.reserve(n2); A.t2o.reserve(n2); A.eflag.reserve(n2); A.epos.reserve(n2);
+        hipLaunchKernelGGL(gate_scatter_kernel, grid_for(n), dim3(256), 0, s, n, A.gflag.p, A.gpos.p, B.Lsq, B.Lst, A.qe0.p, A.te0.p,
+                           A.q2.p, A.t2.p, A.qe2.p, A.te2.p, A.link.p);
+        if (E.p.sw_pk || B.dedup)
+            fix_ambiguous_ends(E, n2, A.q2.p, A.t2.p, A.qe2.p, A.te2.p, A.link.p, A.s0.p, A.qe0.p, A.te0.p, A.work, A.tmp, B.qb - B.qa);
+    }
+    hipLaunchKernelGGL(aln_basic_kernel, grid_for(n), dim3(256), 0, s, n, B.Lidx, A.s0.p, s1p, A.qe0.p, A.te0.p, A.gflag.p, B.alns_b);
+}
+
+// one known-score start pass (packed MODE 6; the optimum of the start pass is the forward score) over the m gate passers flagged in smkeep
+static void known_start_round(Engine &E, const AlignBatch &B, SwPlan &P, uint32_t m, int tab, uint32_t *uniq) {
+    AlignScratch &A = scratch_of(E);
+    hipStream_t s = E.stream;
+    A.q2a.reserve(m); A.t2a.reserve(m); A.qe2a.reserve(m); A.te2a.reserve(m); A.mapa.reserve(m);
+    hipLaunchKernelGGL(sm_gather_kernel, grid_for(B.n2), dim3(256), 0, s, B.n2, A.smkeep.p, A.smpos.p, A.q2.p, A.t2.p, A.qe2.p, A.te2.p,
+                       A.q2a.p, A.t2a.p, A.qe2a.p, A.te2a.p, A.mapa.p);
+    A.sknown.reserve(m);
+    hipLaunchKernelGGL(sm_score_kernel, grid_for(m), dim3(256), 0, s, m, A.mapa.p, A.link.p, A.s0.p, A.sknown.p);
+    build_plan(E, P, A.tmp, m, A.q2a.p, A.t2a.p, A.qe2a.p, A.te2a.p, tab, nullptr, nullptr, A.sknown.p);
+    run_plan(E, P, 6, A.s2s.p, A.q2os.p, A.t2os.p, A.work, A.tmp);
+    hipLaunchKernelGGL(sm_scatter_kernel, grid_for(m), dim3(256), 0, s, m, P.idx.p, A.mapa.p, A.s2s.p, A.q2os.p, A.t2os.p,
+                       A.s2.p, A.q2o.p, A.t2o.p, uniq);
+}
+
+// start pass of the shared-DP path on the packed kernel
+static void start_pass_known(Engine &E, AlignBatch &B) {
+    AlignScratch &A = scratch_of(E);
+    hipStream_t s = E.stream;
+    const uint32_t n2 = B.n2;
+    A.smkeep.reserve(n2); A.smpos.reserve(n2); A.partner.reserve(n2); A.uniq.reserve(n2);
+    UC_HIP(hipMemsetAsync(A.uniq.p, 0, (size_t)n2 * 4, s));
+    hipLaunchKernelGGL(sm_flag_kernel, grid_for(n2), dim3(256), 0, s, n2, A.link.p, A.mirror.p, A.gflag.p, A.gpos.p, A.qe2.p, A.te2.p,
+                       A.qe0.p, A.te0.p, A.smkeep.p, A.partner.p);
+    // round 1: exact in one pass, and it reports whether a single row holds every optimal cell
+    known_start_round(E, B, A.P2, compact(E, A.tmp, A.smkeep.p, A.smpos.p, n2), B.tab, A.uniq.p);
+    hipLaunchKernelGGL(sm_resolve_kernel, grid_for(n2), dim3(256), 0, s, n2, A.partner.p, A.uniq.p, A.s2.p, A.q2o.p, A.t2o.p);
+    // round 2: the mirrors that could not take their partner's result
+    hipLaunchKernelGGL(amb_flag_kernel, grid_for(n2), dim3(256), 0, s, n2, A.q2o.p, A.smkeep.p);
+    const uint32_t n2b = compact(E, A.tmp, A.smkeep.p, A.smpos.p, n2);
+    if (!n2b) return;
+    known_start_round(E, B, A.P2b, n2b, pk_known_tab(n2b, B.qb - B.qa), nullptr);
+    E.stats.n_pk_reruns += n2b;
+}
+
+// start pass; results end up in the natural order of the gate-passer list (iota2 stands for the plan order).  Then the records of the gate
+// passers, the coverage gate and the edge flags (eflag)
+static void start_pass(Engine &E, AlignBatch &B) {
+    AlignScratch &A = scratch_of(E);
+    hipStream_t s = E.stream;
+    const uint32_t n2 = B.n2;
+    A.iota2.reserve(n2); A.s2s.reserve(n2); A.q2os.reserve(n2); A.t2os.reserve(n2);
+    hipLaunchKernelGGL(iota_kernel, grid_for(n2), dim3(256), 0, s, n2, A.iota2.p);
+    UC_HIP(hipMemsetAsync(A.d_cells.p, 0, 8, s));
+    hipLaunchKernelGGL(cells_box_kernel, grid_for(n2), dim3(256), 0, s, n2, A.qe2.p, A.te2.p, A.d_cells.p);
+    if (B.dedup && B.tab == 1) {
+        start_pass_known(E, B);
+    } else {
+        build_plan(E, A.P2, A.tmp, n2, A.q2.p, A.t2.p, A.qe2.p, A.te2.p, B.tab);
+        run_plan(E, A.P2, 2, A.s2s.p, A.q2os.p, A.t2os.p, A.work, A.tmp);
+        hipLaunchKernelGGL(sm_scatter_kernel, grid_for(n2), dim3(256), 0, s, n2, A.P2.idx.p, (const uint32_t *)nullptr, A.s2s.p, A.q2os.p,
+                           A.t2os.p, A.s2.p, A.q2o.p, A.t2o.p, (uint32_t *)nullptr);
+    }
+    unsigned long long hc = 0;
+    UC_HIP(hipMemcpyAsync(&hc, A.d_cells.p, 8, hipMemcpyDeviceToHost, s));
+    UC_HIP(hipStreamSynchronize(s));
+    E.stats.cells_start += hc;
+    hipLaunchKernelGGL(finalize_kernel, grid_for(n2), dim3(256), 0, s, n2, A.iota2.p, A.link.p, B.Lidx, A.q2.p, A.t2.p, A.s2.p,
+                       A.q2o.p, A.t2o.p, E.ddb.len, E.p.cov, E.p.cov_mode, B.alns_b, A.eflag.p, A.mism.p);
+}
+
+// the walk over H bytes needs neighbouring cells within 127 of each other: largest substitution score + gap open
+// (uc_align.hip tb_walk_kernel); anything else takes the int32 pass
+static bool tb_bytes_ok(const Params &p) {
+    int m3 = -128, ma = -128, n3 = 127, na = 127;
+    for (int k = 0; k < 21 * 21; k++) {
+        m3 = std::max<int>(m3, p.S3[k]); ma = std::max<int>(ma, p.SA[k]);
+        n3 = std::min<int>(n3, p.S3[k]); na = std::min<int>(na, p.SA[k]);
+    }
+    return p.gap_open >= p.gap_ext && p.gap_ext >= 0 && m3 + ma + p.gap_open <= 127 && n3 + na >= -127;
+}
+
+constexpr uint32_t TB_GAPS[4] = {0u, 0u, 1u, 0u};   // MODE 3 weights (diagonal, identity, open, extension) of the gap count
+
+// packed MODE 7 for the plan tb_P3 (built in pair order): H bytes of the box's diagonal band (tb_band_of) + walk kernel; queries beyond the
+// systolic classes take int32 MODE 3.  Returns the launches.
+//
+// r05, pk: ONE plan for all flagged pairs of the call, and the byte matrices are produced in batches cut ALONG that plan - a batch is
+// a range of its class-sorted task list that fits the matrix budget, i.e. thousands of tasks of one or two length classes per
+// launch.  (r04 cut the flagged LIST into batches and planned each: every batch then ran all 28 class kernels with a handful of
+// tasks each - 442 batches at nominal configs[3], MODE 7 at 1.5 T cells/s against 5 T for the other passes:
+// profiles/r05/sw_pass_timing_*.txt.)
+static uint64_t tb_run_bytes(Engine &E, int band, const TbBudget &budget) {
+    AlignScratch &A = scratch_of(E);
+    SwPlan &P3 = A.tb_P3;
+    hipStream_t s = E.stream;
+    const auto [n_pk3, nt_pk] = packed_prefix(P3);       // every systolic class of table 1 is packed, and their tasks come first, in pair order
+    uint64_t launches = 0;
+    double tb_ms = 0;
+    unsigned long long total = 0;
+    uint32_t nbatch = 0;
+    if (P3.n > n_pk3) {                                   // long queries: int32 MODE 3 (no matrices)
+        E.timed_ms_begin();
+        launches += launch_plan(E, P3, 7, A.tb_pack3.p, nullptr, nullptr, A.work, nullptr, /*only_long=*/true);
+        if (E.p.want_tb) launches += launch_plan(E, P3, 3, A.tb_gaps3.p, nullptr, nullptr, A.work, TB_GAPS, /*only_long=*/true);
+        tb_ms += E.timed_ms_end();
+    }
+    if (n_pk3) {
+        DevBuf<unsigned long long> &tbsize = A.tb_tbsize, &tboff = A.tb_tboff, &toff = A.tb_toff;
+        DevBuf<uint8_t> &tbm = A.tb_tbm;
+        tbsize.reserve((size_t)n_pk3 + 1); tboff.reserve((size_t)n_pk3 + 1);
+        hipLaunchKernelGGL(tb_size_kernel, grid_for(n_pk3), dim3(256), 0, s, n_pk3, P3.key2.p, P3.segstart.p, P3.ste.p,
+                           P3.sts.p, P3.sqs.p, P3.sqe.p, band, 1, tbsize.p);
+        size_t tbb = 0;
+        UC_HIP(rocprim::exclusive_scan(nullptr, tbb, tbsize.p, tboff.p, 0ull, (size_t)n_pk3, rocprim::plus<unsigned long long>(), s));
+        A.tmp.reserve(tbb + 256);
+        UC_HIP(rocprim::exclusive_scan(A.tmp.p, tbb, tbsize.p, tboff.p, 0ull, (size_t)n_pk3, rocprim::plus<unsigned long long>(), s));
+        // where every task's matrices begin, and its first pair: the host cuts the batches at task boundaries
+        toff.reserve((size_t)nt_pk + 1);
+        hipLaunchKernelGGL(tb_taskoff_kernel, grid_for(nt_pk), dim3(256), 0, s, nt_pk, P3.tasks.p, tboff.p, toff.p);
+        std::vector<unsigned long long> h_toff((size_t)nt_pk + 1);
+        std::vector<SwTask> h_task(nt_pk);
+        unsigned long long lo_ = 0, ls_ = 0;
+        UC_HIP(hipMemcpyAsync(h_toff.data(), toff.p, (size_t)nt_pk * 8, hipMemcpyDeviceToHost, s));
+        UC_HIP(hipMemcpyAsync(h_task.data(), P3.tasks.p, (size_t)nt_pk * sizeof(SwTask), hipMemcpyDeviceToHost, s));
+        UC_HIP(hipMemcpyAsync(&lo_, tboff.p + (n_pk3 - 1), 8, hipMemcpyDeviceToHost, s));
+        UC_HIP(hipMemcpyAsync(&ls_, tbsize.p + (n_pk3 - 1), 8, hipMemcpyDeviceToHost, s));
+        UC_HIP(hipStreamSynchronize(s));
+        total = lo_ + ls_;
+        h_toff[nt_pk] = total;
+        const unsigned long long batch_bytes = budget.batch_bytes(total, tbm.cap);
+        A.tb_tbm_live = true;
+        struct Live { bool &f; ~Live() { f = false; } } live{A.tb_tbm_live};
+        // the batches first, then ONE buffer for the largest of them (r06: every batch that was a little larger than the buffer the first
+        // one had sized took a new ~30 GiB block - 12 allocations of 0.8 s each in a 14 s call at 500 proteomes on a box with untouched memory)
+        std::vector<std::pair<uint32_t, uint32_t>> batches;
+        unsigned long long max_bytes = 0;
+        for (uint32_t t0 = 0; t0 < nt_pk;) {
+            uint32_t t1 = t0 + 1;                      // (a single task always runs, whatever the budget: tests force tiny budgets)
+            while (t1 < nt_pk && h_toff[t1 + 1] - h_toff[t0] <= batch_bytes) t1++;
+            batches.emplace_back(t0, t1);
+            max_bytes = std::max(max_bytes, h_toff[t1] - h_toff[t0]);
+            t0 = t1;
+        }
+        tbm.reserve_exact(std::max<unsigned long long>(max_bytes, std::min<unsigned long long>(total, batch_bytes)) + 64);
+        for (const auto &bt : batches) {
+            const uint32_t t0 = bt.first, t1 = bt.second;
+            const unsigned long long base = h_toff[t0];
+            const uint32_t p0 = h_task[t0].begin, p1 = t1 < nt_pk ? h_task[t1].begin : n_pk3;
+            P3.tbm = tbm.p - base; P3.tboff = tboff.p; P3.tb_band = band;      // (a pair's offset counts from the start of the WHOLE plan)
+            E.timed_ms_begin();
+            launches += launch_plan(E, P3, 7, A.tb_pack3.p, nullptr, nullptr, A.work, nullptr, false, t0, t1, /*skip_long=*/true);
+            hipLaunchKernelGGL(tb_walk_kernel, grid_for(p1 - p0), dim3(256), 0, s, p0, p1, E.ddb, P3.key2.p, P3.st.p, P3.sqs.p, P3.sqe.p,
+                               P3.sts.p, P3.ste.p, P3.saux.p, E.p.gap_open, E.p.gap_ext, band, 1, tbm.p - base, tboff.p, A.tb_pack3.p, A.tb_gaps3.p);
+            tb_ms += E.timed_ms_end();
+            nbatch++;
+        }
+        P3.tbm = nullptr; P3.tboff = nullptr; P3.tb_band = 0;
+    }
+    E.stats.sw_kernel_ms += tb_ms;
+    if (getenv("UC_TIMING")) fprintf(stderr, "unicore-cluster[timing]: sw pass mode 7: %u pairs, %llu cells, %.2f ms (%llu launches), %llu matrix bytes, band %d, %u batch(es)\n",
+                        P3.n, (unsigned long long)P3.cells, tb_ms, (unsigned long long)launches, total, band, nbatch);
+    return launches;
+}
+
+// the traceback statistics of the flagged gate passers: gather, plan, run, apply.  pk: packed MODE 7 (tb_run_bytes); otherwise the int32
+// kernel carries the statistics through the DP (MODE 3, one pass per statistic).  band > 0: the walk marks the pairs whose path left the
+// band in tb_tmiss.
+static void tb_batch(Engine &E, const AlignBatch &B, const uint32_t *flag, bool pk, int band, const TbBudget &budget) {
+    AlignScratch &A = scratch_of(E);
+    hipStream_t s = E.stream;
+    const uint32_t n2 = B.n2;
+    const uint32_t nt = compact(E, A.tmp, flag, A.tb_tpos.p, n2);
+    if (!nt) return;
+    A.tb_q3.reserve(nt); A.tb_t3.reserve(nt); A.tb_src3.reserve(nt); A.tb_qs3.reserve(nt); A.tb_qe3.reserve(nt); A.tb_ts3.reserve(nt); A.tb_te3.reserve(nt);
+    A.tb_pack3.reserve(nt); A.tb_gaps3.reserve(nt); A.tb_sc3.reserve(nt);
+    hipLaunchKernelGGL(tb_gather_kernel, grid_for(n2), dim3(256), 0, s, n2, flag, A.tb_tpos.p, A.iota2.p, A.link.p, B.Lidx, A.q2.p,
+                       A.t2.p, B.alns_b, A.tb_q3.p, A.tb_t3.p, A.tb_qs3.p, A.tb_qe3.p, A.tb_ts3.p, A.tb_te3.p, A.tb_src3.p, A.tb_sc3.p);
+    SwPlan &P3 = A.tb_P3;
+    uint64_t launches = 0;
+    int passes = 1;
+    if (!pk) {
+        build_plan(E, P3, A.tmp, nt, A.tb_q3.p, A.tb_t3.p, A.tb_qe3.p, A.tb_te3.p, 2, A.tb_qs3.p, A.tb_ts3.p);
+        E.timed_ms_begin();
+        launches = launch_plan(E, P3, 3, A.tb_pack3.p, nullptr, nullptr, A.work);
+        if (E.p.want_tb) {   // second statistic of the same traceback: number of gaps (BLAST-tab "gapopen")
+            launches += launch_plan(E, P3, 3, A.tb_gaps3.p, nullptr, nullptr, A.work, TB_GAPS);
+            passes = 2;
+        }
+        E.stats.sw_kernel_ms += E.timed_ms_end();
+    } else {
+        build_plan(E, P3, A.tmp, nt, A.tb_q3.p, A.tb_t3.p, A.tb_qe3.p, A.tb_te3.p, 1, A.tb_qs3.p, A.tb_ts3.p, A.tb_sc3.p, /*lpt=*/false);
+        launches = tb_run_bytes(E, band, budget);
+    }
+    E.stats.sw_kernel_launches += launches;
+    E.stats.sw_algorithmic_bytes += passes * P3.alg_bytes;
+    E.stats.cells_run += passes * P3.cells;
+    E.stats.n_sw_runs += (uint64_t)passes * P3.n;
+    hipLaunchKernelGGL(tb_apply_kernel, grid_for(nt), dim3(256), 0, s, nt, P3.idx.p, A.tb_src3.p, A.tb_pack3.p,
+                       E.p.want_tb ? A.tb_gaps3.p : (const int32_t *)nullptr, A.iota2.p, A.link.p, B.Lidx, E.p.min_seq_id, B.alns_b,
+                       A.eflag.p, A.tb_ttie.p, (pk && band > 0) ? A.tb_tmiss.p : (uint32_t *)nullptr);
+}
+
+// packed MODE 7 for the flagged pairs, in segments of budget.segment_pairs() pairs (TbBudget)
+static void tb_segments(Engine &E, const AlignBatch &B, const uint32_t *flag, int band, const TbBudget &budget) {
+    AlignScratch &A = scratch_of(E);
+    const uint32_t n2 = B.n2, seg = budget.segment_pairs();
+    const uint32_t nlo = compact(E, A.tmp, flag, A.tb_tcpos.p, n2);
+    if (nlo <= seg) { if (nlo) tb_batch(E, B, flag, true, band, budget); return; }
+    for (uint32_t lo = 0; lo < nlo; lo += seg) {
+        hipLaunchKernelGGL(tb_chunk_kernel, grid_for(n2), dim3(256), 0, E.stream, n2, flag, A.tb_tcpos.p, lo, std::min<uint32_t>(nlo, lo + seg), A.tb_tchunk.p);
+        tb_batch(E, B, A.tb_tchunk.p, true, band, budget);
+    }
+}
+
+// the traceback statistics of the flagged gate passers, on the packed kernel where its range and the byte walk allow it
+static void run_tb(Engine &E, const AlignBatch &B, const uint32_t *flag, int band_w, const TbBudget &budget) {
+    AlignScratch &A = scratch_of(E);
+    const uint32_t n2 = B.n2;
+    if (!E.p.sw_pk || !tb_bytes_ok(E.p)) { tb_batch(E, B, flag, false, 0, budget); return; }
+    A.tb_tlo.reserve(n2); A.tb_thi.reserve(n2); A.tb_tmiss.reserve(n2); A.tb_tchunk.reserve(n2); A.tb_tcpos.reserve(n2);
+    hipLaunchKernelGGL(tb_split_kernel, grid_for(n2), dim3(256), 0, E.stream, n2, flag, A.link.p, B.Lidx, B.alns_b, SW_PK_OVF_HOST, A.tb_tlo.p, A.tb_thi.p);
+    tb_batch(E, B, A.tb_thi.p, false, 0, budget);                       // scores beyond the packed range: int32 MODE 3
+    if (band_w > 0) UC_HIP(hipMemsetAsync(A.tb_tmiss.p, 0, (size_t)n2 * 4, E.stream));
+    tb_segments(E, B, A.tb_tlo.p, band_w, budget);
+    if (band_w > 0) tb_segments(E, B, A.tb_tmiss.p, 0, budget);          // tracebacks that left their band: the whole box
+}
+
+// sequence-identity gate / BLAST-tab statistics: (alignment length, identities[, gaps]) of the traceback on
+// the box, for the pairs that passed the coverage gate
+static void traceback_stats(Engine &E, const AlignBatch &B) {
+    AlignScratch &A = scratch_of(E);
+    hipStream_t s = E.stream;
+    const uint32_t n2 = B.n2;
+    // the plans of the passes behind us are dead (their results have been scattered): at sizes where the matrix budget is what is left of the
+    // device (nominal configs[3]: ~35 GB of plan arrays beside ~57 GiB of matrices per batch) they go back before the matrices are sized
+    // (r06, ADVICE r05: only when memory IS short, i.e. when what is free would not give the matrix buffer its full budget (64 GiB = 55 % of 116 GiB) -
+    // re-allocating ~35 GB of plan arrays in the next 256 M-pair batch costs 1-2 s, more than the few batches the room buys: UC_ALLOC_LOG at nominal
+    // configs[3] showed 443 GiB of 1-2 GiB blocks, 10-12 s per call, profiles/r06/c4_nominal_alloc.txt)
+    size_t free_now = 0, total_now = 0;
+    const bool mem_short = hipMemGetInfo(&free_now, &total_now) != hipSuccess || free_now + A.tb_tbm.cap < (120ull << 30);
+    if (n2 >= (8u << 20) && mem_short) {
+        UC_HIP(hipStreamSynchronize(s));
+        A.P1.release(); A.P2.release(); A.P2b.release(); A.rr_P2.release(); A.amb_P3.release();
+        if (B.dedup) A.P0.release();                   // (without sharing, Lsq / Lst / Lidx ARE P0's arrays)
+    }
+    A.tb_trun.reserve(n2); A.tb_tpos.reserve(n2); A.tb_tpart.reserve(n2); A.tb_ttie.reserve(n2);
+    UC_HIP(hipMemsetAsync(A.tb_ttie.p, 0, (size_t)n2 * 4, s));
+    unsigned long long hc = 0;
+    UC_HIP(hipMemsetAsync(A.d_cells.p, 0, 8, s));
+    hipLaunchKernelGGL(cells_tb_kernel, grid_for(n2), dim3(256), 0, s, n2, A.eflag.p, A.link.p, B.Lidx, B.alns_b, A.d_cells.p);
+    UC_HIP(hipMemcpyAsync(&hc, A.d_cells.p, 8, hipMemcpyDeviceToHost, s));
+    UC_HIP(hipStreamSynchronize(s));
+    E.stats.cells_tb += hc;
+    // r05: MODE 7 stores a diagonal band of the box, not the box (tb_band_of); the few pairs whose traceback leaves the band are redone
+    // with everything stored.  UC_TB_BAND = half-width W (default 48; 0 = always the whole box; the tests force 1 and 4)
+    const int band_w = getenv("UC_TB_BAND") ? std::max(0, atoi(getenv("UC_TB_BAND"))) : 48;
+    const TbBudget budget;
+    if (B.dedup) {
+        hipLaunchKernelGGL(tbm_flag_kernel, grid_for(n2), dim3(256), 0, s, n2, A.eflag.p, A.link.p, B.Lidx, A.mirror.p, A.gflag.p, A.gpos.p,
+                           B.alns_b, A.tb_trun.p, A.tb_tpart.p);
+        run_tb(E, B, A.tb_trun.p, band_w, budget);
+        hipLaunchKernelGGL(tbm_resolve_kernel, grid_for(n2), dim3(256), 0, s, n2, A.tb_tpart.p, A.tb_ttie.p, A.link.p, B.Lidx, E.p.min_seq_id,
+                           B.alns_b, A.eflag.p, A.tb_trun.p);
+        run_tb(E, B, A.tb_trun.p, band_w, budget);   // mirrors whose representative had a gap-direction tie on its traceback
+    } else {
+        UC_HIP(hipMemcpyAsync(A.tb_trun.p, A.eflag.p, (size_t)n2 * 4, hipMemcpyDeviceToDevice, s));
+        run_tb(E, B, A.tb_trun.p, band_w, budget);
+    }
+}
+
+// the accepted edges of the batch (ne flagged in eflag / epos) appended to the engine's device edge list
+static void append_edges(Engine &E, const AlignBatch &B, uint32_t ne) {
+    AlignScratch &A = scratch_of(E);
+    hipStream_t s = E.stream;
+    A.d_e.reserve(2 * (size_t)ne);
+    hipLaunchKernelGGL(edge_scatter_kernel, grid_for(B.n2), dim3(256), 0, s, B.n2, A.eflag.p, A.epos.p, A.q2.p, A.t2.p, A.d_e.p);
+    if (E.edges_on_host && !E.edges.empty()) {   // a host list from an earlier call that was read back: continue on the device
+        E.d_edges.reserve(E.edges.size());
+        UC_HIP(hipMemcpyAsync(E.d_edges.p, E.edges.data(), E.edges.size() * 4, hipMemcpyHostToDevice, s));
+        E.n_edges_dev = E.edges.size() / 2;
+    }
+    E.d_edges.grow_preserve(2 * (E.n_edges_dev + ne), 2 * E.n_edges_dev, s);
+    UC_HIP(hipMemcpyAsync(E.d_edges.p + 2 * E.n_edges_dev, A.d_e.p, 2 * (size_t)ne * 4, hipMemcpyDeviceToDevice, s));
+    E.n_edges_dev += ne;
+    E.edges_on_host = false;
+}
+
+// end of a batch: every start-pass score must equal its forward score; the records of a length-gated list go back to the hit-list order
+static void finish_batch(Engine &E, const AlignBatch &B) {
+    AlignScratch &A = scratch_of(E);
+    hipStream_t s = E.stream;
+    uint32_t bad = 0;
+    UC_HIP(hipMemcpyAsync(&bad, A.mism.p, 4, hipMemcpyDeviceToHost, s));
+    UC_HIP(hipStreamSynchronize(s));
+    UC_HIP(hipGetLastError());
+    if (bad) fail(UC_ERR_GENERIC, "start pass score differs from the forward score for %u pairs", bad);
+    E.stats.n_gapped_alignments += B.n;
+    E.stats.n_start_alignments += B.n2;
+    if (B.alns_b != B.alns_list) {
+        hipLaunchKernelGGL(len_gate_putback_kernel, grid_for(B.n), dim3(256), 0, s, B.n, A.lg_map.p, (const uc_aln *)B.alns_b, B.alns_list);
+        UC_HIP(hipStreamSynchronize(s));
+    }
+}
+
 void Engine::align(uint32_t qbegin, uint32_t qend) {
     PressureScope ps(*this, 1);
     if (!have_db) fail(UC_ERR_ARGS, "no database loaded");
@@ -1108,415 +1499,43 @@ void Engine::align(uint32_t qbegin, uint32_t qend) {
         if (m < 0) m = min_score_for(p, (int)h_len[q], dbres);
         h_ms[q - qbegin] = m;
     }
-    if (!aln) aln = take_align_scratch(device);
-    AlignScratch &A = *aln;
-    DevBuf<int32_t> &d_ms = A.d_ms, &s0 = A.s0, &qe0 = A.qe0, &te0 = A.te0, &s1 = A.s1, &s1c = A.s1c, &qe2 = A.qe2, &te2 = A.te2, &s2 = A.s2,
-                    &q2o = A.q2o, &t2o = A.t2o, &work = A.work;
-    DevBuf<uint32_t> &gflag = A.gflag, &gpos = A.gpos, &q1 = A.q1, &t1 = A.t1, &link1 = A.link1, &q2 = A.q2, &t2 = A.t2, &link = A.link,
-                     &eflag = A.eflag, &epos = A.epos, &mism = A.mism, &d_e = A.d_e;
-    DevBuf<uint64_t> &ukey = A.ukey, &ukey2 = A.ukey2;
-    DevBuf<uint32_t> &uidx_in = A.uidx_in, &uidx = A.uidx, &fq = A.fq, &ft = A.ft, &mirror = A.mirror, &rep = A.rep, &rpos = A.rpos, &qr = A.qr,
-                     &tr = A.tr, &jrep = A.jrep, &rcopy = A.rcopy;
-    DevBuf<int32_t> &su = A.su, &qeu = A.qeu, &teu = A.teu, &s2s = A.s2s, &q2os = A.q2os, &t2os = A.t2os, &qe2a = A.qe2a, &te2a = A.te2a,
-                    &sknown = A.sknown;
-    DevBuf<uint32_t> &iota2 = A.iota2, &smkeep = A.smkeep, &smpos = A.smpos, &partner = A.partner, &uniq = A.uniq, &q2a = A.q2a, &t2a = A.t2a,
-                     &mapa = A.mapa;
-    DevBuf<unsigned long long> &d_cells = A.d_cells;
-    d_cells.reserve(2);
-    DevBuf<char> &tmp = A.tmp;
-    SwPlan &P0 = A.P0, &P1 = A.P1, &P2 = A.P2, &P2b = A.P2b;
-    d_ms.reserve(std::max<size_t>(h_ms.size(), 1));
-    if (!h_ms.empty()) UC_HIP(hipMemcpyAsync(d_ms.p, h_ms.data(), h_ms.size() * 4, hipMemcpyHostToDevice, s));
-    mism.reserve(1);
-    UC_HIP(hipMemsetAsync(mism.p, 0, 4, s));
+    AlignScratch &A = scratch_of(*this);
+    A.d_cells.reserve(2);
+    A.d_ms.reserve(std::max<size_t>(h_ms.size(), 1));
+    if (!h_ms.empty()) UC_HIP(hipMemcpyAsync(A.d_ms.p, h_ms.data(), h_ms.size() * 4, hipMemcpyHostToDevice, s));
+    A.mism.reserve(1);
+    UC_HIP(hipMemsetAsync(A.mism.p, 0, 4, s));
 
     const uint64_t CHUNK = 256ull << 20;  // pairs per device batch (~150 B of plan/result state per pair; mutual hits only share a DP inside a batch)
     for (uint32_t qa = qbegin; qa < qend;) {
         uint32_t qb = qa;
         while (qb < qend && (qb == qa || hit_off[qb + 1] - hit_off[qa] <= CHUNK)) qb++;
         const uint64_t b = hit_off[qa];
-        const uint32_t n_listed = (uint32_t)(hit_off[qb] - b);
-        uint32_t n = n_listed;
-        const uint32_t *dq = d_hq.p + b, *dt = d_ht.p + b;
-        uc_aln *alns_b = d_alns.p + b;                 // where record i of the batch's pair list goes
-        if (p.len_gate && p.cov > 0.0f && n) {
-            // rule UC-1/L (optional): the stage works on the pairs the length gate lets through - a compacted copy of the batch's pair list with its own
-            // record array; the records return to their places in the hit-list order at the end of the batch, the gated pairs keep all-zero records
-            DevBuf<uint32_t> &lgq = A.lg_q, &lgt = A.lg_t, &lgmap = A.lg_map, &lgflag = A.lg_flag, &lgpos = A.lg_pos;
-            lgflag.reserve(n); lgpos.reserve(n);
-            hipLaunchKernelGGL(len_gate_kernel, grid_for(n), dim3(256), 0, s, n, dq, dt, ddb.len, p.cov, p.cov_mode, lgflag.p);
-            scan_u32(*this, tmp, lgflag.p, lgpos.p, n, false);
-            const uint32_t nc = scan_total(*this, lgflag.p, lgpos.p, n);
-            lgq.reserve(std::max<uint32_t>(nc, 1)); lgt.reserve(std::max<uint32_t>(nc, 1)); lgmap.reserve(std::max<uint32_t>(nc, 1));
-            A.lg_alns.reserve(std::max<uint32_t>(nc, 1));
-            hipLaunchKernelGGL(len_gate_gather_kernel, grid_for(n), dim3(256), 0, s, n, lgflag.p, lgpos.p, dq, dt, lgq.p, lgt.p, lgmap.p);
-            if (nc) UC_HIP(hipMemsetAsync(A.lg_alns.p, 0, (size_t)nc * sizeof(uc_aln), s));
-            UC_HIP(hipMemsetAsync(d_alns.p + b, 0, (size_t)n * sizeof(uc_aln), s));
-            dq = lgq.p; dt = lgt.p; alns_b = A.lg_alns.p; n = nc;
-        }
-        if (n) {
-            s0.reserve(n); qe0.reserve(n); te0.reserve(n); gflag.reserve(n); gpos.reserve(n);
-            const int tab = p.sw_pk ? 1 : 0;
-            // the directed pair list the gates work on: sorted (query, target) + position in the hit list
-            const uint32_t *Lsq = nullptr, *Lst = nullptr, *Lidx = nullptr;
-            const bool dedup = p.sym_dedup && p.mat_symmetric && n >= 2 && hdb.n <= (1u << 24);
-            UC_HIP(hipMemsetAsync(d_cells.p, 0, 16, s));
-            if (!dedup) {
-                build_plan(*this, P0, tmp, n, dq, dt, nullptr, nullptr, tab);
-                run_plan(*this, P0, 0, s0.p, qe0.p, te0.p, work, tmp, /*ovf_only=*/true);
-                stats.cells_fwd += P0.cells;
-                Lsq = P0.sq.p; Lst = P0.st.p; Lidx = P0.idx.p;
-            } else {
-                // mutual hits share one forward DP, computed in the orientation with the shorter query
-                ukey.reserve(n); ukey2.reserve(n); uidx_in.reserve(n); uidx.reserve(n);
-                fq.reserve(n); ft.reserve(n); mirror.reserve(n); rep.reserve(n); rpos.reserve(n);
-                hipLaunchKernelGGL(ukey_kernel, grid_for(n), dim3(256), 0, s, n, dq, dt, ddb.len, ukey.p, uidx_in.p);
-                size_t tb = 0;
-                UC_HIP(rocprim::radix_sort_pairs(nullptr, tb, ukey.p, ukey2.p, uidx_in.p, uidx.p, (size_t)n, 0u, 49u, s));
-                tmp.reserve(tb + 256);
-                UC_HIP(rocprim::radix_sort_pairs(tmp.p, tb, ukey.p, ukey2.p, uidx_in.p, uidx.p, (size_t)n, 0u, 49u, s));
-                hipLaunchKernelGGL(umark_kernel, grid_for(n), dim3(256), 0, s, n, ukey2.p, uidx.p, dq, dt, fq.p, ft.p, mirror.p, rep.p);
-                scan_u32(*this, tmp, rep.p, rpos.p, n, false);
-                const uint32_t nu = scan_total(*this, rep.p, rpos.p, n);
-                qr.reserve(nu); tr.reserve(nu); jrep.reserve(nu); su.reserve(nu); qeu.reserve(nu); teu.reserve(nu);
-                hipLaunchKernelGGL(ugather_kernel, grid_for(n), dim3(256), 0, s, n, rep.p, rpos.p, fq.p, ft.p, qr.p, tr.p, jrep.p);
-                build_plan(*this, P0, tmp, nu, qr.p, tr.p, nullptr, nullptr, tab);
-                run_plan(*this, P0, 0, su.p, qeu.p, teu.p, work, tmp, /*ovf_only=*/true);
-                uint32_t n_pk0 = 0;   // packed classes form a prefix of the plan's sorted pair list
-                {
-                    const ClassTable &ct = h_tab[P0.tab];
-                    int npk = 0;
-                    while (npk < ct.n && ct.pk[npk]) npk++;
-                    n_pk0 = P0.pair_base[npk];
-                }
-                hipLaunchKernelGGL(uscatter_kernel, grid_for(nu), dim3(256), 0, s, nu, n, P0.idx.p, jrep.p, mirror.p, su.p, qeu.p, teu.p,
-                                   n_pk0, SW_PK_OVF_HOST, s0.p, qe0.p, te0.p);
-                hipLaunchKernelGGL(cells_kernel, grid_for(n), dim3(256), 0, s, n, fq.p, ft.p, (const uint32_t *)nullptr, ddb.len, d_cells.p);
-                Lsq = fq.p; Lst = ft.p; Lidx = uidx.p;
-            }
-            if (p.rev_correction) {
-                // spec UC-1.1: the reversed-query pass only runs for pairs whose forward score reaches the E-value
-                // threshold (corrected <= score, so the others cannot pass); their score_rev is reported as 0
-                s1.reserve(n);
-                UC_HIP(hipMemsetAsync(s1.p, 0, (size_t)n * 4, s));
-                hipLaunchKernelGGL(gate_kernel, grid_for(n), dim3(256), 0, s, n, Lsq, s0.p, (const int32_t *)nullptr, d_ms.p, qbegin, gflag.p);
-                if (dedup) {
-                    rcopy.reserve(n);
-                    hipLaunchKernelGGL(cells_kernel, grid_for(n), dim3(256), 0, s, n, Lsq, Lst, gflag.p, ddb.len, d_cells.p + 1);
-                    hipLaunchKernelGGL(rev_dedup_kernel, grid_for(n), dim3(256), 0, s, n, mirror.p, gflag.p, rcopy.p);
-                    hipLaunchKernelGGL(rev_unflag_kernel, grid_for(n), dim3(256), 0, s, n, rcopy.p, gflag.p);
-                }
-                scan_u32(*this, tmp, gflag.p, gpos.p, n, false);
-                const uint32_t n1 = scan_total(*this, gflag.p, gpos.p, n);
-                if (n1) {
-                    q1.reserve(n1); t1.reserve(n1); link1.reserve(n1); s1c.reserve(n1);
-                    hipLaunchKernelGGL(pair_gather_kernel, grid_for(n), dim3(256), 0, s, n, gflag.p, gpos.p, Lsq, Lst, q1.p, t1.p, link1.p);
-                    build_plan(*this, P1, tmp, n1, q1.p, t1.p, nullptr, nullptr, tab);
-                    run_plan(*this, P1, 1, s1c.p, nullptr, nullptr, work, tmp);
-                    hipLaunchKernelGGL(rev_putback_kernel, grid_for(n1), dim3(256), 0, s, n1, P1.idx.p, link1.p, s1c.p, s1.p);
-                    if (!dedup) stats.cells_rev += P1.cells;
-                }
-                if (dedup) hipLaunchKernelGGL(rev_copy_kernel, grid_for(n), dim3(256), 0, s, n, rcopy.p, s1.p);
-            }
-            if (dedup) {
-                unsigned long long hc[2] = {0, 0};
-                UC_HIP(hipMemcpyAsync(hc, d_cells.p, 16, hipMemcpyDeviceToHost, s));
-                UC_HIP(hipStreamSynchronize(s));
-                stats.cells_fwd += hc[0];
-                stats.cells_rev += hc[1];
-            }
-            const int32_t *s1p = p.rev_correction ? s1.p : nullptr;
-            hipLaunchKernelGGL(gate_kernel, grid_for(n), dim3(256), 0, s, n, Lsq, s0.p, s1p, d_ms.p, qbegin, gflag.p);
-            scan_u32(*this, tmp, gflag.p, gpos.p, n, false);
-            const uint32_t n2 = scan_total(*this, gflag.p, gpos.p, n);
-            if (n2) {
-                q2.reserve(n2); t2.reserve(n2); qe2.reserve(n2); te2.reserve(n2); link.reserve(n2);
-                s2.reserve(n2); q2o.reserve(n2); t2o.reserve(n2); eflag.reserve(n2); epos.reserve(n2);
-                hipLaunchKernelGGL(gate_scatter_kernel, grid_for(n), dim3(256), 0, s, n, gflag.p, gpos.p, Lsq, Lst, qe0.p, te0.p,
-                                   q2.p, t2.p, qe2.p, te2.p, link.p);
-                if (p.sw_pk || dedup) fix_ambiguous_ends(*this, n2, q2.p, t2.p, qe2.p, te2.p, link.p, s0.p, qe0.p, te0.p, work, tmp, qb - qa);
-            }
-            hipLaunchKernelGGL(aln_basic_kernel, grid_for(n), dim3(256), 0, s, n, Lidx, s0.p, s1p, qe0.p, te0.p, gflag.p, alns_b);
-            if (n2) {
-                // start pass; results end up in the natural order of the gate-passer list (iota2 stands for the plan order)
-                iota2.reserve(n2); s2s.reserve(n2); q2os.reserve(n2); t2os.reserve(n2);
-                hipLaunchKernelGGL(iota_kernel, grid_for(n2), dim3(256), 0, s, n2, iota2.p);
-                UC_HIP(hipMemsetAsync(d_cells.p, 0, 8, s));
-                hipLaunchKernelGGL(cells_box_kernel, grid_for(n2), dim3(256), 0, s, n2, qe2.p, te2.p, d_cells.p);
-                if (dedup && tab == 1) {
-                    smkeep.reserve(n2); smpos.reserve(n2); partner.reserve(n2); uniq.reserve(n2);
-                    UC_HIP(hipMemsetAsync(uniq.p, 0, (size_t)n2 * 4, s));
-                    hipLaunchKernelGGL(sm_flag_kernel, grid_for(n2), dim3(256), 0, s, n2, link.p, mirror.p, gflag.p, gpos.p, qe2.p, te2.p,
-                                       qe0.p, te0.p, smkeep.p, partner.p);
-                    scan_u32(*this, tmp, smkeep.p, smpos.p, n2, false);
-                    const uint32_t n2a = scan_total(*this, smkeep.p, smpos.p, n2);
-                    q2a.reserve(n2a); t2a.reserve(n2a); qe2a.reserve(n2a); te2a.reserve(n2a); mapa.reserve(n2a);
-                    hipLaunchKernelGGL(sm_gather_kernel, grid_for(n2), dim3(256), 0, s, n2, smkeep.p, smpos.p, q2.p, t2.p, qe2.p, te2.p,
-                                       q2a.p, t2a.p, qe2a.p, te2a.p, mapa.p);
-                    // round 1: known-score start pass (packed MODE 6; the optimum of the start pass is the forward score) - exact
-                    // in one pass, and it reports whether a single row holds every optimal cell
-                    sknown.reserve(n2a);
-                    hipLaunchKernelGGL(sm_score_kernel, grid_for(n2a), dim3(256), 0, s, n2a, mapa.p, link.p, s0.p, sknown.p);
-                    build_plan(*this, P2, tmp, n2a, q2a.p, t2a.p, qe2a.p, te2a.p, tab, nullptr, nullptr, sknown.p);
-                    run_plan(*this, P2, 6, s2s.p, q2os.p, t2os.p, work, tmp);
-                    hipLaunchKernelGGL(sm_scatter_kernel, grid_for(n2a), dim3(256), 0, s, n2a, P2.idx.p, mapa.p, s2s.p, q2os.p, t2os.p,
-                                       s2.p, q2o.p, t2o.p, uniq.p);
-                    hipLaunchKernelGGL(sm_resolve_kernel, grid_for(n2), dim3(256), 0, s, n2, partner.p, uniq.p, s2.p, q2o.p, t2o.p);
-                    // round 2: the mirrors that could not take their partner's result
-                    hipLaunchKernelGGL(amb_flag_kernel, grid_for(n2), dim3(256), 0, s, n2, q2o.p, smkeep.p);
-                    scan_u32(*this, tmp, smkeep.p, smpos.p, n2, false);
-                    const uint32_t n2b = scan_total(*this, smkeep.p, smpos.p, n2);
-                    if (n2b) {
-                        q2a.reserve(n2b); t2a.reserve(n2b); qe2a.reserve(n2b); te2a.reserve(n2b); mapa.reserve(n2b);
-                        hipLaunchKernelGGL(sm_gather_kernel, grid_for(n2), dim3(256), 0, s, n2, smkeep.p, smpos.p, q2.p, t2.p, qe2.p, te2.p,
-                                           q2a.p, t2a.p, qe2a.p, te2a.p, mapa.p);
-                        sknown.reserve(n2b);
-                        hipLaunchKernelGGL(sm_score_kernel, grid_for(n2b), dim3(256), 0, s, n2b, mapa.p, link.p, s0.p, sknown.p);
-                        build_plan(*this, P2b, tmp, n2b, q2a.p, t2a.p, qe2a.p, te2a.p, pk_known_tab(n2b, qb - qa), nullptr, nullptr, sknown.p);
-                        run_plan(*this, P2b, 6, s2s.p, q2os.p, t2os.p, work, tmp);   // known-score start pass (packed MODE 6)
-                        hipLaunchKernelGGL(sm_scatter_kernel, grid_for(n2b), dim3(256), 0, s, n2b, P2b.idx.p, mapa.p, s2s.p, q2os.p, t2os.p,
-                                           s2.p, q2o.p, t2o.p, (uint32_t *)nullptr);
-                        stats.n_pk_reruns += n2b;
-                    }
-                } else {
-                    build_plan(*this, P2, tmp, n2, q2.p, t2.p, qe2.p, te2.p, tab);
-                    run_plan(*this, P2, 2, s2s.p, q2os.p, t2os.p, work, tmp);
-                    hipLaunchKernelGGL(sm_scatter_kernel, grid_for(n2), dim3(256), 0, s, n2, P2.idx.p, (const uint32_t *)nullptr, s2s.p, q2os.p,
-                                       t2os.p, s2.p, q2o.p, t2o.p, (uint32_t *)nullptr);
-                }
-                {
-                    unsigned long long hc = 0;
-                    UC_HIP(hipMemcpyAsync(&hc, d_cells.p, 8, hipMemcpyDeviceToHost, s));
-                    UC_HIP(hipStreamSynchronize(s));
-                    stats.cells_start += hc;
-                }
-                hipLaunchKernelGGL(finalize_kernel, grid_for(n2), dim3(256), 0, s, n2, iota2.p, link.p, Lidx, q2.p, t2.p, s2.p,
-                                   q2o.p, t2o.p, ddb.len, p.cov, p.cov_mode, alns_b, eflag.p, mism.p);
-                scan_u32(*this, tmp, eflag.p, epos.p, n2, false);
-                uint32_t ne = scan_total(*this, eflag.p, epos.p, n2);
-                if ((p.min_seq_id > 0.0f || p.want_tb) && ne) {
-                    // sequence-identity gate / BLAST-tab statistics: (alignment length, identities[, gaps]) of the traceback on
-                    // the box, computed by the MODE 3 pass of the int32 kernel for the pairs that passed the coverage gate
-                    DevBuf<uint32_t> &q3 = A.tb_q3, &t3 = A.tb_t3, &src3 = A.tb_src3, &trun = A.tb_trun, &tpos = A.tb_tpos, &tpart = A.tb_tpart,
-                                     &ttie = A.tb_ttie, &tlo = A.tb_tlo, &thi = A.tb_thi, &tmiss = A.tb_tmiss, &tchunk = A.tb_tchunk, &tcpos = A.tb_tcpos;
-                    DevBuf<unsigned long long> &tbsize = A.tb_tbsize, &tboff = A.tb_tboff;
-                    DevBuf<uint8_t> &tbm = A.tb_tbm;
-                    DevBuf<int32_t> &qs3 = A.tb_qs3, &qe3 = A.tb_qe3, &ts3 = A.tb_ts3, &te3 = A.tb_te3, &pack3 = A.tb_pack3, &gaps3 = A.tb_gaps3, &sc3 = A.tb_sc3;
-                    SwPlan &P3 = A.tb_P3;
-                    // the plans of the passes behind us are dead (their results have been scattered): at sizes where the matrix budget is what is left of the
-                    // device (nominal configs[3]: ~35 GB of plan arrays beside ~57 GiB of matrices per batch) they go back before the matrices are sized
-                    // (r06, ADVICE r05: only when memory IS short, i.e. when what is free would not give the matrix buffer its full budget (64 GiB = 55 % of 116 GiB) -
-                    // re-allocating ~35 GB of plan arrays in the next 256 M-pair batch costs 1-2 s, more than the few batches the room buys: UC_ALLOC_LOG at nominal
-                    // configs[3] showed 443 GiB of 1-2 GiB blocks, 10-12 s per call, profiles/r06/c4_nominal_alloc.txt)
-                    size_t free_now = 0, total_now = 0;
-                    const bool mem_short = hipMemGetInfo(&free_now, &total_now) != hipSuccess || free_now + A.tb_tbm.cap < (120ull << 30);
-                    if (n2 >= (8u << 20) && mem_short) {
-                        UC_HIP(hipStreamSynchronize(s));
-                        P1.release(); P2.release(); P2b.release(); A.rr_P2.release(); A.amb_P3.release();
-                        if (dedup) P0.release();                   // (without sharing, Lsq / Lst / Lidx ARE P0's arrays)
-                    }
-                    trun.reserve(n2); tpos.reserve(n2); tpart.reserve(n2); ttie.reserve(n2);
-                    UC_HIP(hipMemsetAsync(ttie.p, 0, (size_t)n2 * 4, s));
-                    {
-                        unsigned long long hc = 0;
-                        UC_HIP(hipMemsetAsync(d_cells.p, 0, 8, s));
-                        hipLaunchKernelGGL(cells_tb_kernel, grid_for(n2), dim3(256), 0, s, n2, eflag.p, link.p, Lidx, alns_b, d_cells.p);
-                        UC_HIP(hipMemcpyAsync(&hc, d_cells.p, 8, hipMemcpyDeviceToHost, s));
-                        UC_HIP(hipStreamSynchronize(s));
-                        stats.cells_tb += hc;
-                    }
-                    // the flagged entries: gather, plan, run, apply.  pk: packed MODE 7 (H bytes of the box's diagonal band, tb_band_of) + walk
-                    // kernel; otherwise the int32 kernel carries the statistics through the DP (MODE 3, one pass per statistic).
-                    //
-                    // r05, pk: ONE plan for all flagged pairs of the call, and the byte matrices are produced in batches cut ALONG that plan - a batch is
-                    // a range of its class-sorted task list that fits the matrix budget, i.e. thousands of tasks of one or two length classes per
-                    // launch.  (r04 cut the flagged LIST into batches and planned each: every batch then ran all 28 class kernels with a handful of
-                    // tasks each - 442 batches at nominal configs[3], MODE 7 at 1.5 T cells/s against 5 T for the other passes:
-                    // profiles/r05/sw_pass_timing_*.txt.)  band > 0: the walk marks the pairs whose path left the band in tmiss.
-                    auto tb_batch = [&](const uint32_t *flag, bool pk, int band) {
-                        scan_u32(*this, tmp, flag, tpos.p, n2, false);
-                        const uint32_t nt = scan_total(*this, flag, tpos.p, n2);
-                        if (!nt) return;
-                        q3.reserve(nt); t3.reserve(nt); src3.reserve(nt); qs3.reserve(nt); qe3.reserve(nt); ts3.reserve(nt); te3.reserve(nt);
-                        pack3.reserve(nt); gaps3.reserve(nt); sc3.reserve(nt);
-                        hipLaunchKernelGGL(tb_gather_kernel, grid_for(n2), dim3(256), 0, s, n2, flag, tpos.p, iota2.p, link.p, Lidx, q2.p,
-                                           t2.p, alns_b, q3.p, t3.p, qs3.p, qe3.p, ts3.p, te3.p, src3.p, sc3.p);
-                        static const uint32_t tb_gaps[4] = {0u, 0u, 1u, 0u};
-                        uint64_t launches = 0;
-                        int passes = 1;
-                        const bool timing = getenv("UC_TIMING") != nullptr;
-                        if (!pk) {
-                            build_plan(*this, P3, tmp, nt, q3.p, t3.p, qe3.p, te3.p, 2, qs3.p, ts3.p);
-                            timed_ms_begin();
-                            launches = launch_plan(*this, P3, 3, pack3.p, nullptr, nullptr, work);
-                            if (p.want_tb) {   // second statistic of the same traceback: number of gaps (BLAST-tab "gapopen")
-                                launches += launch_plan(*this, P3, 3, gaps3.p, nullptr, nullptr, work, tb_gaps);
-                                passes = 2;
-                            }
-                            stats.sw_kernel_ms += timed_ms_end();
-                        } else {
-                            build_plan(*this, P3, tmp, nt, q3.p, t3.p, qe3.p, te3.p, 1, qs3.p, ts3.p, sc3.p, /*lpt=*/false);
-                            const uint32_t n_pk3 = P3.pair_base[h_tab[1].n];      // every systolic class of table 1 is packed
-                            const uint32_t nt_pk = P3.task_base[h_tab[1].n];      // ... and their tasks come first, in pair order
-                            double tb_ms = 0;
-                            unsigned long long total = 0;
-                            uint32_t nbatch = 0;
-                            if (P3.n > n_pk3) {                                   // long queries: int32 MODE 3 (no matrices)
-                                timed_ms_begin();
-                                launches += launch_plan(*this, P3, 7, pack3.p, nullptr, nullptr, work, nullptr, /*only_long=*/true);
-                                if (p.want_tb) launches += launch_plan(*this, P3, 3, gaps3.p, nullptr, nullptr, work, tb_gaps, /*only_long=*/true);
-                                tb_ms += timed_ms_end();
-                            }
-                            if (n_pk3) {
-                                tbsize.reserve((size_t)n_pk3 + 1); tboff.reserve((size_t)n_pk3 + 1);
-                                hipLaunchKernelGGL(tb_size_kernel, grid_for(n_pk3), dim3(256), 0, s, n_pk3, P3.key2.p, P3.segstart.p, P3.ste.p,
-                                                   P3.sts.p, P3.sqs.p, P3.sqe.p, band, 1, tbsize.p);
-                                size_t tbb = 0;
-                                UC_HIP(rocprim::exclusive_scan(nullptr, tbb, tbsize.p, tboff.p, 0ull, (size_t)n_pk3, rocprim::plus<unsigned long long>(), s));
-                                tmp.reserve(tbb + 256);
-                                UC_HIP(rocprim::exclusive_scan(tmp.p, tbb, tbsize.p, tboff.p, 0ull, (size_t)n_pk3, rocprim::plus<unsigned long long>(), s));
-                                // where every task's matrices begin, and its first pair: the host cuts the batches at task boundaries
-                                DevBuf<unsigned long long> &toff = A.tb_toff;
-                                toff.reserve((size_t)nt_pk + 1);
-                                hipLaunchKernelGGL(tb_taskoff_kernel, grid_for(nt_pk), dim3(256), 0, s, nt_pk, P3.tasks.p, tboff.p, toff.p);
-                                std::vector<unsigned long long> h_toff((size_t)nt_pk + 1);
-                                std::vector<SwTask> h_task(nt_pk);
-                                unsigned long long lo_ = 0, ls_ = 0;
-                                UC_HIP(hipMemcpyAsync(h_toff.data(), toff.p, (size_t)nt_pk * 8, hipMemcpyDeviceToHost, s));
-                                UC_HIP(hipMemcpyAsync(h_task.data(), P3.tasks.p, (size_t)nt_pk * sizeof(SwTask), hipMemcpyDeviceToHost, s));
-                                UC_HIP(hipMemcpyAsync(&lo_, tboff.p + (n_pk3 - 1), 8, hipMemcpyDeviceToHost, s));
-                                UC_HIP(hipMemcpyAsync(&ls_, tbsize.p + (n_pk3 - 1), 8, hipMemcpyDeviceToHost, s));
-                                UC_HIP(hipStreamSynchronize(s));
-                                total = lo_ + ls_;
-                                h_toff[nt_pk] = total;
-                                // Fresh device memory is not free: 25-60 ms per GiB on a box whose memory has been used before (tools/ubench/alloc_cost.hip,
-                                // profiles/r04/alloc_*.log), so a call whose matrices would fit a few times over takes a third of them at a time, at least
-                                // 16 GiB (about the buffer r04 took for an eighth of its whole-box matrices).  What the buffer already holds is free to use.
-                                unsigned long long budget = tb_budget_bytes(tbm.cap);
-                                if (!getenv("UC_TB_BUDGET_MB")) {
-                                    const unsigned long long want = std::max<unsigned long long>(16ull << 30, total / 3);
-                                    budget = std::min(budget, std::max<unsigned long long>(want, (unsigned long long)tbm.cap));
-                                    // a buffer of a useful size that is there already IS the budget: a segment whose batches would be a little larger than
-                                    // the last one's must not take a new block (r06)
-                                    if (tbm.cap >= ((size_t)8 << 30)) budget = (unsigned long long)tbm.cap - 64;
-                                }
-                                A.tb_tbm_live = true;
-                                struct Live { bool &f; ~Live() { f = false; } } live{A.tb_tbm_live};
-                                // the batches first, then ONE buffer for the largest of them (r06: every batch that was a little larger than the buffer the first
-                                // one had sized took a new ~30 GiB block - 12 allocations of 0.8 s each in a 14 s call at 500 proteomes on a box with untouched memory)
-                                std::vector<std::pair<uint32_t, uint32_t>> batches;
-                                unsigned long long max_bytes = 0;
-                                for (uint32_t t0 = 0; t0 < nt_pk;) {
-                                    uint32_t t1 = t0 + 1;                      // (a single task always runs, whatever the budget: tests force tiny budgets)
-                                    while (t1 < nt_pk && h_toff[t1 + 1] - h_toff[t0] <= budget) t1++;
-                                    batches.emplace_back(t0, t1);
-                                    max_bytes = std::max(max_bytes, h_toff[t1] - h_toff[t0]);
-                                    t0 = t1;
-                                }
-                                tbm.reserve_exact(std::max<unsigned long long>(max_bytes, std::min<unsigned long long>(total, budget)) + 64);
-                                for (const auto &bt : batches) {
-                                    const uint32_t t0 = bt.first, t1 = bt.second;
-                                    const unsigned long long base = h_toff[t0];
-                                    const uint32_t p0 = h_task[t0].begin, p1 = t1 < nt_pk ? h_task[t1].begin : n_pk3;
-                                    P3.tbm = tbm.p - base; P3.tboff = tboff.p; P3.tb_band = band;      // (a pair's offset counts from the start of the WHOLE plan)
-                                    timed_ms_begin();
-                                    launches += launch_plan(*this, P3, 7, pack3.p, nullptr, nullptr, work, nullptr, false, t0, t1, /*skip_long=*/true);
-                                    hipLaunchKernelGGL(tb_walk_kernel, grid_for(p1 - p0), dim3(256), 0, s, p0, p1, ddb, P3.key2.p, P3.st.p, P3.sqs.p, P3.sqe.p,
-                                                       P3.sts.p, P3.ste.p, P3.saux.p, p.gap_open, p.gap_ext, band, 1, tbm.p - base, tboff.p, pack3.p, gaps3.p);
-                                    tb_ms += timed_ms_end();
-                                    nbatch++;
-                                }
-                                P3.tbm = nullptr; P3.tboff = nullptr; P3.tb_band = 0;
-                            }
-                            stats.sw_kernel_ms += tb_ms;
-                            if (timing) fprintf(stderr, "unicore-cluster[timing]: sw pass mode 7: %u pairs, %llu cells, %.2f ms (%llu launches), %llu matrix bytes, band %d, %u batch(es)\n",
-                                                P3.n, (unsigned long long)P3.cells, tb_ms, (unsigned long long)launches, total, band, nbatch);
-                        }
-                        stats.sw_kernel_launches += launches;
-                        stats.sw_algorithmic_bytes += passes * P3.alg_bytes;
-                        stats.cells_run += passes * P3.cells;
-                        stats.n_sw_runs += (uint64_t)passes * P3.n;
-                        hipLaunchKernelGGL(tb_apply_kernel, grid_for(nt), dim3(256), 0, s, nt, P3.idx.p, src3.p, pack3.p,
-                                           p.want_tb ? gaps3.p : (const int32_t *)nullptr, iota2.p, link.p, Lidx, p.min_seq_id, alns_b,
-                                           eflag.p, ttie.p, (pk && band > 0) ? tmiss.p : (uint32_t *)nullptr);
-                    };
-                    // the walk over H bytes needs neighbouring cells within 127 of each other: largest substitution score + gap open
-                    // (uc_align.hip tb_walk_kernel); anything else takes the int32 pass
-                    bool tb_bytes_ok = p.gap_open >= p.gap_ext && p.gap_ext >= 0;
-                    {
-                        int m3 = -128, ma = -128, n3 = 127, na = 127;
-                        for (int k = 0; k < 21 * 21; k++) {
-                            m3 = std::max<int>(m3, p.S3[k]); ma = std::max<int>(ma, p.SA[k]);
-                            n3 = std::min<int>(n3, p.S3[k]); na = std::min<int>(na, p.SA[k]);
-                        }
-                        tb_bytes_ok = tb_bytes_ok && m3 + ma + p.gap_open <= 127 && n3 + na >= -127;
-                    }
-                    // r05: MODE 7 stores a diagonal band of the box, not the box (tb_band_of); the few pairs whose traceback leaves the band are redone
-                    // with everything stored.  UC_TB_BAND = half-width W (default 48; 0 = always the whole box; the tests force 1 and 4)
-                    const int tb_band_w = getenv("UC_TB_BAND") ? std::max(0, atoi(getenv("UC_TB_BAND"))) : 48;
-                    // the plan of a MODE 7 call costs ~110 B per pair beside the matrices: the flagged list is worked off in segments of 32 M pairs (nominal
-                    // configs[3]: 170 M flagged pairs per 256 M-pair batch of the stage), each planned and cut into matrix batches on its own; a segment
-                    // still holds ~1.5 TB of matrices, i.e. dozens of one-class batches.  (Tests: a forced matrix budget also forces 1000-pair segments.)
-                    auto tb_pk = [&](const uint32_t *flag, int band) {
-                        const uint32_t seg = getenv("UC_TB_BUDGET_MB") ? 1000u : (32u << 20);
-                        scan_u32(*this, tmp, flag, tcpos.p, n2, false);
-                        const uint32_t nlo = scan_total(*this, flag, tcpos.p, n2);
-                        if (nlo <= seg) { if (nlo) tb_batch(flag, true, band); return; }
-                        for (uint32_t lo = 0; lo < nlo; lo += seg) {
-                            hipLaunchKernelGGL(tb_chunk_kernel, grid_for(n2), dim3(256), 0, s, n2, flag, tcpos.p, lo, std::min<uint32_t>(nlo, lo + seg), tchunk.p);
-                            tb_batch(tchunk.p, true, band);
-                        }
-                    };
-                    auto run_tb = [&](const uint32_t *flag) {
-                        if (!p.sw_pk || !tb_bytes_ok) { tb_batch(flag, false, 0); return; }
-                        tlo.reserve(n2); thi.reserve(n2); tmiss.reserve(n2); tchunk.reserve(n2); tcpos.reserve(n2);
-                        hipLaunchKernelGGL(tb_split_kernel, grid_for(n2), dim3(256), 0, s, n2, flag, link.p, Lidx, alns_b, SW_PK_OVF_HOST, tlo.p, thi.p);
-                        tb_batch(thi.p, false, 0);                            // scores beyond the packed range: int32 MODE 3
-                        if (tb_band_w > 0) UC_HIP(hipMemsetAsync(tmiss.p, 0, (size_t)n2 * 4, s));
-                        tb_pk(tlo.p, tb_band_w);
-                        if (tb_band_w > 0) tb_pk(tmiss.p, 0);                 // tracebacks that left their band: the whole box
-                    };
-                    if (dedup) {
-                        hipLaunchKernelGGL(tbm_flag_kernel, grid_for(n2), dim3(256), 0, s, n2, eflag.p, link.p, Lidx, mirror.p, gflag.p, gpos.p,
-                                           alns_b, trun.p, tpart.p);
-                        run_tb(trun.p);
-                        hipLaunchKernelGGL(tbm_resolve_kernel, grid_for(n2), dim3(256), 0, s, n2, tpart.p, ttie.p, link.p, Lidx, p.min_seq_id,
-                                           alns_b, eflag.p, trun.p);
-                        run_tb(trun.p);   // mirrors whose representative had a gap-direction tie on its traceback
-                    } else {
-                        UC_HIP(hipMemcpyAsync(trun.p, eflag.p, (size_t)n2 * 4, hipMemcpyDeviceToDevice, s));
-                        run_tb(trun.p);
-                    }
-                    scan_u32(*this, tmp, eflag.p, epos.p, n2, false);
-                    ne = scan_total(*this, eflag.p, epos.p, n2);
-                }
-                if (ne) {
-                    d_e.reserve(2 * (size_t)ne);
-                    hipLaunchKernelGGL(edge_scatter_kernel, grid_for(n2), dim3(256), 0, s, n2, eflag.p, epos.p, q2.p, t2.p, d_e.p);
-                    if (edges_on_host && !edges.empty()) {   // a host list from an earlier call that was read back: continue on the device
-                        d_edges.reserve(edges.size());
-                        UC_HIP(hipMemcpyAsync(d_edges.p, edges.data(), edges.size() * 4, hipMemcpyHostToDevice, s));
-                        n_edges_dev = edges.size() / 2;
-                    }
-                    d_edges.grow_preserve(2 * (n_edges_dev + ne), 2 * n_edges_dev, s);
-                    UC_HIP(hipMemcpyAsync(d_edges.p + 2 * n_edges_dev, d_e.p, 2 * (size_t)ne * 4, hipMemcpyDeviceToDevice, s));
-                    n_edges_dev += ne;
-                    edges_on_host = false;
-                }
-            }
-            uint32_t bad = 0;
-            UC_HIP(hipMemcpyAsync(&bad, mism.p, 4, hipMemcpyDeviceToHost, s));
-            UC_HIP(hipStreamSynchronize(s));
-            UC_HIP(hipGetLastError());
-            if (bad) fail(UC_ERR_GENERIC, "start pass score differs from the forward score for %u pairs", bad);
-            stats.n_gapped_alignments += n;
-            stats.n_start_alignments += n2;
-            if (alns_b != d_alns.p + b) {
-                hipLaunchKernelGGL(len_gate_putback_kernel, grid_for(n), dim3(256), 0, s, n, A.lg_map.p, (const uc_aln *)alns_b, d_alns.p + b);
-                UC_HIP(hipStreamSynchronize(s));
-            }
-        }
+        AlignBatch B{qbegin, qa, qb, (uint32_t)(hit_off[qb] - b), d_hq.p + b, d_ht.p + b, d_alns.p + b, d_alns.p + b, false, p.sw_pk ? 1 : 0};
         qa = qb;
+        if (p.len_gate && p.cov > 0.0f && B.n) length_gate(*this, B);
+        if (!B.n) continue;
+        B.dedup = p.sym_dedup && p.mat_symmetric && B.n >= 2 && hdb.n <= (1u << 24);
+        forward_pass(*this, B);
+        if (p.rev_correction) rev_correction_pass(*this, B);
+        if (B.dedup) {   // the shared-DP passes count their cells on the device
+            unsigned long long hc[2] = {0, 0};
+            UC_HIP(hipMemcpyAsync(hc, A.d_cells.p, 16, hipMemcpyDeviceToHost, s));
+            UC_HIP(hipStreamSynchronize(s));
+            stats.cells_fwd += hc[0];
+            stats.cells_rev += hc[1];
+        }
+        evalue_gate(*this, B);
+        if (B.n2) {
+            start_pass(*this, B);
+            uint32_t ne = compact(*this, A.tmp, A.eflag.p, A.epos.p, B.n2);
+            if ((p.min_seq_id > 0.0f || p.want_tb) && ne) {
+                traceback_stats(*this, B);
+                ne = compact(*this, A.tmp, A.eflag.p, A.epos.p, B.n2);
+            }
+            if (ne) append_edges(*this, B, ne);
+        }
+        finish_batch(*this, B);
     }
     alns_valid = true;
     last_align_hits = qbegin == 0 && qend == hdb.n ? n_hits : 0;      // what the buffers of this set have just served (uc_prefilter.hip: scratch_release_target)
@@ -1699,8 +1718,7 @@ void Engine::set_cover_graph(uint32_t n, const uint32_t *h_edges, const uint32_t
         tmp.reserve(tb + 256);
         UC_HIP(rocprim::radix_sort_keys(tmp.p, tb, key.p, key2.p, (size_t)m, 0u, 64u, stream));
         hipLaunchKernelGGL(edge_uniq_kernel, grid_for(m), dim3(256), 0, stream, m, key2.p, flag.p);
-        scan_u32(*this, tmp, flag.p, pos.p, (uint32_t)m, false);
-        const uint32_t mu = scan_total(*this, flag.p, pos.p, (uint32_t)m);
+        const uint32_t mu = compact(*this, tmp, flag.p, pos.p, (uint32_t)m);
         uint32_t hbad = 0;
         UC_HIP(hipMemcpy(&hbad, bad.p, 4, hipMemcpyDeviceToHost));
         if (hbad) fail(UC_ERR_ARGS, "set cover: %u edges with an endpoint out of range", hbad);

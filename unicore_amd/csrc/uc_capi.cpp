@@ -120,8 +120,8 @@ int uc_option_arity(const char *flag) { return flag ? option_arity(flag) : -1; }
 
 void uc_release_scratch(void) {
     for (int d = 0; d < 16; d++) {
-        free_prefilter_scratch(take_parked_prefilter_scratch(d));
-        free_align_scratch(take_parked_align_scratch(d));
+        free_scratch(ParkedScratch<PrefilterScratch>::take(d));
+        free_scratch(ParkedScratch<AlignScratch>::take(d));
     }
 }
 

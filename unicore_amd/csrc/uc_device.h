@@ -91,7 +91,6 @@ size_t sw_long_work_ints(int mode, uint32_t n_pairs, uint32_t max_len, uint32_t 
 void launch_sw_long(int mode, const SwArgs &a, uint32_t n_tasks, uint32_t pair_base, int32_t *work, uint32_t stride, hipStream_t s);
 void launch_ungapped(const DeviceDb &db, uint64_t n, const uint32_t *q, const uint32_t *t, const int32_t *diag,
                      int32_t *score, unsigned long long *overlap_sum /* nullable */, hipStream_t s);
-bool sw_class_for(int lq, int *G, int *R);
 // padded device layout of the sequence tracks from the raw (unpadded) ones: s3 / sa[total] with pad letter 20, lt[total + 16]
 // (16 PAD pairs in front) with the PAD pair in all padding; off = padded offsets (n + 1), roff = raw offsets (n + 1)
 void launch_comp_bias(const DeviceDb &db, int scale_milli, int8_t *out, hipStream_t s);   // rule UC-1/B

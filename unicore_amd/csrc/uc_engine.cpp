@@ -68,9 +68,9 @@ Engine::~Engine() {
         if (ev_join[i]) (void)hipEventDestroy(ev_join[i]);
         if (aux[i]) (void)hipStreamDestroy(aux[i]);
     }
-    park_prefilter_scratch(pre, device);
+    ParkedScratch<PrefilterScratch>::park(pre, device);
     pre = nullptr;
-    park_align_scratch(aln, device);
+    ParkedScratch<AlignScratch>::park(aln, device);
     aln = nullptr;
     if (ev_fork) (void)hipEventDestroy(ev_fork);
     if (stream) (void)hipStreamDestroy(stream);
@@ -199,8 +199,8 @@ void Engine::drop_scratch() {
     UC_HIP(hipStreamSynchronize(stream));
     // parked, not freed: the next virtual rank on this device takes the same buffers (one set per device), so no rank pays for
     // tens of GB of hipMalloc inside its timed phase
-    if (pre) { park_prefilter_scratch(pre, device); pre = nullptr; }
-    if (aln) { park_align_scratch(aln, device); aln = nullptr; last_align_hits = 0; }
+    if (pre) { ParkedScratch<PrefilterScratch>::park(pre, device); pre = nullptr; }
+    if (aln) { ParkedScratch<AlignScratch>::park(aln, device); aln = nullptr; last_align_hits = 0; }
 }
 
 bool Engine::relieve_pressure(int stage) {
@@ -209,11 +209,11 @@ bool Engine::relieve_pressure(int stage) {
     (void)hipMemGetInfo(&f0, &tot);
     bool freed = false;
     // a scratch set goes only when no frame of its own stage is open on this engine - the innermost scope decides what is asked for, every open one what is pinned
-    if (stage != 1 && !stage_frames[1] && aln) { free_align_scratch(aln); aln = nullptr; last_align_hits = 0; freed = true; }
+    if (stage != 1 && !stage_frames[1] && aln) { free_scratch(aln); aln = nullptr; last_align_hits = 0; freed = true; }
     if (stage == 1 && aln && release_tb_matrices(aln)) freed = true;      // the gapped stage's own traceback-byte buffer, when no batch loop is using it
-    if (stage != 0 && !stage_frames[0] && pre) { free_prefilter_scratch(pre); pre = nullptr; freed = true; }
-    if (PrefilterScratch *x = take_parked_prefilter_scratch(device)) { free_prefilter_scratch(x); freed = true; }
-    if (AlignScratch *x = take_parked_align_scratch(device)) { free_align_scratch(x); freed = true; }
+    if (stage != 0 && !stage_frames[0] && pre) { free_scratch(pre); pre = nullptr; freed = true; }
+    if (PrefilterScratch *x = ParkedScratch<PrefilterScratch>::take(device)) { free_scratch(x); freed = true; }
+    if (AlignScratch *x = ParkedScratch<AlignScratch>::take(device)) { free_scratch(x); freed = true; }
     (void)hipMemGetInfo(&f1, &tot);
     if (getenv("UC_TIMING") && g_verbosity < 2)
         fprintf(stderr, "unicore-cluster[timing]: device memory ran out in the %s; %s work buffers released (%.1f -> %.1f GiB free)\n",

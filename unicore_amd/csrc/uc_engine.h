@@ -9,6 +9,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <mutex>
 #include <string>
 #include <utility>
 #include <vector>
@@ -130,18 +131,42 @@ struct PinnedBuf {   // page-locked host staging buffer (hipHostMalloc): D2H cop
     }
 };
 
+inline dim3 grid_for(uint64_t n, uint32_t cap = 16384) {
+    const uint64_t b = (n + 255) / 256;
+    return dim3((uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(b, cap)));
+}
+
 struct PairIn { uint32_t q, t; int32_t qe, te; };
 struct PrefilterScratch;                                  // uc_prefilter.hip
-void free_prefilter_scratch(PrefilterScratch *p);
-void park_prefilter_scratch(PrefilterScratch *p, int device);   // keeps one set per device for the next engine of the process
-PrefilterScratch *take_prefilter_scratch(int device);
-PrefilterScratch *take_parked_prefilter_scratch(int device);
+void free_scratch(PrefilterScratch *p);
 struct AlignScratch;                                      // uc_align.hip
-void free_align_scratch(AlignScratch *p);
+void free_scratch(AlignScratch *p);
 bool release_tb_matrices(AlignScratch *p);   // the traceback-byte buffer, unless a MODE 7 batch loop is using it right now (uc_align.hip)
-void park_align_scratch(AlignScratch *p, int device);
-AlignScratch *take_align_scratch(int device);
-AlignScratch *take_parked_align_scratch(int device);
+
+// A destroyed engine parks its work buffers here (one set per device) and the next engine of the process takes them
+// over: freeing and re-allocating tens of GB between two uc_cluster calls is usually free, but now and then the next
+// hipMalloc then takes 1-3 s (measured: 1 in ~5 calls).  UC_KEEP_SCRATCH=0 releases them with the engine instead.
+template <typename S>
+class ParkedScratch {   // S = PrefilterScratch / AlignScratch; one slot per device
+    static inline std::mutex mu;
+    static inline S *slot[16] = {};
+
+  public:
+    static void park(S *p, int device) {
+        const char *e = getenv("UC_KEEP_SCRATCH");
+        if (p && !(e && e[0] == '0') && device >= 0 && device < 16) {
+            std::lock_guard<std::mutex> g(mu);
+            if (!slot[device]) { slot[device] = p; return; }
+        }
+        free_scratch(p);
+    }
+    static S *take(int device) {   // nullptr if nothing is parked (uc_release_scratch)
+        if (device < 0 || device >= 16) return nullptr;
+        std::lock_guard<std::mutex> g(mu);
+        return std::exchange(slot[device], nullptr);
+    }
+    static S *take_or_new(int device) { S *p = take(device); return p ? p : new S; }   // in the stage's own file, where S is complete
+};
 
 struct Engine {
     Params p;

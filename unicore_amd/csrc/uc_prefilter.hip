@@ -21,7 +21,6 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
-#include <mutex>
 #include <type_traits>
 
 #include <rocprim/rocprim.hpp>
@@ -1308,11 +1307,6 @@ __global__ void __launch_bounds__(256) owner_gather_kernel(uint64_t n, const uin
     }
 }
 
-static inline dim3 grid_for(uint64_t n, uint32_t cap = 16384) {
-    const uint64_t b = (n + 255) / 256;
-    return dim3((uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(b, cap)));
-}
-
 struct WidenU32 {
     __host__ __device__ uint64_t operator()(uint32_t x) const { return (uint64_t)x; }
 };
@@ -1371,38 +1365,7 @@ struct PrefilterScratch {
         }
     }
 };
-void free_prefilter_scratch(PrefilterScratch *p) { delete p; }
-
-// A destroyed engine parks its work buffers here (one set per device) and the next engine of the process takes them
-// over: freeing and re-allocating tens of GB between two uc_cluster calls is usually free, but now and then the next
-// hipMalloc then takes 1-3 s (measured: 1 in ~5 calls).  UC_KEEP_SCRATCH=0 releases them with the engine instead.
-namespace {
-std::mutex g_park_mutex;
-PrefilterScratch *g_parked_pre[16] = {};
-bool keep_scratch() { const char *e = getenv("UC_KEEP_SCRATCH"); return !(e && e[0] == '0'); }
-}  // namespace
-void park_prefilter_scratch(PrefilterScratch *p, int device) {
-    if (!p) return;
-    if (keep_scratch() && device >= 0 && device < 16) {
-        std::lock_guard<std::mutex> g(g_park_mutex);
-        if (!g_parked_pre[device]) { g_parked_pre[device] = p; return; }
-    }
-    delete p;
-}
-PrefilterScratch *take_parked_prefilter_scratch(int device) {   // nullptr if nothing is parked (uc_release_scratch)
-    if (device < 0 || device >= 16) return nullptr;
-    std::lock_guard<std::mutex> g(g_park_mutex);
-    PrefilterScratch *p = g_parked_pre[device];
-    g_parked_pre[device] = nullptr;
-    return p;
-}
-PrefilterScratch *take_prefilter_scratch(int device) {
-    if (device >= 0 && device < 16) {
-        std::lock_guard<std::mutex> g(g_park_mutex);
-        if (PrefilterScratch *p = g_parked_pre[device]) { g_parked_pre[device] = nullptr; return p; }
-    }
-    return new PrefilterScratch;
-}
+void free_scratch(PrefilterScratch *p) { delete p; }
 
 // the prefilter's work buffers stay allocated between steps (re-allocating the 34 GiB key regions alone costs a second per
 // step at configs[1]) unless they hold more than 40 % of the device memory: then the gapped stage, which sizes its batches by
@@ -1508,7 +1471,7 @@ void Engine::prefilter_impl(uint32_t tbegin, uint32_t tend, uint32_t qbegin, uin
             // running top-M accumulator of <= max_seqs x queries — made configs[2] SLOWER, 35.7 -> 39.3 s per pass: the single merge needs ~64 B per
             // record of work buffers at the moment the key regions are largest.  The accumulator is merged after every pass.)
             // (r06: the accumulator / pass arrays live in the scratch set - up to 4 x 7 GB at configs[2] were allocated and freed by every call)
-            if (!pre) pre = take_prefilter_scratch(device);
+            if (!pre) pre = ParkedScratch<PrefilterScratch>::take_or_new(device);
             DevBuf<uint32_t> &aq = pre->acc_q, &at = pre->acc_t, &tq = pre->pass_q, &tt = pre->pass_t;
             DevBuf<int32_t> &as = pre->acc_s, &ad = pre->acc_d, &ts = pre->pass_s, &td = pre->pass_d;
             uint64_t acc_n = 0;
@@ -1569,7 +1532,7 @@ bool Engine::prefilter_one(uint32_t tbegin, uint32_t tend, uint32_t qbegin, uint
     if (n > (1u << 24)) fail(UC_ERR_GENERIC, "prefilter: %u sequences exceed the 2^24 limit of the hit keys", n);
     // counters: [0] similar k-mers, [1] kept candidates, [2] ungapped overlap residues, [3] run cursor,
     //           [4] k-mer hits of the batch, [5] key cursor, [6] candidate cursor
-    if (!pre) pre = take_prefilter_scratch(device);
+    if (!pre) pre = ParkedScratch<PrefilterScratch>::take_or_new(device);
     PrefilterScratch &S = *pre;
     DevBuf<unsigned long long> &d_counters = S.d_counters;
     d_counters.reserve(8);
@@ -2001,7 +1964,7 @@ void Engine::partition_hits_by_owner(uint32_t world, uint32_t *dq, uint32_t *dt,
     if (!n_hits) return;
     if (n_hits >= (1ull << 32)) fail(UC_ERR_GENERIC, "partition_hits_by_owner: %llu records exceed the 32-bit index", (unsigned long long)n_hits);
     UC_HIP(hipSetDevice(device));
-    if (!pre) pre = take_prefilter_scratch(device);
+    if (!pre) pre = ParkedScratch<PrefilterScratch>::take_or_new(device);
     DevBuf<uint32_t> &okey = pre->d_cq, &okey2 = pre->d_ct, &idx = pre->d_flag, &idx2 = pre->d_cnt;
     DevBuf<unsigned long long> cnt;
     DevBuf<char> &tmp = pre->d_temp;
@@ -2052,7 +2015,7 @@ uint64_t Engine::merge_hits_dev(uint64_t n1, const uint32_t *q1, const uint32_t 
     timed_ms_begin();
     // work buffers from the engine's prefilter scratch: a chunked or sharded run merges once per chunk / shard, and allocating
     // ~50 B per record anew every time was most of the merge time at 10^9 records
-    if (!pre) pre = take_prefilter_scratch(device);
+    if (!pre) pre = ParkedScratch<PrefilterScratch>::take_or_new(device);
     DevBuf<uint64_t> &skey = pre->d_skey, &skey2 = pre->d_skey2, &pos = pre->d_pos;
     DevBuf<int32_t> &cd2 = pre->d_cd2;
     DevBuf<uint32_t> &flag = pre->d_flag, &cnt = pre->d_cnt;

@@ -9,15 +9,6 @@ void launch_sw_class_m1(int G, int R, const SwArgs &a, uint32_t n_tasks, hipStre
 void launch_sw_class_m2(int G, int R, const SwArgs &a, uint32_t n_tasks, hipStream_t s);
 void launch_sw_class_m3(int G, int R, const SwArgs &a, uint32_t n_tasks, hipStream_t s);
 
-// smallest (G,R) class whose G*R rows hold the query; false if it needs the generic kernel
-bool sw_class_for(int lq, int *G, int *R) {
-    static const int cls[][2] = {{16, 4}, {16, 8}, {16, 12}, {16, 16}, {16, 20}, {16, 24}, {16, 28}, {16, 32},
-                                 {32, 20}, {32, 24}, {32, 28}, {32, 32}, {64, 20}, {64, 24}, {64, 28}, {64, 32}};
-    for (const auto &c : cls)
-        if (c[0] * c[1] >= lq) { *G = c[0]; *R = c[1]; return true; }
-    return false;
-}
-
 void launch_sw_class(int G, int R, int mode, const SwArgs &a, uint32_t n_tasks, hipStream_t s) {
     if (n_tasks == 0) return;
     if (mode == 0) launch_sw_class_m0(G, R, a, n_tasks, s);
