@@ -261,6 +261,30 @@ int uc_engine_sw_batch(uc_engine *e, int mode, uint64_t n, const uint32_t *q, co
                        const int32_t *qend_in, const int32_t *tend_in,
                        int32_t *score_out, int32_t *qend_out, int32_t *tend_out);
 
+/* ---- kernel-level entry points of the ProstT5 encoder (tests/test_t5_kernels.py calls the HIP kernels through these).
+ * Each device call takes host arrays: it allocates, copies, runs the library's own launcher on `device` (-1 = the current one),
+ * synchronizes, copies back and frees.  Inputs that break a kernel's preconditions are UC_ERR_ARGS before the device is touched.
+ * f16 data crosses as uint16_t bit patterns.
+ * uc_t5_gemm_variant (host only): the kernel the encoder's GEMM picks for M x N x K: 0 = 128 x 128 tile, 1 = 256 x 256 tile,
+ *   2 = 256 x 256 two-phase persistent.  Every shape needs K % 64 == 0 and N % 4 == 0.
+ * uc_t5_kernel_gemm: out[M, N] (+)= A[M, K] . W[N, K]^T; epi 0: f16 out, 1: ReLU + f16 out, 2: fp32 out, read and accumulated into.
+ *   variant -1 = the library's pick; a forced variant must admit the shape (1: N % 256 == 0; 2: also K >= 128 and M * K, N * K < 2^31).
+ * uc_t5_kernel_rmsnorm: y[T, D] (f16) = x * rsqrt(mean(x^2) + eps) * w, x fp32 [T, D], w fp32 [D]; D % 4 == 0.
+ * uc_t5_kernel_attention: n_seqs sequences of seq_len[i] tokens packed in order; qkv [T, 3 * H * 128] (q | k | v), out [T, H * 128];
+ *   bias [H][2 * bias_span - 1] fp32 indexed by key - query + bias_span - 1; bias_span >= max seq_len.
+ * uc_t5_kernel_cnn_head: seq_len[i] counts a sequence's tokens including <AA2fold> and </s> (>= 2); x [T, D] f16 (D % 64 == 0);
+ *   w1 [C1][D][KW], b1 [C1], w2 [NO][C1][KW], b2 [NO] fp32 (GGUF order; w1 is rounded to f16 as the loader does); KW odd <= 31,
+ *   NO <= 21.  The conv1 GEMM plus the head kernels; codes [T], logits [T, NO] (nullable) are written for every token.
+ * uc_t5_bias_table (host only): the table the encoder uploads, rel_bias [H][buckets] -> out [H][2 * span - 1]. */
+int uc_t5_gemm_variant(int32_t M, int32_t N, int32_t K, int32_t *variant);
+int uc_t5_kernel_gemm(int32_t device, int32_t variant, int32_t epi, int32_t M, int32_t N, int32_t K, const uint16_t *A, const uint16_t *W, void *out);
+int uc_t5_kernel_rmsnorm(int32_t device, int32_t T, int32_t D, float eps, const float *x, const float *w, uint16_t *y);
+int uc_t5_kernel_attention(int32_t device, int32_t H, int32_t n_seqs, const int32_t *seq_len, int32_t bias_span, const float *bias,
+                           const uint16_t *qkv, uint16_t *out);
+int uc_t5_kernel_cnn_head(int32_t device, int32_t n_seqs, const int32_t *seq_len, int32_t D, int32_t C1, int32_t KW, int32_t NO, int32_t eos_in_head,
+                          const uint16_t *x, const float *w1, const float *b1, const float *w2, const float *b2, uint8_t *codes, float *logits);
+int uc_t5_bias_table(int32_t H, int32_t buckets, int32_t max_dist, int32_t span, const float *rel_bias, float *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -258,6 +258,10 @@ def test_bench_launches_itself_for_more_than_one_gpu():
     if torch.cuda.is_available():
         pytest.skip("a GPU is present: tests/test_multi_gpu.py runs the real thing")
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    # the launcher polls its workers every 0.1 s by default and terminates the others as soon as one has failed: on a loaded host the
+    # rank that is still importing torch then dies before it can print.  Its first poll after 60 s (--monitor-interval, read from
+    # PET_MONITOR_INTERVAL) lets every rank reach its own message.
+    env["PET_MONITOR_INTERVAL"] = "60"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0"], capture_output=True, text=True, env=env, timeout=300)
     assert r.returncode != 0
     assert (r.stdout + r.stderr).count("bench.py needs a GPU") == 2

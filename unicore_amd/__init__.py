@@ -63,6 +63,7 @@ SYMBOLS = (
     "uc_hits_merge", "uc_engine_align", "uc_engine_alns_get", "uc_engine_edges_size", "uc_engine_edges_get",
     "uc_engine_stats", "uc_engine_reset_stats", "uc_setcover", "uc_write_cluster_db",
     "uc_engine_ungapped_batch", "uc_engine_sw_batch", "uc_abi_version", "uc_stats_size", "uc_set_round_hook",
+    "uc_t5_gemm_variant", "uc_t5_kernel_gemm", "uc_t5_kernel_rmsnorm", "uc_t5_kernel_attention", "uc_t5_kernel_cnn_head", "uc_t5_bias_table",
 )
 ABI_VERSION = 6      # == UC_ABI_VERSION of include/unicore_cluster.h this binding mirrors
 ROUND_HOOK = C.CFUNCTYPE(None, C.c_void_p, C.c_int32, C.c_uint32, C.POINTER(C.c_uint32), C.c_int32, C.c_void_p)
@@ -135,6 +136,12 @@ def lib():
     L.uc_write_cluster_db.argtypes = [C.c_char_p, u32, vp]
     L.uc_engine_ungapped_batch.argtypes = [vp, u64, vp, vp, vp, vp]
     L.uc_engine_sw_batch.argtypes = [vp, C.c_int, u64, vp, vp, vp, vp, vp, vp, vp]
+    L.uc_t5_gemm_variant.argtypes = [i32, i32, i32, C.POINTER(i32)]
+    L.uc_t5_kernel_gemm.argtypes = [i32, i32, i32, i32, i32, i32, vp, vp, vp]
+    L.uc_t5_kernel_rmsnorm.argtypes = [i32, i32, i32, C.c_float, vp, vp, vp]
+    L.uc_t5_kernel_attention.argtypes = [i32, i32, i32, vp, i32, vp, vp, vp]
+    L.uc_t5_kernel_cnn_head.argtypes = [i32, i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]
+    L.uc_t5_bias_table.argtypes = [i32, i32, i32, i32, vp, vp]
     L.uc_abi_version.restype = u32
     L.uc_stats_size.restype = C.c_size_t
     L.uc_set_round_hook.argtypes = [ROUND_HOOK, vp]
@@ -286,6 +293,73 @@ class T5Encoder:
         st = UcT5Stats()
         _check(lib().uc_t5_get_stats(self._h, C.byref(st)))
         return {k: getattr(st, k) for k, _ in UcT5Stats._fields_}
+
+
+# ---- kernel-level entry points of the ProstT5 encoder: numpy in, numpy out (f16 arrays cross the ABI as their uint16 bit patterns)
+def _f16(a):
+    return np.ascontiguousarray(a, np.float16).view(np.uint16)
+
+
+def _f32(a):
+    return np.ascontiguousarray(a, np.float32)
+
+
+def t5_gemm_variant(M, N, K):
+    """the GEMM kernel the encoder picks for M x N x K: 0 = 128 x 128 tile, 1 = 256 x 256 tile, 2 = 256 x 256 persistent (host only)"""
+    v = C.c_int32()
+    _check(lib().uc_t5_gemm_variant(M, N, K, C.byref(v)))
+    return v.value
+
+
+def t5_kernel_gemm(A, W, epi, variant=-1, init=None, device=-1):
+    """A [M, K], W [N, K] f16 -> A . W^T as f16 (epi 0), ReLU'd f16 (epi 1) or init + A . W^T in fp32 (epi 2, init [M, N] fp32)"""
+    A, W = _f16(A), _f16(W)
+    (M, K), N = A.shape, W.shape[0]
+    if W.shape[1] != K:
+        raise ValueError("A is [M, %d] but W is [N, %d]" % (K, W.shape[1]))
+    if epi == 2:
+        out = np.zeros((M, N), np.float32) if init is None else np.array(init, np.float32, order="C").reshape(M, N)
+    else:
+        out = np.zeros((M, N), np.uint16)
+    _check(lib().uc_t5_kernel_gemm(device, variant, epi, M, N, K, A.ctypes.data, W.ctypes.data, out.ctypes.data))
+    return out if epi == 2 else out.view(np.float16)
+
+
+def t5_kernel_rmsnorm(x, w, eps, device=-1):
+    """x [T, D] fp32, w [D] fp32 -> f16 [T, D]"""
+    x, w = _f32(x), _f32(w)
+    y = np.zeros(x.shape, np.uint16)
+    _check(lib().uc_t5_kernel_rmsnorm(device, x.shape[0], x.shape[1], eps, x.ctypes.data, w.ctypes.data, y.ctypes.data))
+    return y.view(np.float16)
+
+
+def t5_kernel_attention(qkv, seq_len, bias, bias_span, n_heads, device=-1):
+    """qkv [T, 3 * H * 128] f16 of the sequences packed in order, bias [H, 2 * bias_span - 1] fp32 -> f16 [T, H * 128]"""
+    qkv, bias = _f16(qkv), _f32(bias)
+    sl = np.ascontiguousarray(seq_len, np.int32)
+    out = np.zeros((qkv.shape[0], n_heads * 128), np.uint16)
+    _check(lib().uc_t5_kernel_attention(device, n_heads, len(sl), sl.ctypes.data, bias_span, bias.ctypes.data, qkv.ctypes.data, out.ctypes.data))
+    return out.view(np.float16)
+
+
+def t5_kernel_cnn_head(x, seq_len, w1, b1, w2, b2, eos_in_head, device=-1):
+    """x [T, D] f16 (per sequence <AA2fold>, residues, </s>), w1 [C1, D, KW], b1 [C1], w2 [NO, C1, KW], b2 [NO] fp32
+    -> (codes uint8 [T], logits fp32 [T, NO]) for every token"""
+    x, w1, b1, w2, b2 = _f16(x), _f32(w1), _f32(b1), _f32(w2), _f32(b2)
+    sl = np.ascontiguousarray(seq_len, np.int32)
+    (C1, D, KW), NO, T = w1.shape, w2.shape[0], x.shape[0]
+    codes, logits = np.zeros(T, np.uint8), np.zeros((T, NO), np.float32)
+    _check(lib().uc_t5_kernel_cnn_head(device, len(sl), sl.ctypes.data, D, C1, KW, NO, int(eos_in_head), x.ctypes.data, w1.ctypes.data, b1.ctypes.data,
+                                       w2.ctypes.data, b2.ctypes.data, codes.ctypes.data, logits.ctypes.data))
+    return codes, logits
+
+
+def t5_bias_table(rel_bias, max_dist, span):
+    """rel_bias [H, buckets] fp32 -> the encoder's table [H, 2 * span - 1] over key - query in (-span, span) (host only)"""
+    rb = _f32(rel_bias)
+    out = np.zeros((rb.shape[0], 2 * span - 1), np.float32)
+    _check(lib().uc_t5_bias_table(rb.shape[0], rb.shape[1], max_dist, span, rb.ctypes.data, out.ctypes.data))
+    return out
 
 
 class Comm:

@@ -94,6 +94,62 @@ void require(const void *p, const char *what) {
     if (!p) fail(UC_ERR_ARGS, "%s must not be NULL", what);
 }
 
+// ---- the encoder's kernel-level entry points: one call = one device, buffers freed on every exit path
+void t5_use_device(int32_t device) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) fail(UC_ERR_DEVICE, "no HIP device available; the ProstT5 kernels have no CPU fallback");
+    if (device < 0) UC_HIP(hipGetDevice(&device));
+    if (device >= ndev) fail(UC_ERR_DEVICE, "device %d requested but only %d visible", device, ndev);
+    UC_HIP(hipSetDevice(device));
+}
+
+struct DevBufs {
+    std::vector<void *> p;
+    DevBufs() = default;
+    DevBufs(const DevBufs &) = delete;
+    DevBufs &operator=(const DevBufs &) = delete;
+    ~DevBufs() { for (void *q : p) (void)hipFree(q); }
+    template <typename T = void> T *alloc(size_t bytes) {
+        void *q = nullptr;
+        UC_HIP(hipMalloc(&q, std::max<size_t>(bytes, 16)));
+        p.push_back(q);
+        return (T *)q;
+    }
+    template <typename T> T *up(const T *src, size_t n) {
+        T *q = alloc<T>(n * sizeof(T));
+        UC_HIP(hipMemcpy(q, src, n * sizeof(T), hipMemcpyHostToDevice));
+        return q;
+    }
+    // an output every element of which the kernel must write: filled with 0xff (NaN as f16 / fp32) so that a missed one shows
+    template <typename T> T *out(size_t n) {
+        T *q = alloc<T>(n * sizeof(T));
+        UC_HIP(hipMemset(q, 0xff, n * sizeof(T)));
+        return q;
+    }
+};
+
+void t5_finish() {
+    UC_HIP(hipGetLastError());
+    UC_HIP(hipDeviceSynchronize());
+}
+
+// packed sequence lengths -> token offsets (n + 1); every length >= min_len
+std::vector<int32_t> t5_offsets(int32_t n_seqs, const int32_t *seq_len, int32_t min_len, int32_t *max_len) {
+    if (n_seqs < 1) fail(UC_ERR_ARGS, "n_seqs must be >= 1");
+    require(seq_len, "seq_len");
+    std::vector<int32_t> off((size_t)n_seqs + 1, 0);
+    int64_t t = 0;
+    *max_len = 0;
+    for (int32_t i = 0; i < n_seqs; i++) {
+        if (seq_len[i] < min_len) fail(UC_ERR_ARGS, "seq_len[%d] = %d < %d", i, seq_len[i], min_len);
+        t += seq_len[i];
+        if (t > (1 << 28)) fail(UC_ERR_ARGS, "more than 2^28 tokens");
+        off[(size_t)i + 1] = (int32_t)t;
+        *max_len = std::max(*max_len, seq_len[i]);
+    }
+    return off;
+}
+
 }  // namespace
 
 extern "C" {
@@ -869,6 +925,113 @@ int uc_t5_get_stats(const uc_t5 *m, uc_t5_stats *out) {
         require(m, "model"); require(out, "out");
         out->n_seqs = m->m.stats.n_seqs; out->n_tokens = m->m.stats.n_tokens; out->flops = m->m.stats.flops; out->gpu_ms = m->m.stats.total_ms;
         out->n_replicas = 1; out->reserved0 = 0; out->gpu_ms_sum = m->m.stats.total_ms; out->tokens_min_replica = out->tokens_max_replica = m->m.stats.n_tokens;
+    });
+}
+
+int uc_t5_gemm_variant(int32_t M, int32_t N, int32_t K, int32_t *variant) {
+    return guard([&] {
+        require(variant, "variant");
+        if (!t5_gemm_admits(0, M, N, K)) fail(UC_ERR_ARGS, "t5 gemm: %d x %d x %d: needs M, N >= 1, N %% 4 == 0, K %% 64 == 0", M, N, K);
+        *variant = t5_gemm_pick(M, N, K);
+    });
+}
+
+int uc_t5_kernel_gemm(int32_t device, int32_t variant, int32_t epi, int32_t M, int32_t N, int32_t K, const uint16_t *A, const uint16_t *W, void *out) {
+    return guard([&] {
+        require(A, "A"); require(W, "W"); require(out, "out");
+        if (epi < 0 || epi > 2) fail(UC_ERR_ARGS, "t5 gemm: epilogue must be 0, 1 or 2");
+        if (variant < -1 || variant > 2) fail(UC_ERR_ARGS, "t5 gemm: variant must be -1 (the library's pick), 0, 1 or 2");
+        if (!t5_gemm_admits(0, M, N, K)) fail(UC_ERR_ARGS, "t5 gemm: %d x %d x %d: needs M, N >= 1, N %% 4 == 0, K %% 64 == 0", M, N, K);
+        const int v = variant < 0 ? t5_gemm_pick(M, N, K) : variant;
+        if (!t5_gemm_admits(v, M, N, K)) fail(UC_ERR_ARGS, "t5 gemm: variant %d cannot run %d x %d x %d", v, M, N, K);
+        t5_use_device(device);
+        DevBufs b;
+        const size_t mn = (size_t)M * N, ob = mn * (epi == 2 ? 4 : 2);
+        const uint16_t *dA = b.up(A, (size_t)M * K), *dW = b.up(W, (size_t)N * K);
+        void *dO = epi == 2 ? (void *)b.up((const float *)out, mn) : (void *)b.out<uint16_t>(mn);
+        t5_gemm_run(v, epi, dA, dW, dO, M, N, K, nullptr);
+        t5_finish();
+        UC_HIP(hipMemcpy(out, dO, ob, hipMemcpyDeviceToHost));
+    });
+}
+
+int uc_t5_kernel_rmsnorm(int32_t device, int32_t T, int32_t D, float eps, const float *x, const float *w, uint16_t *y) {
+    return guard([&] {
+        require(x, "x"); require(w, "w"); require(y, "y");
+        if (T < 1 || D < 4 || D % 4) fail(UC_ERR_ARGS, "t5 rmsnorm: needs T >= 1 and D a positive multiple of 4 (T %d, D %d)", T, D);
+        t5_use_device(device);
+        DevBufs b;
+        const size_t n = (size_t)T * D;
+        const float *dx = b.up(x, n), *dw = b.up(w, (size_t)D);
+        uint16_t *dy = b.out<uint16_t>(n);
+        t5_rmsnorm(dx, dw, dy, T, D, eps, nullptr);
+        t5_finish();
+        UC_HIP(hipMemcpy(y, dy, n * 2, hipMemcpyDeviceToHost));
+    });
+}
+
+int uc_t5_kernel_attention(int32_t device, int32_t H, int32_t n_seqs, const int32_t *seq_len, int32_t bias_span, const float *bias,
+                           const uint16_t *qkv, uint16_t *out) {
+    return guard([&] {
+        require(bias, "bias"); require(qkv, "qkv"); require(out, "out");
+        if (H < 1 || H > 1024) fail(UC_ERR_ARGS, "t5 attention: H = %d outside 1 .. 1024", H);
+        int32_t maxL = 0;
+        const std::vector<int32_t> off = t5_offsets(n_seqs, seq_len, 1, &maxL);
+        if (bias_span < maxL) fail(UC_ERR_ARGS, "t5 attention: bias_span %d < longest sequence %d", bias_span, maxL);
+        if (bias_span > (1 << 24)) fail(UC_ERR_ARGS, "t5 attention: bias_span %d too large", bias_span);
+        std::vector<T5AttnTile> tiles;
+        t5_attn_tiles(off.data(), (size_t)n_seqs, tiles);
+        t5_use_device(device);
+        DevBufs b;
+        const size_t T = (size_t)off[(size_t)n_seqs], HD = (size_t)H * 128;
+        const uint16_t *dq = b.up(qkv, T * 3 * HD);
+        const float *db = b.up(bias, (size_t)H * (2 * (size_t)bias_span - 1));
+        const T5AttnTile *dt = b.up(tiles.data(), tiles.size());
+        uint16_t *dO = b.out<uint16_t>(T * HD);
+        t5_attention(dq, dt, (int)tiles.size(), db, bias_span, H, dO, nullptr);
+        t5_finish();
+        UC_HIP(hipMemcpy(out, dO, T * HD * 2, hipMemcpyDeviceToHost));
+    });
+}
+
+int uc_t5_kernel_cnn_head(int32_t device, int32_t n_seqs, const int32_t *seq_len, int32_t D, int32_t C1, int32_t KW, int32_t NO, int32_t eos_in_head,
+                          const uint16_t *x, const float *w1, const float *b1, const float *w2, const float *b2, uint8_t *codes, float *logits) {
+    return guard([&] {
+        require(x, "x"); require(w1, "w1"); require(b1, "b1"); require(w2, "w2"); require(b2, "b2"); require(codes, "codes");
+        if (D < 64 || D % 64 || D > 65536) fail(UC_ERR_ARGS, "t5 cnn head: d_model %d is not a multiple of 64 in 64 .. 65536", D);
+        if (C1 < 1 || C1 > 4096 || KW < 1 || KW > 31 || !(KW & 1) || NO < 1 || NO > 21)
+            fail(UC_ERR_ARGS, "t5 cnn head: C1 %d (1 .. 4096), KW %d (odd, <= 31), NO %d (1 .. 21)", C1, KW, NO);
+        int32_t maxL = 0;
+        const std::vector<int32_t> off = t5_offsets(n_seqs, seq_len, 2, &maxL);
+        const int T = off[(size_t)n_seqs], ldc1 = t5_conv1_rows(C1, KW);
+        std::vector<int32_t> seq_of((size_t)T);
+        for (int32_t s = 0; s < n_seqs; s++) std::fill(seq_of.begin() + off[(size_t)s], seq_of.begin() + off[(size_t)s + 1], s);
+        const std::vector<float> w1r = t5_conv1_rearrange(w1, C1, D, KW);
+        t5_use_device(device);
+        DevBufs b;
+        const uint16_t *dx = b.up(x, (size_t)T * D);
+        const float *dw1f = b.up(w1r.data(), w1r.size());
+        void *dw1 = b.alloc(w1r.size() * 2);
+        t5_f32_to_f16(dw1f, dw1, w1r.size(), nullptr);                  // as the loader rounds conv1
+        const float *db1 = b.up(b1, (size_t)C1), *dw2 = b.up(w2, (size_t)NO * C1 * KW), *db2 = b.up(b2, (size_t)NO);
+        const int32_t *dof = b.up(seq_of.data(), seq_of.size()), *doff = b.up(off.data(), off.size());
+        void *dy = b.alloc((size_t)T * ldc1 * 2);
+        float *dh1 = b.alloc<float>((size_t)T * C1 * 4), *dlg = logits ? b.out<float>((size_t)T * NO) : nullptr;
+        uint8_t *dc = b.out<uint8_t>((size_t)T);
+        t5_gemm(0, dx, dw1, dy, T, ldc1, D, nullptr);
+        t5_cnn_head(dy, ldc1, dof, doff, db1, dw2, db2, dh1, dc, dlg, T, C1, KW, NO, eos_in_head ? 1 : 0, nullptr);
+        t5_finish();
+        UC_HIP(hipMemcpy(codes, dc, (size_t)T, hipMemcpyDeviceToHost));
+        if (logits) UC_HIP(hipMemcpy(logits, dlg, (size_t)T * NO * 4, hipMemcpyDeviceToHost));
+    });
+}
+
+int uc_t5_bias_table(int32_t H, int32_t buckets, int32_t max_dist, int32_t span, const float *rel_bias, float *out) {
+    return guard([&] {
+        require(rel_bias, "rel_bias"); require(out, "out");
+        if (H < 1 || buckets < 4 || buckets % 2 || max_dist <= buckets / 4 || span < 1 || span > (1 << 24))
+            fail(UC_ERR_ARGS, "t5 bias table: H %d >= 1, buckets %d even >= 4, max_dist %d > buckets / 4, span %d in 1 .. 2^24", H, buckets, max_dist, span);
+        t5_bias_table(H, buckets, max_dist, span, rel_bias, out);
     });
 }
 

@@ -151,6 +151,29 @@ int rel_bucket(int rel /* key - query */, int num_buckets, int max_distance) {
 
 }  // namespace
 
+void t5_attn_tiles(const int32_t *seq_off, size_t n_seqs, std::vector<T5AttnTile> &tiles) {
+    tiles.clear();
+    for (size_t s = 0; s < n_seqs; s++) {
+        const int L = seq_off[s + 1] - seq_off[s];
+        for (int q0 = 0; q0 < L; q0 += 128) tiles.push_back({seq_off[s], L, q0});
+    }
+}
+
+void t5_bias_table(int H, int buckets, int max_dist, int span, const float *rel_bias, float *out) {
+    for (int rel = -(span - 1); rel <= span - 1; rel++) {
+        const int b = rel_bucket(rel, buckets, max_dist);
+        for (int h = 0; h < H; h++) out[(size_t)h * (2 * span - 1) + (rel + span - 1)] = rel_bias[(size_t)h * buckets + b];
+    }
+}
+
+std::vector<float> t5_conv1_rearrange(const float *w1, int C1, int D, int KW) {
+    std::vector<float> w1r((size_t)t5_conv1_rows(C1, KW) * D, 0.f);
+    for (int c = 0; c < C1; c++)
+        for (int d = 0; d < D; d++)
+            for (int k = 0; k < KW; k++) w1r[((size_t)k * C1 + c) * D + d] = w1[((size_t)c * D + d) * KW + k];
+    return w1r;
+}
+
 T5Model::~T5Model() {
     (void)hipSetDevice(device);
     for (void *p : allocs) (void)hipFree(p);
@@ -188,7 +211,8 @@ void T5Model::load(const std::string &gguf_path, int dev) {
     cfg.rel_buckets = (int)num("attention.relative_buckets_count", 32);
     cfg.rel_max_dist = (int)num("attention.relative_max_distance", 128);
     cfg.eps = (float)num("attention.layer_norm_epsilon", num("attention.layer_norm_rms_epsilon", 1e-6));
-    if (cfg.n_layers < 1 || cfg.n_layers > 1024 || cfg.n_heads < 1 || cfg.rel_buckets < 2 || cfg.rel_buckets % 2 || cfg.rel_max_dist < 2 || cfg.d_ff < 64)
+    if (cfg.n_layers < 1 || cfg.n_layers > 1024 || cfg.n_heads < 1 || cfg.rel_buckets < 4 || cfg.rel_buckets % 2 ||
+        cfg.rel_max_dist <= cfg.rel_buckets / 4 || cfg.d_ff < 64)      // (fewer buckets or a max distance inside the exact range: rel_bucket divides by zero)
         fail(UC_ERR_IO, "%s: implausible encoder geometry (%d layers, %d heads, %d buckets, d_ff %d)", gguf_path.c_str(), cfg.n_layers, cfg.n_heads, cfg.rel_buckets, cfg.d_ff);
     if (const char *e = getenv("UC_T5_EOS_IN_HEAD")) cfg.eos_in_head = atoi(e) != 0;
     if (const char *e = getenv("UC_T5_KEEP_UZOB")) cfg.uzob_to_x = atoi(e) == 0;
@@ -271,13 +295,8 @@ void T5Model::load(const std::string &gguf_path, int dev) {
         cfg.cnn_kernel = (int)(c1->n_elems() / ((uint64_t)cfg.cnn_hidden * D));
         if (cfg.cnn_kernel < 1 || cfg.cnn_kernel > 31 || !(cfg.cnn_kernel & 1) || (uint64_t)cfg.cnn_hidden * D * cfg.cnn_kernel != c1->n_elems() || (uint64_t)cfg.n_out * cfg.cnn_hidden * cfg.cnn_kernel != c2->n_elems() || cfg.n_out > 21)
             fail(UC_ERR_IO, "%s: unexpected CNN head shapes", gguf_path.c_str());
-        const int C1 = cfg.cnn_hidden, KW = cfg.cnn_kernel;
-        ldc1 = (KW * C1 + 127) / 128 * 128;
-        std::vector<uint16_t> w1r((size_t)ldc1 * D, 0);
-        std::vector<float> w1f((size_t)ldc1 * D, 0.f);
-        for (int c = 0; c < C1; c++)
-            for (int d = 0; d < D; d++)
-                for (int k = 0; k < KW; k++) w1f[((size_t)k * C1 + c) * D + d] = w1[((size_t)c * D + d) * KW + k];
+        ldc1 = t5_conv1_rows(cfg.cnn_hidden, cfg.cnn_kernel);
+        const std::vector<float> w1f = t5_conv1_rearrange(w1.data(), cfg.cnn_hidden, D, cfg.cnn_kernel);
         float *tmp = nullptr;
         UC_HIP(hipMalloc((void **)&tmp, w1f.size() * 4));
         UC_HIP(hipMemcpy(tmp, w1f.data(), w1f.size() * 4, hipMemcpyHostToDevice));
@@ -332,10 +351,10 @@ void T5Model::encode_batch(const std::vector<const std::string *> &seqs, std::ve
         for (char c : a) tok.push_back(aa_token[(unsigned char)c]);
         tok.push_back(cfg.eos_token);
         for (int i = 0; i < L; i++) seq_of.push_back((int32_t)s);
-        for (int q0 = 0; q0 < L; q0 += 128) tiles.push_back({seq_off[s], L, q0});
         maxL = std::max(maxL, L);
     }
     seq_off[ns] = (int32_t)tok.size();
+    t5_attn_tiles(seq_off.data(), ns, tiles);
     const int T = (int)tok.size();
     if (!T) return;
     // buffers
@@ -354,10 +373,7 @@ void T5Model::encode_batch(const std::vector<const std::string *> &seqs, std::ve
         std::vector<float> hb((size_t)H * cfg.rel_buckets);
         UC_HIP(hipMemcpy(hb.data(), rel_bias, hb.size() * 4, hipMemcpyDeviceToHost));
         std::vector<float> tab((size_t)H * (2 * bias_span - 1));
-        for (int rel = -(bias_span - 1); rel <= bias_span - 1; rel++) {
-            const int b = rel_bucket(rel, cfg.rel_buckets, cfg.rel_max_dist);
-            for (int h = 0; h < H; h++) tab[(size_t)h * (2 * bias_span - 1) + (rel + bias_span - 1)] = hb[(size_t)h * cfg.rel_buckets + b];
-        }
+        t5_bias_table(H, cfg.rel_buckets, cfg.rel_max_dist, bias_span, hb.data(), tab.data());
         UC_HIP(hipMemcpyAsync(bias_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, stream));
         UC_HIP(hipStreamSynchronize(stream));
     }

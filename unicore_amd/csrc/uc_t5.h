@@ -48,13 +48,27 @@ struct GgufFile {
 void gguf_read_header(const std::string &path, GgufFile &g);
 
 // ---- kernels (uc_t5_kernels.hip) -------------------------------------------------------------------------------------------
+// t5_gemm = t5_gemm_run(t5_gemm_pick(M, N, K), ...).  Variants: 0 = 128 x 128 tile, 1 = 256 x 256 tile, 2 = 256 x 256 two-phase persistent.
+// t5_gemm_admits: the shapes a variant can run (the kernel-level entry points reject the others; the loader's geometry checks keep the encoder inside them)
 void t5_gemm(int epi, const void *A, const void *W, void *out, int M, int N, int K, hipStream_t s);
+int t5_gemm_pick(int M, int N, int K);
+bool t5_gemm_admits(int variant, int M, int N, int K);
+void t5_gemm_run(int variant, int epi, const void *A, const void *W, void *out, int M, int N, int K, hipStream_t s);
 void t5_embed(const int32_t *tok, const void *emb, float *hidden, int T, int D, int vocab, hipStream_t s);
 void t5_rmsnorm(const float *x, const float *w, void *y, int T, int D, float eps, hipStream_t s);
 void t5_attention(const void *qkv, const T5AttnTile *tiles, int n_tiles, const float *bias, int bias_span, int H, void *out, hipStream_t s);
 void t5_cnn_head(const void *y, int ldy, const int32_t *seq_of, const int32_t *seq_off, const float *b1, const float *w2, const float *b2, float *h1,
                  uint8_t *codes, float *logits, int T, int C1, int KW, int NO, int eos_in_head, hipStream_t s);
 void t5_f32_to_f16(const float *x, void *y, size_t n, hipStream_t s);
+
+// ---- host-side pieces shared by T5Model and the kernel-level entry points (uc_capi.cpp) ----------------------------------------
+// the attention workgroups of a packed batch: one tile per 128 queries of each sequence (seq_off: n_seqs + 1 token offsets)
+void t5_attn_tiles(const int32_t *seq_off, size_t n_seqs, std::vector<T5AttnTile> &tiles);
+// the per-head bias over key - query in (-span, span): out[h * (2 span - 1) + rel + span - 1] = rel_bias[h * buckets + bucket(rel)]
+void t5_bias_table(int H, int buckets, int max_dist, int span, const float *rel_bias, float *out);
+// conv1 as one GEMM: W1r[k * C1 + c][d] = w1[c][d][k] (w1 in GGUF / torch Conv1d order), rows C1 * KW .. ldc1 - 1 zero
+inline int t5_conv1_rows(int C1, int KW) { return (KW * C1 + 127) / 128 * 128; }
+std::vector<float> t5_conv1_rearrange(const float *w1, int C1, int D, int KW);
 
 // ---- the model on one GPU ------------------------------------------------------------------------------------------------------
 struct T5Stats {

@@ -18,6 +18,7 @@
 #include <algorithm>
 #include <cstdint>
 #include <cstdlib>
+#include <mutex>
 
 #include "uc_t5.h"
 
@@ -434,17 +435,17 @@ __global__ void __launch_bounds__(512) t5_gemm256x_kernel(const _Float16 *__rest
 template <int EPI>
 static void t5_gemm256x_launch(const void *A, const void *W, void *out, int M, int N, int K, hipStream_t s) {
     constexpr int LDS = 2 * 4 * 128 * GBK * 2;
-    static bool once[64] = {};
+    // per device, once: encoder replicas on several host threads (and the kernel-level entry points) reach this concurrently
+    static std::once_flag once[64];
     static int cus[64] = {};
     int dev = 0;
     (void)hipGetDevice(&dev);
     if (dev < 0 || dev >= 64) dev = 0;
-    if (!once[dev]) {
+    std::call_once(once[dev], [dev] {
         (void)hipFuncSetAttribute((const void *)t5_gemm256x_kernel<EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
         hipDeviceProp_t pr;
         cus[dev] = hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount >= 8 ? pr.multiProcessorCount : 256;
-        once[dev] = true;
-    }
+    });
     const int gxm = 2;     // M-tiles per XCD group (swept in r03: profiles/r03_t5_gxm*.log)
     const int nn = N / HBN_, nm = (M + HBM_ - 1) / HBM_, n_local = ((nm + 7) / 8 + gxm - 1) / gxm * gxm * nn;
     const int slots = std::min(n_local, std::max(1, cus[dev] / 8));
@@ -454,34 +455,49 @@ static void t5_gemm256x_launch(const void *A, const void *W, void *out, int M, i
 template <int EPI>
 static void t5_gemm256_launch(const void *A, const void *W, void *out, int M, int N, int K, hipStream_t s) {
     constexpr int LDS = 2 * 2 * HBM_ * GBK * 2;
-    static bool once[64] = {};
+    static std::once_flag once[64];
     int dev = 0;
     (void)hipGetDevice(&dev);
-    if (dev >= 0 && dev < 64 && !once[dev]) {
-        (void)hipFuncSetAttribute((const void *)t5_gemm256_kernel<EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        once[dev] = true;
-    }
+    if (dev >= 0 && dev < 64)
+        std::call_once(once[dev], [] { (void)hipFuncSetAttribute((const void *)t5_gemm256_kernel<EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS); });
     const int nn = (N + HBN_ - 1) / HBN_, nm = (M + HBM_ - 1) / HBM_, per_xcd = ((nm + 7) / 8 + GXM - 1) / GXM * GXM;
     hipLaunchKernelGGL(t5_gemm256_kernel<EPI>, dim3((unsigned)(8 * per_xcd * nn)), dim3(512), LDS, s, (const _Float16 *)A, (const _Float16 *)W, out, M, N, K);
 }
 
-void t5_gemm(int epi, const void *A, const void *W, void *out, int M, int N, int K, hipStream_t s) {
-    if (M <= 0) return;
-    // UC_T5_GEMM256: 0 = 128 x 128 tile only, 1 = 256 x 256 tile, 8 waves of 128 x 64, one barrier per K-step (r3), 2 (default) = the same tile worked off in
-    // two phases per K-step by persistent workgroups (t5_gemm256x_kernel).  All sum K in the same order: bit-identical results (tools/t5_gemm_ab.py).
-    // Measured and NOT kept in the library (r4; numbers in profiles/r03_t5_gemm_ab*.json, profiles/r03_gemm_supply.log): a 256 x 256 tile with FOUR waves of
-    // 128 x 128 and AGPR accumulators (tools/experiments/uc_t5_gemm4w.hip: 693 TFLOP/s for the 24-block encoder against 739 with the 128 x 128 tile - one wave
-    // per SIMD leaves nobody to cover its barrier and wait stalls); four phases of 16 MFMAs per K-step (+3 % over the one-barrier kernel, +5.5 % persistent;
-    // superseded by the two-phase kernel, +8.5 %); a ten-slot ring of half-tiles over all 160 KB of LDS (seven half-tiles in flight: 5 % slower); a start skew
-    // between the workgroups of an XCD (no effect); a wait that names the epilogue's stores so that loads issued before them are not held up (no effect).
+// UC_T5_GEMM256: 0 = 128 x 128 tile only, 1 = 256 x 256 tile, 8 waves of 128 x 64, one barrier per K-step (r3), 2 (default) = the same tile worked off in
+// two phases per K-step by persistent workgroups (t5_gemm256x_kernel).  All sum K in the same order: bit-identical results (tools/t5_gemm_ab.py,
+// tests/test_t5_kernels.py).
+// Measured and NOT kept in the library (r4; numbers in profiles/r03_t5_gemm_ab*.json, profiles/r03_gemm_supply.log): a 256 x 256 tile with FOUR waves of
+// 128 x 128 and AGPR accumulators (tools/experiments/uc_t5_gemm4w.hip: 693 TFLOP/s for the 24-block encoder against 739 with the 128 x 128 tile - one wave
+// per SIMD leaves nobody to cover its barrier and wait stalls); four phases of 16 MFMAs per K-step (+3 % over the one-barrier kernel, +5.5 % persistent;
+// superseded by the two-phase kernel, +8.5 %); a ten-slot ring of half-tiles over all 160 KB of LDS (seven half-tiles in flight: 5 % slower); a start skew
+// between the workgroups of an XCD (no effect); a wait that names the epilogue's stores so that loads issued before them are not held up (no effect).
+int t5_gemm_pick(int M, int N, int K) {
     static const int big = getenv("UC_T5_GEMM256") ? atoi(getenv("UC_T5_GEMM256")) : 2;
-    if (big >= 2 && M >= 2048 && N % HBN_ == 0 && K % GBK == 0 && K >= 2 * GBK && (size_t)M * K * 2 < (1ull << 32) && (size_t)N * K * 2 < (1ull << 32)) {
+    if (big >= 2 && M >= 2048 && N % HBN_ == 0 && K % GBK == 0 && K >= 2 * GBK && (size_t)M * K * 2 < (1ull << 32) && (size_t)N * K * 2 < (1ull << 32)) return 2;
+    if (big && M >= 2048 && N % HBN_ == 0) return 1;     // large batches: the 256 x 256 tile (small ones would leave most CUs without a tile)
+    return 0;
+}
+
+bool t5_gemm_admits(int variant, int M, int N, int K) {
+    if (M < 1 || N < 4 || K < GBK || N % 4 || K % GBK) return false;           // every variant: whole K-tiles, 4-column epilogue stores
+    switch (variant) {
+        case 0: return true;
+        case 1: return N % HBN_ == 0;
+        case 2: return N % HBN_ == 0 && K >= 2 * GBK && (size_t)M * K * 2 < (1ull << 32) && (size_t)N * K * 2 < (1ull << 32);   // 32-bit staging offsets
+        default: return false;
+    }
+}
+
+void t5_gemm_run(int variant, int epi, const void *A, const void *W, void *out, int M, int N, int K, hipStream_t s) {
+    if (M <= 0) return;
+    if (variant == 2) {
         if (epi == 0) t5_gemm256x_launch<0>(A, W, out, M, N, K, s);
         else if (epi == 1) t5_gemm256x_launch<1>(A, W, out, M, N, K, s);
         else t5_gemm256x_launch<2>(A, W, out, M, N, K, s);
         return;
     }
-    if (big && M >= 2048 && N % HBN_ == 0) {     // large batches: the 256 x 256 tile (small ones would leave most CUs without a tile)
+    if (variant == 1) {
         if (epi == 0) t5_gemm256_launch<0>(A, W, out, M, N, K, s);
         else if (epi == 1) t5_gemm256_launch<1>(A, W, out, M, N, K, s);
         else t5_gemm256_launch<2>(A, W, out, M, N, K, s);
@@ -492,6 +508,11 @@ void t5_gemm(int epi, const void *A, const void *W, void *out, int M, int N, int
     if (epi == 0) hipLaunchKernelGGL(t5_gemm_kernel<0>, grid, dim3(256), 0, s, (const _Float16 *)A, (const _Float16 *)W, out, M, N, K);
     else if (epi == 1) hipLaunchKernelGGL(t5_gemm_kernel<1>, grid, dim3(256), 0, s, (const _Float16 *)A, (const _Float16 *)W, out, M, N, K);
     else hipLaunchKernelGGL(t5_gemm_kernel<2>, grid, dim3(256), 0, s, (const _Float16 *)A, (const _Float16 *)W, out, M, N, K);
+}
+
+void t5_gemm(int epi, const void *A, const void *W, void *out, int M, int N, int K, hipStream_t s) {
+    if (M <= 0) return;
+    t5_gemm_run(t5_gemm_pick(M, N, K), epi, A, W, out, M, N, K, s);
 }
 
 // ---------------------------------------------------------------------------------------------- embedding / RMSNorm
