@@ -260,6 +260,18 @@ int uc_engine_ungapped_batch(uc_engine *e, uint64_t n, const uint32_t *q, const 
 int uc_engine_sw_batch(uc_engine *e, int mode, uint64_t n, const uint32_t *q, const uint32_t *t,
                        const int32_t *qend_in, const int32_t *tend_in,
                        int32_t *score_out, int32_t *qend_out, int32_t *tend_out);
+/* ONE pass of the gapped stage on n pairs, as Engine::align runs it: class table `table` (0: int32, 1: packed, 2: int32 traceback
+ * statistics, 3: packed sparse) and mode - table 0: 0, 1, 2;  1: 0, 1, 2, 4, 6, 7;  2: 3;  3: 4, 6 (4 / 6: modes 0 / 2 with the optimum
+ * known; 7: traceback bytes + walk).  box [n][4] = (qs, qe, ts, te): modes 2 / 6 read qe, te (forward end), modes 3 / 7 the whole box;
+ * known [n] (> 0): modes 4, 6, 7 (7: the box's score).  band: half-width W of the stored band of mode 7 (0 = whole box).
+ * raw = 1: the kernels' outputs as they are (packed: qend -2 for an ambiguous end row, scores >= the packed range limit; mode 7: pairs
+ * whose walk left the band keep aln_len = idents = gaps = -1).  raw = 0: the library's re-run rules (int32 re-runs, mode 7 scores beyond
+ * the packed range in int32 mode 3, band misses with the whole box).  Outputs (any may be NULL): score, qend, tend (modes 0 / 2 / 4 / 6;
+ * tend keeps the one-row bit 1 << 30 of mode 6), class (the table's class of the pair, its class count = long-query kernel),
+ * aln_len / idents / gaps (modes 3 / 7), miss (mode 7, band > 0: the walk left the band).  Anything else is UC_ERR_ARGS. */
+int uc_engine_sw_pass(uc_engine *e, int table, int mode, int band, int raw, uint64_t n, const uint32_t *q, const uint32_t *t,
+                      const int32_t *box, const int32_t *known, int32_t *score_out, int32_t *qend_out, int32_t *tend_out,
+                      int32_t *class_out, int32_t *aln_len_out, int32_t *idents_out, int32_t *gaps_out, int32_t *miss_out);
 
 /* ---- kernel-level entry points of the ProstT5 encoder (tests/test_t5_kernels.py calls the HIP kernels through these).
  * Each device call takes host arrays: it allocates, copies, runs the library's own launcher on `device` (-1 = the current one),

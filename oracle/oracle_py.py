@@ -89,6 +89,9 @@ def lib():
                          C.POINTER(Params), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.uco_min_score.argtypes = [C.POINTER(Params), C.c_int, C.c_uint64]
     L.uco_min_score.restype = C.c_int32
+    L.uco_traceback.argtypes = [C.POINTER(Db), C.c_uint32, C.c_uint32, C.POINTER(Params), C.c_int, C.c_int, C.c_int, C.c_int,
+                                C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    L.uco_traceback.restype = None
     L.uco_align_pair.argtypes = [C.POINTER(Db), C.c_uint32, C.c_uint32, C.POINTER(Params), C.c_int32, C.POINTER(Aln)]
     L.uco_setcover.argtypes = [C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p]
     L.uco_cluster.argtypes = [C.POINTER(Db), C.POINTER(Params), C.c_int, C.c_void_p, C.POINTER(Counts), C.c_void_p, C.c_void_p, C.c_void_p]
@@ -417,6 +420,13 @@ def align_pair(odb, p, q, t, min_score):
     out = np.zeros(1, ALN_DTYPE)
     lib().uco_align_pair(C.byref(odb.db), int(q), int(t), C.byref(p), int(min_score), out.ctypes.data)
     return out[0]
+
+
+def traceback(odb, p, q, t, qs, qe, ts, te):
+    """the scalar oracle's traceback statistics (alignment length, identities, gap opens) of the box [qs..qe] x [ts..te]"""
+    ln, idn, gp = C.c_int32(), C.c_int32(), C.c_int32()
+    lib().uco_traceback(C.byref(odb.db), int(q), int(t), C.byref(p), int(qs), int(qe), int(ts), int(te), C.byref(ln), C.byref(idn), C.byref(gp))
+    return ln.value, idn.value, gp.value
 
 
 def min_score(odb, p, q):

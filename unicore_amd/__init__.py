@@ -62,7 +62,7 @@ SYMBOLS = (
     "uc_engine_hits_export_dev", "uc_engine_hits_import_dev", "uc_engine_setcover",
     "uc_hits_merge", "uc_engine_align", "uc_engine_alns_get", "uc_engine_edges_size", "uc_engine_edges_get",
     "uc_engine_stats", "uc_engine_reset_stats", "uc_setcover", "uc_write_cluster_db",
-    "uc_engine_ungapped_batch", "uc_engine_sw_batch", "uc_abi_version", "uc_stats_size", "uc_set_round_hook",
+    "uc_engine_ungapped_batch", "uc_engine_sw_batch", "uc_engine_sw_pass", "uc_abi_version", "uc_stats_size", "uc_set_round_hook",
     "uc_t5_gemm_variant", "uc_t5_kernel_gemm", "uc_t5_kernel_rmsnorm", "uc_t5_kernel_attention", "uc_t5_kernel_cnn_head", "uc_t5_bias_table",
 )
 ABI_VERSION = 6      # == UC_ABI_VERSION of include/unicore_cluster.h this binding mirrors
@@ -136,6 +136,7 @@ def lib():
     L.uc_write_cluster_db.argtypes = [C.c_char_p, u32, vp]
     L.uc_engine_ungapped_batch.argtypes = [vp, u64, vp, vp, vp, vp]
     L.uc_engine_sw_batch.argtypes = [vp, C.c_int, u64, vp, vp, vp, vp, vp, vp, vp]
+    L.uc_engine_sw_pass.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, u64, vp, vp, vp, vp] + [vp] * 8
     L.uc_t5_gemm_variant.argtypes = [i32, i32, i32, C.POINTER(i32)]
     L.uc_t5_kernel_gemm.argtypes = [i32, i32, i32, i32, i32, i32, vp, vp, vp]
     L.uc_t5_kernel_rmsnorm.argtypes = [i32, i32, i32, C.c_float, vp, vp, vp]
@@ -536,3 +537,17 @@ class Engine:
                                         qe.ctypes.data if qe is not None else None, te.ctypes.data if te is not None else None,
                                         s.ctypes.data, oq.ctypes.data, ot.ctypes.data))
         return s, oq, ot
+
+    def sw_pass(self, table, mode, q, t, box=None, known=None, band=0, raw=False):
+        """ONE gapped pass (class table, mode) on the pairs (q[i], t[i]), as Engine.align runs it (uc_engine_sw_pass):
+        box [n, 4] = (qs, qe, ts, te), known [n] optimum scores.  Returns a dict of int32 arrays: score, qe, te, cls,
+        aln_len, idents, gaps, miss."""
+        q = np.ascontiguousarray(q, np.uint32); t = np.ascontiguousarray(t, np.uint32)
+        n = len(q)
+        bx = np.ascontiguousarray(box, np.int32).reshape(n, 4) if box is not None else None
+        kn = np.ascontiguousarray(known, np.int32) if known is not None else None
+        out = {k: np.full(n, -1, np.int32) for k in ("score", "qe", "te", "cls", "aln_len", "idents", "gaps", "miss")}
+        _check(lib().uc_engine_sw_pass(self._h, table, mode, band, int(bool(raw)), n, q.ctypes.data, t.ctypes.data,
+                                       bx.ctypes.data if bx is not None else None, kn.ctypes.data if kn is not None else None,
+                                       *[out[k].ctypes.data for k in ("score", "qe", "te", "cls", "aln_len", "idents", "gaps", "miss")]))
+        return out

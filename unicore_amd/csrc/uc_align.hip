@@ -1400,6 +1400,131 @@ static void run_tb(Engine &E, const AlignBatch &B, const uint32_t *flag, int ban
     if (band_w > 0) tb_segments(E, B, A.tb_tmiss.p, 0, budget);          // tracebacks that left their band: the whole box
 }
 
+// the class a plan of table `tab` puts each pair in (class_of, as plan_key_kernel keys it; c_tab[tab].n = long-query kernel)
+__global__ void __launch_bounds__(256) pass_class_kernel(uint32_t n, const uint32_t *q, const uint32_t *len, int tab, int32_t *out) {
+    for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) out[i] = class_of((int)len[q[i]], tab);
+}
+// the records the traceback passes read their boxes and end-cell scores from
+__global__ void __launch_bounds__(256) pass_records_kernel(uint32_t n, const int32_t *qs, const int32_t *qe, const int32_t *ts, const int32_t *te,
+                                                           const int32_t *known, uc_aln *out, uint32_t *iota, uint32_t *all) {
+    for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+        uc_aln a = {};
+        a.score = known ? known[i] : 0;
+        a.qstart = qs[i]; a.qend = qe[i]; a.tstart = ts[i]; a.tend = te[i];
+        a.aln_len = -1; a.idents = -1; a.gap_opens = -1;
+        out[i] = a;
+        iota[i] = i;
+        all[i] = 1u;
+    }
+}
+
+// ---- kernel-level entry point: ONE gapped pass (table, mode) on a pair list from the host -----------
+// The passes of Engine::align on a list the caller chooses: build_plan + launch_plan (raw) or run_plan (the library's re-run rules) for
+// MODE 0/1/2/4/6; the traceback passes through run_tb / tb_batch / tb_run_bytes on a batch whose gate passers are exactly the listed pairs.
+static bool sw_pass_allowed(int tab, int mode) {
+    switch (tab) {
+    case 0: return mode == 0 || mode == 1 || mode == 2;
+    case 1: return mode == 0 || mode == 1 || mode == 2 || mode == 4 || mode == 6 || mode == 7;
+    case 2: return mode == 3;
+    case 3: return mode == 4 || mode == 6;
+    default: return false;
+    }
+}
+
+void Engine::sw_pass(int tab, int mode, int band, bool raw, const std::vector<SwPassPair> &pairs, const SwPassOut &o) {
+    PressureScope ps(*this, 1);
+    if (!have_db) fail(UC_ERR_ARGS, "no database loaded");
+    if (!sw_pass_allowed(tab, mode)) fail(UC_ERR_ARGS, "sw_pass: no such (table, mode)");
+    if (mode == 7 && (!tb_bytes_ok(p) || !p.sw_pk)) fail(UC_ERR_ARGS, "sw_pass: MODE 7 needs the byte walk's score range and the packed kernel");
+    if (band < 0) fail(UC_ERR_ARGS, "sw_pass: negative band");
+    const size_t n = pairs.size();
+    if (n == 0) return;
+    if (n >= (1ull << 31)) fail(UC_ERR_ARGS, "sw_pass: too many pairs");
+    const bool ends = mode == 2 || mode == 6, box = mode == 3 || mode == 7, known = mode == 4 || mode == 6 || mode == 7;
+    for (size_t i = 0; i < n; i++) {
+        const SwPassPair &x = pairs[i];
+        if (x.q >= hdb.n || x.t >= hdb.n) fail(UC_ERR_ARGS, "sw_pass: sequence id out of range");
+        const int lq = (int)h_len[x.q], lt = (int)h_len[x.t];
+        if ((ends || box) && (x.qe < 0 || x.te < 0 || x.qe >= lq || x.te >= lt)) fail(UC_ERR_ARGS, "sw_pass: end position out of range");
+        if (box && (x.qs < 0 || x.ts < 0 || x.qs > x.qe || x.ts > x.te)) fail(UC_ERR_ARGS, "sw_pass: box start out of range");
+        if (known && x.known <= 0) fail(UC_ERR_ARGS, "sw_pass: known score missing");
+    }
+    UC_HIP(hipSetDevice(device));
+    std::vector<uint32_t> hq(n), ht(n);
+    std::vector<int32_t> hqs(n), hqe(n), hts(n), hte(n), hk(n);
+    for (size_t i = 0; i < n; i++) {
+        const SwPassPair &x = pairs[i];
+        hq[i] = x.q; ht[i] = x.t; hqs[i] = x.qs; hqe[i] = x.qe; hts[i] = x.ts; hte[i] = x.te; hk[i] = x.known;
+    }
+    const uint32_t nn = (uint32_t)n;
+    DevBuf<uint32_t> dq, dt;
+    DevBuf<int32_t> dqs, dqe, dts, dte, dk, os, oq, ot, rs, rq, rt, cls;
+    auto up = [&](auto &d, const auto &h) { d.reserve(n); UC_HIP(hipMemcpyAsync(d.p, h.data(), n * 4, hipMemcpyHostToDevice, stream)); };
+    up(dq, hq); up(dt, ht); up(dqs, hqs); up(dqe, hqe); up(dts, hts); up(dte, hte); up(dk, hk);
+    cls.reserve(n);
+    auto down = [&](int32_t *h, const int32_t *d) { if (h) UC_HIP(hipMemcpyAsync(h, d, n * 4, hipMemcpyDeviceToHost, stream)); };
+    // (after the pass: build_plan is what puts the class tables into this device's constant memory)
+    auto classes = [&] {
+        hipLaunchKernelGGL(pass_class_kernel, grid_for(nn), dim3(256), 0, stream, nn, dq.p, ddb.len, tab, cls.p);
+        down(o.cls, cls.p);
+    };
+    if (!box) {
+        const bool track = mode != 1;
+        DevBuf<int32_t> work;
+        DevBuf<char> tmp;
+        os.reserve(n); rs.reserve(n);
+        if (track) { oq.reserve(n); ot.reserve(n); rq.reserve(n); rt.reserve(n); }
+        SwPlan P;
+        build_plan(*this, P, tmp, nn, dq.p, dt.p, ends ? dqe.p : nullptr, ends ? dte.p : nullptr, tab, nullptr, nullptr, known ? dk.p : nullptr);
+        if (raw) launch_plan(*this, P, mode, os.p, oq.p, ot.p, work);
+        else run_plan(*this, P, mode, os.p, oq.p, ot.p, work, tmp);
+        hipLaunchKernelGGL(scatter3_kernel, grid_for(nn), dim3(256), 0, stream, nn, P.idx.p, os.p, oq.p, ot.p, rs.p, rq.p, rt.p);
+        classes();
+        down(o.score, rs.p);
+        if (track) { down(o.qe, rq.p); down(o.te, rt.p); }
+        UC_HIP(hipStreamSynchronize(stream));
+        UC_HIP(hipGetLastError());
+        return;
+    }
+    // traceback statistics: a batch whose gate passers are the listed pairs, in list order, with their boxes in the records
+    AlignScratch &A = scratch_of(*this);
+    DevBuf<uc_aln> recs;
+    DevBuf<uint32_t> iota, all;
+    recs.reserve(n); iota.reserve(n); all.reserve(n);
+    hipLaunchKernelGGL(pass_records_kernel, grid_for(nn), dim3(256), 0, stream, nn, dqs.p, dqe.p, dts.p, dte.p, dk.p, recs.p, iota.p, all.p);
+    A.q2.reserve(n); A.t2.reserve(n); A.link.reserve(n); A.iota2.reserve(n); A.eflag.reserve(n);
+    A.tb_trun.reserve(n); A.tb_tpos.reserve(n); A.tb_tpart.reserve(n); A.tb_ttie.reserve(n); A.tb_tmiss.reserve(n);
+    UC_HIP(hipMemcpyAsync(A.q2.p, dq.p, n * 4, hipMemcpyDeviceToDevice, stream));
+    UC_HIP(hipMemcpyAsync(A.t2.p, dt.p, n * 4, hipMemcpyDeviceToDevice, stream));
+    UC_HIP(hipMemcpyAsync(A.link.p, iota.p, n * 4, hipMemcpyDeviceToDevice, stream));
+    UC_HIP(hipMemcpyAsync(A.iota2.p, iota.p, n * 4, hipMemcpyDeviceToDevice, stream));
+    UC_HIP(hipMemcpyAsync(A.eflag.p, all.p, n * 4, hipMemcpyDeviceToDevice, stream));
+    UC_HIP(hipMemsetAsync(A.tb_ttie.p, 0, n * 4, stream));
+    UC_HIP(hipMemsetAsync(A.tb_tmiss.p, 0, n * 4, stream));
+    AlignBatch B{};
+    B.n = nn; B.n2 = nn; B.dq = dq.p; B.dt = dt.p; B.alns_b = recs.p; B.alns_list = recs.p; B.tab = tab; B.Lidx = iota.p;
+    struct Keep { Params &p; Params saved; ~Keep() { p = saved; } } keep{p, p};
+    p.want_tb = 1;         // both statistics: (alignment length, identities) and the gap count (the TB_GAPS weighting of MODE 3)
+    p.min_seq_id = 0.0f;   // no gate on the result
+    const TbBudget budget;
+    if (mode == 3) tb_batch(*this, B, all.p, false, 0, budget);
+    else if (raw) tb_batch(*this, B, all.p, true, band, budget);
+    else run_tb(*this, B, all.p, band, budget);
+    classes();
+    std::vector<uc_aln> h(n);
+    UC_HIP(hipMemcpyAsync(h.data(), recs.p, n * sizeof(uc_aln), hipMemcpyDeviceToHost, stream));
+    if (o.miss) UC_HIP(hipMemcpyAsync(o.miss, A.tb_tmiss.p, n * 4, hipMemcpyDeviceToHost, stream));
+    UC_HIP(hipStreamSynchronize(stream));
+    UC_HIP(hipGetLastError());
+    if (o.miss && (mode != 7 || band == 0)) memset(o.miss, 0, n * 4);
+    for (size_t i = 0; i < n; i++) {
+        if (o.score) o.score[i] = h[i].score;
+        if (o.aln_len) o.aln_len[i] = h[i].aln_len;
+        if (o.idents) o.idents[i] = h[i].idents;
+        if (o.gaps) o.gaps[i] = h[i].gap_opens;
+    }
+}
+
 // sequence-identity gate / BLAST-tab statistics: (alignment length, identities[, gaps]) of the traceback on
 // the box, for the pairs that passed the coverage gate
 static void traceback_stats(Engine &E, const AlignBatch &B) {

@@ -406,6 +406,26 @@ int uc_engine_sw_batch(uc_engine *e, int mode, uint64_t n, const uint32_t *q, co
     });
 }
 
+int uc_engine_sw_pass(uc_engine *e, int table, int mode, int band, int raw, uint64_t n, const uint32_t *q, const uint32_t *t,
+                      const int32_t *box, const int32_t *known, int32_t *score_out, int32_t *qend_out, int32_t *tend_out,
+                      int32_t *class_out, int32_t *aln_len_out, int32_t *idents_out, int32_t *gaps_out, int32_t *miss_out) {
+    return guard([&] {
+        require(e, "engine");
+        if (!n) return;
+        require(q, "q"); require(t, "t");
+        if (mode == 2 || mode == 3 || mode == 6 || mode == 7) require(box, "box");
+        if (mode == 4 || mode == 6 || mode == 7) require(known, "known");
+        std::vector<SwPassPair> pairs(n);
+        for (uint64_t i = 0; i < n; i++) {
+            SwPassPair &x = pairs[i];
+            x.q = q[i]; x.t = t[i];
+            x.qs = box ? box[4 * i] : 0; x.qe = box ? box[4 * i + 1] : 0; x.ts = box ? box[4 * i + 2] : 0; x.te = box ? box[4 * i + 3] : 0;
+            x.known = known ? known[i] : 0;
+        }
+        e->e->sw_pass(table, mode, band, raw != 0, pairs, {score_out, qend_out, tend_out, class_out, aln_len_out, idents_out, gaps_out, miss_out});
+    });
+}
+
 }  // extern "C"
 
 namespace {

@@ -137,6 +137,11 @@ inline dim3 grid_for(uint64_t n, uint32_t cap = 16384) {
 }
 
 struct PairIn { uint32_t q, t; int32_t qe, te; };
+// one pair of a single gapped pass (Engine::sw_pass): box [qs..qe] x [ts..te] (MODE 3 / 7; MODE 2 / 6 read qe, te only), known optimum (MODE 4 / 6 / 7)
+struct SwPassPair { uint32_t q, t; int32_t qs, qe, ts, te, known; };
+// its outputs in list order (any may be null): score, qe, te (MODE 0 / 2 / 4 / 6; te keeps SW_TE_UNIQUE), class id of the table,
+// traceback statistics (MODE 3 / 7) and the band-miss mark of the MODE 7 walk
+struct SwPassOut { int32_t *score, *qe, *te, *cls, *aln_len, *idents, *gaps, *miss; };
 struct PrefilterScratch;                                  // uc_prefilter.hip
 void free_scratch(PrefilterScratch *p);
 struct AlignScratch;                                      // uc_align.hip
@@ -281,6 +286,7 @@ struct Engine {
     // kernel-level
     void ungapped_batch(uint64_t n, const uint32_t *q, const uint32_t *t, const int32_t *diag, int32_t *out);
     void sw_batch(int mode, const std::vector<PairIn> &pairs, int32_t *score, int32_t *qe, int32_t *te);
+    void sw_pass(int tab, int mode, int band, bool raw, const std::vector<SwPassPair> &pairs, const SwPassOut &out);
 
     double timed_ms_begin();   // records ev0 on the stream
     double timed_ms_end();     // records ev1, syncs, returns elapsed ms
