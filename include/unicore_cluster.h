@@ -46,7 +46,7 @@ typedef struct uc_opts {
 /* ABI revision of this header: bumped whenever a struct below grows or an entry point changes meaning.  uc_stats is written in full by
  * uc_cluster / uc_search / uc_engine_stats and carries no size field of its own, so a caller built against an older header must check
  * uc_abi_version() == UC_ABI_VERSION (or uc_stats_size() == sizeof(uc_stats)) before passing one in. */
-#define UC_ABI_VERSION 6
+#define UC_ABI_VERSION 7
 uint32_t uc_abi_version(void);
 size_t uc_stats_size(void);
 
@@ -272,6 +272,31 @@ int uc_engine_sw_batch(uc_engine *e, int mode, uint64_t n, const uint32_t *q, co
 int uc_engine_sw_pass(uc_engine *e, int table, int mode, int band, int raw, uint64_t n, const uint32_t *q, const uint32_t *t,
                       const int32_t *box, const int32_t *known, int32_t *score_out, int32_t *qend_out, int32_t *tend_out,
                       int32_t *class_out, int32_t *aln_len_out, int32_t *idents_out, int32_t *gaps_out, int32_t *miss_out);
+
+/* ---- alignment backtraces (-a; ABI 7).  A backtrace is a slice of runs, each `length << 2 | op` with op 0 = M (diagonal step, match or
+ * mismatch), 1 = I (query residue only), 2 = D (target residue only), from the start of the alignment to its end; adjacent runs differ in op.
+ * An engine created with -a in its options keeps them on the device for every hit uc_engine_align accepts.
+ * uc_engine_backtraces_get is aligned with uc_engine_alns_get: run_off holds one entry per hit of the query range plus one, slice k is
+ * runs[run_off[k] .. run_off[k + 1]), empty for hits that were not accepted.  uc_engine_backtraces_size gives the length of `runs`. */
+int uc_engine_backtraces_size(const uc_engine *e, uint32_t qbegin, uint32_t qend, uint64_t *n_runs);
+int uc_engine_backtraces_get(const uc_engine *e, uint32_t qbegin, uint32_t qend, uint64_t *run_off, uint32_t *runs);
+/* A slice as text ("35M2D110M1I7M"), NUL-terminated, as uc_search -a writes it into the 15th field of an alignment-DB row and
+ * uc_convertalis prints it in its `cigar` column.  len_out (optional) receives the length without the NUL; a buffer that is too
+ * small and a word that is no run are UC_ERR_ARGS. */
+int uc_backtrace_render(const uint32_t *runs, uint64_t n_runs, char *out, uint64_t out_capacity, uint64_t *len_out);
+/* uc_convertalis reads `--format-output LIST` from uc_opts.cluster_options (comma-separated column names; default: the 12 BLAST-tab
+ * columns).  This checks a LIST the same way: UC_OK and the number of columns, or UC_ERR_ARGS for an unknown name. */
+int uc_format_output_check(const char *list, uint32_t *n_columns);
+/* Kernel-level sibling of uc_engine_sw_pass: ONE traceback pass with emission on the n boxes box[4 i ..] = (qs, qe, ts, te), raw (no redo
+ * of band misses), by route: 0 = table 1 MODE 7 + walk with half band `band`, 1 = the same with the whole box stored, 2 = the stored
+ * int32 matrix for every pair (the route of scores beyond the packed range and of the all-int32 configuration), 3 = the long-query route
+ * of the packed pass (every query must be longer than the systolic classes; routes 0 / 1 take only shorter ones).  known[i] = the
+ * box's optimum score (routes 0, 1, 3).  Outputs in list order, any may be NULL except run_off (n + 1): class of table 1, statistics,
+ * band-miss mark, plain_out = 1 where the stored-int32-matrix kernels served the pair, and the slices (empty for a band miss).
+ * More runs than runs_capacity is UC_ERR_ARGS with the number needed in *n_runs. */
+int uc_engine_tb_emit_pass(uc_engine *e, int route, int band, uint64_t n, const uint32_t *q, const uint32_t *t, const int32_t *box, const int32_t *known,
+                           int32_t *class_out, int32_t *aln_len_out, int32_t *idents_out, int32_t *gaps_out, int32_t *miss_out, int32_t *plain_out,
+                           uint64_t *run_off, uint32_t *runs, uint64_t runs_capacity, uint64_t *n_runs);
 
 /* ---- kernel-level entry points of the ProstT5 encoder (tests/test_t5_kernels.py calls the HIP kernels through these).
  * Each device call takes host arrays: it allocates, copies, runs the library's own launcher on `device` (-1 = the current one),

@@ -62,10 +62,11 @@ SYMBOLS = (
     "uc_engine_hits_export_dev", "uc_engine_hits_import_dev", "uc_engine_setcover",
     "uc_hits_merge", "uc_engine_align", "uc_engine_alns_get", "uc_engine_edges_size", "uc_engine_edges_get",
     "uc_engine_stats", "uc_engine_reset_stats", "uc_setcover", "uc_write_cluster_db",
-    "uc_engine_ungapped_batch", "uc_engine_sw_batch", "uc_engine_sw_pass", "uc_abi_version", "uc_stats_size", "uc_set_round_hook",
+    "uc_engine_ungapped_batch", "uc_engine_sw_batch", "uc_engine_sw_pass", "uc_engine_backtraces_size", "uc_engine_backtraces_get",
+    "uc_backtrace_render", "uc_format_output_check", "uc_engine_tb_emit_pass", "uc_abi_version", "uc_stats_size", "uc_set_round_hook",
     "uc_t5_gemm_variant", "uc_t5_kernel_gemm", "uc_t5_kernel_rmsnorm", "uc_t5_kernel_attention", "uc_t5_kernel_cnn_head", "uc_t5_bias_table",
 )
-ABI_VERSION = 6      # == UC_ABI_VERSION of include/unicore_cluster.h this binding mirrors
+ABI_VERSION = 7      # == UC_ABI_VERSION of include/unicore_cluster.h this binding mirrors
 ROUND_HOOK = C.CFUNCTYPE(None, C.c_void_p, C.c_int32, C.c_uint32, C.POINTER(C.c_uint32), C.c_int32, C.c_void_p)
 
 _lib = None
@@ -137,6 +138,11 @@ def lib():
     L.uc_engine_ungapped_batch.argtypes = [vp, u64, vp, vp, vp, vp]
     L.uc_engine_sw_batch.argtypes = [vp, C.c_int, u64, vp, vp, vp, vp, vp, vp, vp]
     L.uc_engine_sw_pass.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, u64, vp, vp, vp, vp] + [vp] * 8
+    L.uc_engine_backtraces_size.argtypes = [vp, u32, u32, C.POINTER(u64)]
+    L.uc_engine_backtraces_get.argtypes = [vp, u32, u32, vp, vp]
+    L.uc_backtrace_render.argtypes = [vp, u64, C.c_char_p, u64, C.POINTER(u64)]
+    L.uc_format_output_check.argtypes = [C.c_char_p, C.POINTER(u32)]
+    L.uc_engine_tb_emit_pass.argtypes = [vp, C.c_int, C.c_int, u64, vp, vp, vp, vp] + [vp] * 6 + [vp, vp, u64, C.POINTER(u64)]
     L.uc_t5_gemm_variant.argtypes = [i32, i32, i32, C.POINTER(i32)]
     L.uc_t5_kernel_gemm.argtypes = [i32, i32, i32, i32, i32, i32, vp, vp, vp]
     L.uc_t5_kernel_rmsnorm.argtypes = [i32, i32, i32, C.c_float, vp, vp, vp]
@@ -199,10 +205,25 @@ def search(query_db, target_db, out_aln_db, tmp, search_options="-c 0.8", thread
     return st.as_dict()
 
 
-def convertalis(query_db, target_db, aln_db, out_m8, verbosity=1):
-    """== `foldseek convertalis` (search.rs:57-60)"""
-    o = make_opts("", 1, verbosity)
+def convertalis(query_db, target_db, aln_db, out_m8, verbosity=1, format_output=None):
+    """== `foldseek convertalis` (search.rs:57-60); format_output: the LIST of --format-output (None = the 12 BLAST-tab columns)"""
+    o = make_opts("--format-output %s" % format_output if format_output else "", 1, verbosity)
     _check(lib().uc_convertalis(query_db.encode(), target_db.encode(), aln_db.encode(), out_m8.encode(), C.byref(o)))
+
+
+def render_backtrace(runs):
+    """run words (length << 2 | op; 0 M, 1 I, 2 D) -> "35M2D110M" (uc_backtrace_render: the text of the alignment DB's 15th field)"""
+    r = np.ascontiguousarray(runs, np.uint32)
+    buf = C.create_string_buffer(12 * len(r) + 1)
+    _check(lib().uc_backtrace_render(r.ctypes.data, len(r), buf, len(buf), None))
+    return buf.value.decode()
+
+
+def format_output_columns(names):
+    """number of columns of a --format-output LIST; UcError for an unknown name"""
+    k = C.c_uint32(0)
+    _check(lib().uc_format_output_check(names.encode(), C.byref(k)))
+    return k.value
 
 
 def rmdb(prefix):
@@ -537,6 +558,38 @@ class Engine:
                                         qe.ctypes.data if qe is not None else None, te.ctypes.data if te is not None else None,
                                         s.ctypes.data, oq.ctypes.data, ot.ctypes.data))
         return s, oq, ot
+
+    def backtraces(self, qbegin=0, qend=None):
+        """(run_off, runs) of the hits of queries [qbegin, qend), aligned with alns_range: slice k = runs[run_off[k]:run_off[k + 1]],
+        words length << 2 | op (0 M, 1 I, 2 D); needs -a in the engine's options (uc_engine_backtraces_get)"""
+        qend = self.n if qend is None else qend
+        k = C.c_uint64(0)
+        _check(lib().uc_engine_backtraces_size(self._h, qbegin, qend, C.byref(k)))
+        nh = C.c_uint64(0)
+        _check(lib().uc_engine_hits_size(self._h, C.byref(nh)))
+        off = np.zeros(nh.value + 2, np.uint64)       # at least one per hit of the range + 1
+        runs = np.zeros(max(k.value, 1), np.uint32)
+        _check(lib().uc_engine_backtraces_get(self._h, qbegin, qend, off.ctypes.data, runs.ctypes.data))
+        return off, runs[: k.value]
+
+    def tb_emit_pass(self, route, q, t, box, known=None, band=0):
+        """ONE traceback pass with backtrace emission (uc_engine_tb_emit_pass): route 0 banded packed MODE 7 + walk, 1 whole box,
+        2 stored int32 matrix, 3 long-query route.  Returns a dict: cls, aln_len, idents, gaps, miss, plain (int32) and cigar (list of str)."""
+        q = np.ascontiguousarray(q, np.uint32); t = np.ascontiguousarray(t, np.uint32)
+        n = len(q)
+        bx = np.ascontiguousarray(box, np.int32).reshape(n, 4)
+        kn = np.ascontiguousarray(known, np.int32) if known is not None else None
+        out = {k: np.full(n, -1, np.int32) for k in ("cls", "aln_len", "idents", "gaps", "miss", "plain")}
+        cap = int((bx[:, 1] - bx[:, 0] + 1).sum() + (bx[:, 3] - bx[:, 2] + 1).sum()) + 1     # a path has at most rows + columns steps
+        off = np.zeros(n + 1, np.uint64)
+        runs = np.zeros(cap, np.uint32)
+        k = C.c_uint64(0)
+        _check(lib().uc_engine_tb_emit_pass(self._h, route, band, n, q.ctypes.data, t.ctypes.data, bx.ctypes.data,
+                                            kn.ctypes.data if kn is not None else None,
+                                            *[out[x].ctypes.data for x in ("cls", "aln_len", "idents", "gaps", "miss", "plain")],
+                                            off.ctypes.data, runs.ctypes.data, cap, C.byref(k)))
+        out["cigar"] = [render_backtrace(runs[int(off[i]):int(off[i + 1])]) if off[i + 1] > off[i] else "" for i in range(n)]
+        return out
 
     def sw_pass(self, table, mode, q, t, box=None, known=None, band=0, raw=False):
         """ONE gapped pass (class table, mode) on the pairs (q[i], t[i]), as Engine.align runs it (uc_engine_sw_pass):

@@ -137,7 +137,9 @@ int search_run(const std::string &input, const std::string &target, const std::s
     int rc = uc_search(target.c_str(), input.c_str(), output_aln_db.c_str(), tmp.c_str(), &o, nullptr);   // search.rs:45-55
     if (rc != 0) error(ERR_GENERAL, std::string("search engine failed with code ") + std::to_string(rc) + "\n" + uc_last_error());
     println_message(" Done", 3);
-    rc = uc_convertalis(target.c_str(), input.c_str(), output_aln_db.c_str(), output_m8.c_str(), &o);     // search.rs:57-63
+    uc_opts oc = o;
+    oc.cluster_options = "";   // convertalis gets no options (search.rs:57-60): OUTPUT.m8 is the 12 default columns whatever the search options say
+    rc = uc_convertalis(target.c_str(), input.c_str(), output_aln_db.c_str(), output_m8.c_str(), &oc);    // search.rs:57-63
     if (rc != 0) error(ERR_GENERAL, std::string("convertalis failed with code ") + std::to_string(rc) + "\n" + uc_last_error());
     if (!keep_aln_db) {                                                                                   // search.rs:66-75
         rc = uc_rmdb(output_aln_db.c_str());

@@ -506,35 +506,69 @@ __global__ void __launch_bounds__(256) tb_size_kernel(uint32_t n_pk, const uint6
 // of such values:  diagonal iff H(i,j) == H(i-1,j-1) + s(i,j);  H(i,j) == F(i,j) iff some k has H(i-k,j) - open - (k-1) ext == H(i,j),
 // and the search up the column ends at the first k with H(i-k,j) < H(i,j) + k ext (F <= H in every cell, so no gap that long or longer
 // can reach H(i,j));  inside a gap of value f the gap was opened from the neighbour iff H(neighbour) - open == f.  E likewise along the row.
+//
+// Backtraces (-a).  EMIT = 0: statistics only, the kernel of every call without -a.  EMIT = 1: the same walk also counts the runs of its path
+// (maximal stretches of one operation: M diagonal, I query residue only, D target residue only) into bt_cnt[p], 0 for a pair that left its band.
+// EMIT = 2: the walk again, writing run r of pair p as (length << 2 | op) into its slice bt_runs[bt_off[p] ..+ bt_cnt[p]) FROM THE TAIL (the walk goes
+// from the end of the alignment to its start), and where the slice lies in the engine's buffer into bt_pos[p].  A run that would fall outside
+// the slice is not written and raises *bt_err (the counts come from the same walk over the same bytes, so this never happens).
+// PLAIN = 1: the matrix is not the packed kernel's banded byte layout but a row-major int32 H of the box (tb_plain_dp_kernel), for the pairs the
+// packed kernel does not serve; everything else is the same walk.
+constexpr uint32_t BT_M = 0u, BT_I = 1u, BT_D = 2u, BT_NONE = 3u;
+template <int EMIT>
+struct BtSink {
+    uint32_t op = BT_NONE, len = 0, n = 0;
+    uint32_t *out = nullptr;     // the pair's slice
+    int w = 0;                   // next slot, counting down
+    bool ovf = false;
+    __device__ __forceinline__ void flush() {
+        if (op == BT_NONE) return;
+        if (EMIT == 2) { if (w >= 0) out[w] = (len << 2) | op; else ovf = true; w--; }
+        n++;
+    }
+    __device__ __forceinline__ void step(uint32_t o) {
+        if (o == op) { len++; return; }
+        flush();
+        op = o; len = 1;
+    }
+};
+template <int EMIT, int PLAIN>
 __global__ void __launch_bounds__(256) tb_walk_kernel(uint32_t p_begin, uint32_t n_pk /* pairs [p_begin, n_pk) of the plan */, const DeviceDb db, const uint64_t *key, const uint32_t *st,
                                                       const int32_t *sqs, const int32_t *sqe, const int32_t *sts, const int32_t *ste,
                                                       const int32_t *score, int open, int ext, int band,
                                                       int tab, const uint8_t *tbm, const unsigned long long *tboff, int32_t *pack,
-                                                      int32_t *gaps_out) {
+                                                      int32_t *gaps_out, uint32_t *bt_cnt, const uint32_t *bt_off, uint32_t *bt_runs,
+                                                      unsigned long long bt_base, unsigned long long *bt_pos, uint32_t *bt_plain, uint32_t *bt_err) {
     __shared__ int8_t s_S3[21 * 21], s_SA[21 * 21];
     for (int k = threadIdx.x; k < 21 * 21; k += 256) { s_S3[k] = db.S3[k]; s_SA[k] = db.SA[k]; }
     __syncthreads();
     for (uint32_t p = p_begin + blockIdx.x * 256 + threadIdx.x; p < n_pk; p += gridDim.x * 256) {
+        if (EMIT == 2 && bt_cnt[p] == 0) continue;                    // left its band: nothing to write, the pair is redone
         const int cls = (int)(key[p] >> 40);
         const uint32_t q = (uint32_t)(key[p] >> 16) & 0xFFFFFFu, t = st[p];
-        const int G = c_tab[tab].G[cls], R = c_tab[tab].R[cls], RB = 4 * ((R + 3) / 4);
+        const int G = PLAIN ? 1 : c_tab[tab].G[cls], R = PLAIN ? 1 : c_tab[tab].R[cls], RB = 4 * ((R + 3) / 4);
         const int qs = sqs[p], ts = sts[p];
-        const TbBand bd = tb_band_of(qs, sqe[p], ste[p] - ts + 1, G, R, band);
-        const bool full = bd.nl >= G;
+        const TbBand bd = PLAIN ? TbBand{1, 0, 0} : tb_band_of(qs, sqe[p], ste[p] - ts + 1, G, R, band);
+        const bool full = PLAIN || bd.nl >= G;
         const unsigned long long trow = (unsigned long long)(bd.nl * RB);
         bool miss = false;           // the walk asked for a cell outside the stored band: the pair is redone with the whole box stored
         const uint8_t *m = tbm + tboff[p];
+        const int32_t *m32 = (const int32_t *)m;                      // PLAIN: H(ii, jj) at (ii - qs) * pw + (jj - ts)
+        const size_t pw = (size_t)(ste[p] - ts + 1);
         const uint16_t *ql = db.lt + db.off[q], *tl = db.lt + db.off[t];   // 3Di | AA << 8 per residue
+        BtSink<EMIT> sink;
+        if (EMIT == 2) { sink.out = bt_runs + bt_off[p]; sink.w = (int)bt_cnt[p] - 1; }
         // full H of cell (ii, jj), a neighbour of a cell (or gap state) whose value is within 127 of it: ref
         auto H_at = [&](int ii, int jj, int ref) -> int {
             if (ii < qs || jj < ts) return 0;
+            if (PLAIN) return m32[(size_t)(ii - qs) * pw + (size_t)(jj - ts)];
             const int lane = ii / R, stp = jj - ts + lane;
             if (!full && (stp < lane * (R + 1) - bd.dhi || stp > lane * (R + 1) + R - 1 - bd.dlo)) { miss = true; return ref; }
             const uint32_t b = m[(unsigned long long)stp * trow + (unsigned long long)((lane % bd.nl) * RB + (ii - lane * R))];
             return ref + (int)(int8_t)(uint8_t)(b - (uint32_t)ref);
         };
         int i = sqe[p], j = ste[p], state = 0;
-        int h = score[p];            // state 0: H(i,j);  states 1 / 2: the value of the gap state the walk is in
+        int h = PLAIN ? m32[(size_t)(sqe[p] - qs) * pw + (size_t)(ste[p] - ts)] : score[p];   // state 0: H(i,j);  states 1 / 2: the value of the gap state the walk is in
         uint32_t len = 0, id = 0, gaps = 0, tie = 0;
         while (i >= qs && j >= ts && !miss) {
             if (state == 0) {
@@ -552,7 +586,8 @@ __global__ void __launch_bounds__(256) tb_walk_kernel(uint32_t p_begin, uint32_t
                     lqv[k] = in ? ql[ii] : 0u;
                     ltv[k] = in ? tl[jj] : 0u;
                     uint32_t b = 0x100u;
-                    if (in && ii - 1 >= qs && jj - 1 >= ts) {
+                    if (PLAIN) b = (in && ii - 1 >= qs && jj - 1 >= ts) ? (uint32_t)m32[(size_t)(ii - 1 - qs) * pw + (size_t)(jj - 1 - ts)] : 0u;   // H itself
+                    else if (in && ii - 1 >= qs && jj - 1 >= ts) {
                         const int lane = (ii - 1) / R, stp = jj - 1 - ts + lane;
                         if (!full && (stp < lane * (R + 1) - bd.dhi || stp > lane * (R + 1) + R - 1 - bd.dlo)) b = 0x200u;
                         else b = m[(unsigned long long)stp * trow + (unsigned long long)((lane % bd.nl) * RB + (ii - 1 - lane * R))];
@@ -565,10 +600,10 @@ __global__ void __launch_bounds__(256) tb_walk_kernel(uint32_t p_begin, uint32_t
                 for (int k = 0; k < SPEC; k++) {
                     if (off_diag || miss || i < qs || j < ts || h <= 0) continue;
                     lq = lqv[k]; lt = ltv[k];
-                    if (bv[k] == 0x200u) { miss = true; continue; }
-                    const int hd = bv[k] == 0x100u ? 0 : h + (int)(int8_t)(uint8_t)(bv[k] - (uint32_t)h);
+                    if (!PLAIN && bv[k] == 0x200u) { miss = true; continue; }
+                    const int hd = PLAIN ? (int)bv[k] : bv[k] == 0x100u ? 0 : h + (int)(int8_t)(uint8_t)(bv[k] - (uint32_t)h);
                     const int sc = (int)s_S3[(lq & 0xffu) * 21 + (lt & 0xffu)] + (int)s_SA[(lq >> 8) * 21 + (lt >> 8)];
-                    if (h == hd + sc) { len++; id += (lq >> 8) == (lt >> 8); i--; j--; h = hd; }
+                    if (h == hd + sc) { len++; id += (lq >> 8) == (lt >> 8); i--; j--; h = hd; if (EMIT) sink.step(BT_M); }
                     else off_diag = true;
                 }
                 if (!off_diag) continue;                                // the run ended on a diagonal step (or the walk is over): next run
@@ -594,6 +629,7 @@ __global__ void __launch_bounds__(256) tb_walk_kernel(uint32_t p_begin, uint32_t
                 gaps++;
             } else if (state == 1) {                                    // gap consuming query residue i, value h = F(i,j)
                 len++;
+                if (EMIT) sink.step(BT_I);
                 if (i - 1 < qs) state = 0;
                 else {
                     const int hu = H_at(i - 1, j, h);                   // F(i,j) = max(F(i-1,j) - ext, H(i-1,j) - open): ext .. open above h
@@ -602,6 +638,7 @@ __global__ void __launch_bounds__(256) tb_walk_kernel(uint32_t p_begin, uint32_t
                 i--;
             } else {                                                    // gap consuming target residue j, value h = E(i,j)
                 len++;
+                if (EMIT) sink.step(BT_D);
                 if (j - 1 < ts) state = 0;
                 else {
                     const int hl = H_at(i, j - 1, h);
@@ -610,6 +647,14 @@ __global__ void __launch_bounds__(256) tb_walk_kernel(uint32_t p_begin, uint32_t
                 j--;
             }
         }
+        if (EMIT) sink.flush();
+        if (EMIT == 2) {
+            if (sink.ovf || sink.w != -1) atomicOr(bt_err, 1u);
+            bt_pos[p] = bt_base + bt_off[p];
+            bt_plain[p] = PLAIN;
+            continue;                                                  // the statistics were written by the counting walk
+        }
+        if (EMIT == 1) bt_cnt[p] = miss ? 0u : sink.n;
         pack[p] = miss ? (int32_t)TB_BAND_MISS : (int32_t)((len << 16) | id | (tie << 31));
         if (gaps_out) gaps_out[p] = (int32_t)gaps;
     }
@@ -617,6 +662,78 @@ __global__ void __launch_bounds__(256) tb_walk_kernel(uint32_t p_begin, uint32_t
 // byte offset of the first matrix of every task of the traceback plan (the batches are cut at task boundaries)
 __global__ void __launch_bounds__(256) tb_taskoff_kernel(uint32_t ntasks, const SwTask *tasks, const unsigned long long *tboff, unsigned long long *out) {
     for (uint32_t k = blockIdx.x * 256 + threadIdx.x; k < ntasks; k += gridDim.x * 256) out[k] = tboff[tasks[k].begin];
+}
+// ---- the stored-matrix pass of the pairs the packed kernel does not serve (backtraces only) --------------------------------------
+// Scores beyond the packed range, queries beyond the systolic classes and the all-int32 configuration take their statistics from int32 MODE 3, which
+// carries them through the DP and stores nothing.  With -a those pairs need a path: a plain int32 DP of the box that keeps H of every cell, row-major,
+// and the walk above with that address function (PLAIN).  int32 per cell whatever the matrices and gap costs (no byte-difference argument needed).
+// One workgroup per pair, one anti-diagonal per barrier; E of the cell to the left lives per row, F of the cell above per column (each is touched by
+// exactly one thread per anti-diagonal).  Rare routes: simple, not fast.
+// bytes of pair p: 4 * (rows * cols + rows + cols), rounded up to 8
+__global__ void __launch_bounds__(256) tb_plain_size_kernel(uint32_t p_begin, uint32_t p_end, const int32_t *sqs, const int32_t *sqe, const int32_t *sts,
+                                                            const int32_t *ste, unsigned long long *size) {
+    for (uint32_t p = p_begin + blockIdx.x * 256 + threadIdx.x; p < p_end; p += gridDim.x * 256) {
+        const unsigned long long r = (unsigned long long)(sqe[p] - sqs[p] + 1), c = (unsigned long long)(ste[p] - sts[p] + 1);
+        size[p] = (4ull * (r * c + r + c) + 7ull) & ~7ull;
+    }
+}
+__global__ void __launch_bounds__(256) tb_plain_dp_kernel(uint32_t p_begin, uint32_t p_end, const DeviceDb db, const uint64_t *key, const uint32_t *st,
+                                                          const int32_t *sqs, const int32_t *sqe, const int32_t *sts, const int32_t *ste, int open, int ext,
+                                                          uint8_t *tbm, const unsigned long long *tboff) {
+    __shared__ int8_t s_S3[21 * 21], s_SA[21 * 21];
+    for (int k = threadIdx.x; k < 21 * 21; k += 256) { s_S3[k] = db.S3[k]; s_SA[k] = db.SA[k]; }
+    __syncthreads();
+    for (uint32_t p = p_begin + blockIdx.x; p < p_end; p += gridDim.x) {
+        const uint32_t q = (uint32_t)(key[p] >> 16) & 0xFFFFFFu, t = st[p];
+        const int nr = sqe[p] - sqs[p] + 1, nc = ste[p] - sts[p] + 1;
+        const uint16_t *ql = db.lt + db.off[q] + sqs[p], *tl = db.lt + db.off[t] + sts[p];
+        int32_t *H = (int32_t *)(tbm + tboff[p]);
+        int32_t *Er = H + (size_t)nr * (size_t)nc, *Fc = Er + nr;
+        constexpr int32_t NEG = -(1 << 28);
+        for (int k = threadIdx.x; k < nr + nc; k += 256) Er[k] = NEG;
+        __syncthreads();
+        for (int d = 0; d < nr + nc - 1; d++) {
+            const int lo = max(0, d - nc + 1), hi = min(nr - 1, d);
+            for (int i = lo + (int)threadIdx.x; i <= hi; i += 256) {
+                const int j = d - i;
+                const size_t at = (size_t)i * (size_t)nc + (size_t)j;
+                const int hl = j > 0 ? H[at - 1] : 0, hu = i > 0 ? H[at - (size_t)nc] : 0, hd = (i > 0 && j > 0) ? H[at - (size_t)nc - 1] : 0;
+                const uint32_t lq = ql[i], lt = tl[j];
+                const int sc = (int)s_S3[(lq & 0xffu) * 21 + (lt & 0xffu)] + (int)s_SA[(lq >> 8) * 21 + (lt >> 8)];
+                const int e = max(Er[i] - ext, hl - open), f = max(Fc[j] - ext, hu - open);
+                H[at] = max(max(0, hd + sc), max(e, f));
+                Er[i] = e; Fc[j] = f;
+            }
+            __syncthreads();
+        }
+    }
+}
+// the slices of the walked pairs of a traceback plan -> the per-record (position, runs) pair of the batch; a pair that left its band writes nothing
+constexpr uint32_t BT_SWAP = 0x80000000u, BT_PLAIN = 0x40000000u;    // marks in the per-record run count: I / D exchanged when read; served by the stored-matrix pass
+__global__ void __launch_bounds__(256) bt_apply_kernel(uint32_t n3, const uint32_t *idx3, const uint32_t *src3, const uint32_t *cnt, const unsigned long long *pos,
+                                                       const uint32_t *plain, const uint32_t *idx2, const uint32_t *link, const uint32_t *idx0,
+                                                       unsigned long long *rpos, uint32_t *rn) {
+    for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n3; i += gridDim.x * 256) {
+        if (!cnt[i]) continue;
+        const uint32_t o = idx0[link[idx2[src3[idx3[i]]]]];
+        rpos[o] = pos[i];
+        rn[o] = cnt[i] | (plain[i] ? BT_PLAIN : 0u);
+    }
+}
+// a mirror that took its representative's statistics (tbm_resolve_kernel) takes its slice too: the transposed path is the same runs with I and D exchanged
+__global__ void __launch_bounds__(256) bt_mirror_kernel(uint32_t n2, const uint32_t *partner, const uint32_t *tie, const uint32_t *link, const uint32_t *idx0,
+                                                        unsigned long long *rpos, uint32_t *rn) {
+    for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n2; i += gridDim.x * 256) {
+        const uint32_t pr = partner[i];
+        if (pr == 0xFFFFFFFFu || tie[pr]) continue;
+        const uint32_t om = idx0[link[i]], orp = idx0[link[pr]];
+        rpos[om] = rpos[orp];
+        rn[om] = rn[orp] ^ BT_SWAP;
+    }
+}
+__global__ void __launch_bounds__(256) bt_putback_kernel(uint32_t nc, const uint32_t *map, const unsigned long long *spos, const uint32_t *sn,
+                                                         unsigned long long *dpos, uint32_t *dn) {
+    for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < nc; i += gridDim.x * 256) { dpos[map[i]] = spos[i]; dn[map[i]] = sn[i]; }
 }
 // accepted pairs by forward score: the packed DP of MODE 7 is only valid below its score range
 __global__ void __launch_bounds__(256) tb_split_kernel(uint32_t n2, const uint32_t *flag, const uint32_t *link, const uint32_t *idx0,
@@ -942,6 +1059,9 @@ struct AlignScratch {
     bool tb_tbm_live = false;        // inside the batch loop of a MODE 7 call: the one time the matrices may not be given back (release_tb_matrices)
     DevBuf<int32_t> tb_qs3, tb_qe3, tb_ts3, tb_te3, tb_pack3, tb_gaps3, tb_sc3;
     SwPlan tb_P3;
+    // backtraces (-a): runs per pair of the traceback plan, slice offsets inside a matrix batch, where each slice went, which kernel walked it
+    DevBuf<uint32_t> bt_cnt3, bt_off3, bt_plain3, bt_err, lg_btn;
+    DevBuf<unsigned long long> bt_pos3, lg_btpos;
     // set-cover graph build + greedy cover (set_cover_graph)
     DevBuf<uint32_t> sc_e, sc_flag, sc_pos, sc_dadj, sc_bad, sc_assign, sc_cnt, sc_work, sc_work2, sc_picks, sc_newly, sc_ctr;
     DevBuf<uint64_t> sc_m1;
@@ -1083,6 +1203,9 @@ struct AlignBatch {
     // the directed pair list the gates work on: sorted (query, target) + position in the hit list
     const uint32_t *Lsq = nullptr, *Lst = nullptr, *Lidx = nullptr;
     uint32_t n2 = 0;                  // pairs that passed the E-value gate
+    // backtraces (-a): slice position and run count per record, indexed like alns_b (null: not emitted)
+    unsigned long long *bt_pos_b = nullptr;
+    uint32_t *bt_n_b = nullptr;
 };
 
 // rule UC-1/L (optional): the stage works on the pairs the length gate lets through - a compacted copy of the batch's pair list with its own
@@ -1099,6 +1222,12 @@ static void length_gate(Engine &E, AlignBatch &B) {
     hipLaunchKernelGGL(len_gate_gather_kernel, grid_for(n), dim3(256), 0, s, n, A.lg_flag.p, A.lg_pos.p, B.dq, B.dt, A.lg_q.p, A.lg_t.p, A.lg_map.p);
     if (nc) UC_HIP(hipMemsetAsync(A.lg_alns.p, 0, (size_t)nc * sizeof(uc_aln), s));
     UC_HIP(hipMemsetAsync(B.alns_list, 0, (size_t)n * sizeof(uc_aln), s));
+    if (B.bt_pos_b) {
+        A.lg_btpos.reserve(std::max<uint32_t>(nc, 1)); A.lg_btn.reserve(std::max<uint32_t>(nc, 1));
+        UC_HIP(hipMemsetAsync(A.lg_btn.p, 0, (size_t)std::max<uint32_t>(nc, 1) * 4, s));
+        UC_HIP(hipMemsetAsync(B.bt_n_b, 0, (size_t)n * 4, s));
+        B.bt_pos_b = A.lg_btpos.p; B.bt_n_b = A.lg_btn.p;
+    }
     B.dq = A.lg_q.p; B.dt = A.lg_t.p; B.alns_b = A.lg_alns.p; B.n = nc;
 }
 
@@ -1256,6 +1385,90 @@ static bool tb_bytes_ok(const Params &p) {
 
 constexpr uint32_t TB_GAPS[4] = {0u, 0u, 1u, 0u};   // MODE 3 weights (diagonal, identity, open, extension) of the gap count
 
+// the walk over the matrices of pairs [p0, p1) of the plan tb_P3 that are resident now.  Without -a: the statistics walk.  With -a (E.emit_bt):
+// count (statistics + runs per pair), scan, make room in the engine's run buffer for exactly that many, write.
+template <int PLAIN>
+static void tb_walk(Engine &E, uint32_t p0, uint32_t p1, int band, const uint8_t *tbm, const unsigned long long *tboff) {
+    AlignScratch &A = scratch_of(E);
+    SwPlan &P3 = A.tb_P3;
+    hipStream_t s = E.stream;
+    if (p1 <= p0) return;
+    const dim3 grid = grid_for(p1 - p0);
+#define UC_TB_WALK(EMIT, base)                                                                                                                   \
+    hipLaunchKernelGGL((tb_walk_kernel<EMIT, PLAIN>), grid, dim3(256), 0, s, p0, p1, E.ddb, P3.key2.p, P3.st.p, P3.sqs.p, P3.sqe.p, P3.sts.p, P3.ste.p,  \
+                       P3.saux.p, E.p.gap_open, E.p.gap_ext, band, 1, tbm, tboff, A.tb_pack3.p, A.tb_gaps3.p, A.bt_cnt3.p, A.bt_off3.p,              \
+                       E.d_bt_runs.p + (base), (unsigned long long)(base), A.bt_pos3.p, A.bt_plain3.p, A.bt_err.p)
+    if (!E.emit_bt) {
+        if constexpr (PLAIN == 0) UC_TB_WALK(0, 0);
+        else fail(UC_ERR_GENERIC, "the stored-matrix pass runs for backtraces only");
+        return;
+    }
+    UC_TB_WALK(1, 0);
+    const size_t k = p1 - p0;
+    size_t tb = 0;
+    UC_HIP(rocprim::exclusive_scan(nullptr, tb, A.bt_cnt3.p + p0, A.bt_off3.p + p0, 0u, k, rocprim::plus<uint32_t>(), s));
+    A.tmp.reserve(tb + 256);
+    UC_HIP(rocprim::exclusive_scan(A.tmp.p, tb, A.bt_cnt3.p + p0, A.bt_off3.p + p0, 0u, k, rocprim::plus<uint32_t>(), s));
+    uint32_t lo = 0, lc = 0;
+    UC_HIP(hipMemcpyAsync(&lo, A.bt_off3.p + (p1 - 1), 4, hipMemcpyDeviceToHost, s));
+    UC_HIP(hipMemcpyAsync(&lc, A.bt_cnt3.p + (p1 - 1), 4, hipMemcpyDeviceToHost, s));
+    UC_HIP(hipStreamSynchronize(s));
+    const uint64_t total = (uint64_t)lo + lc;
+    if (total >= (1ull << 31)) fail(UC_ERR_GENERIC, "backtraces: %llu runs in one matrix batch", (unsigned long long)total);
+    if (!total) return;
+    E.d_bt_runs.grow_preserve(E.bt_used + total, E.bt_used, s);
+    UC_TB_WALK(2, E.bt_used);
+    E.bt_used += total;
+#undef UC_TB_WALK
+}
+
+// -a, the pairs [p0, p1) of the plan tb_P3 that the packed kernel does not serve: plain int32 H matrices (tb_plain_dp_kernel) in batches of the same
+// budget as the byte matrices, in pair order; a single pair always runs.  Returns the launches.
+static uint64_t tb_run_plain(Engine &E, uint32_t p0, uint32_t p1, const TbBudget &budget) {
+    AlignScratch &A = scratch_of(E);
+    SwPlan &P3 = A.tb_P3;
+    hipStream_t s = E.stream;
+    if (p1 <= p0) return 0;
+    const size_t k = p1 - p0;
+    A.tb_tbsize.reserve((size_t)P3.n + 1); A.tb_tboff.reserve((size_t)P3.n + 1);
+    hipLaunchKernelGGL(tb_plain_size_kernel, grid_for(k), dim3(256), 0, s, p0, p1, P3.sqs.p, P3.sqe.p, P3.sts.p, P3.ste.p, A.tb_tbsize.p);
+    std::vector<unsigned long long> h_size(k);
+    UC_HIP(hipMemcpyAsync(h_size.data(), A.tb_tbsize.p + p0, k * 8, hipMemcpyDeviceToHost, s));
+    UC_HIP(hipStreamSynchronize(s));
+    std::vector<unsigned long long> h_off(k + 1, 0);
+    for (size_t i = 0; i < k; i++) h_off[i + 1] = h_off[i] + h_size[i];
+    UC_HIP(hipMemcpyAsync(A.tb_tboff.p + p0, h_off.data(), k * 8, hipMemcpyHostToDevice, s));
+    const unsigned long long batch_bytes = budget.batch_bytes(h_off[k], A.tb_tbm.cap);
+    A.tb_tbm_live = true;
+    struct Live { bool &f; ~Live() { f = false; } } live{A.tb_tbm_live};
+    std::vector<std::pair<size_t, size_t>> batches;
+    unsigned long long max_bytes = 0;
+    for (size_t a = 0; a < k;) {
+        size_t b = a + 1;
+        while (b < k && h_off[b + 1] - h_off[a] <= batch_bytes) b++;
+        batches.emplace_back(a, b);
+        max_bytes = std::max(max_bytes, h_off[b] - h_off[a]);
+        a = b;
+    }
+    A.tb_tbm.reserve_exact(max_bytes + 64);
+    uint64_t launches = 0;
+    double ms = 0;
+    for (const auto &bt : batches) {
+        const uint32_t a = p0 + (uint32_t)bt.first, b = p0 + (uint32_t)bt.second;
+        uint8_t *base = A.tb_tbm.p - h_off[bt.first];                 // (a pair's offset counts from the first pair of the range)
+        E.timed_ms_begin();
+        hipLaunchKernelGGL(tb_plain_dp_kernel, dim3(std::min<uint32_t>(b - a, 4096u)), dim3(256), 0, s, a, b, E.ddb, P3.key2.p, P3.st.p, P3.sqs.p, P3.sqe.p,
+                           P3.sts.p, P3.ste.p, E.p.gap_open, E.p.gap_ext, base, A.tb_tboff.p);
+        tb_walk<1>(E, a, b, 0, base, A.tb_tboff.p);
+        ms += E.timed_ms_end();
+        launches += 3;
+    }
+    E.stats.sw_kernel_ms += ms;
+    if (getenv("UC_TIMING")) fprintf(stderr, "unicore-cluster[timing]: sw pass stored int32 matrices: %zu pairs, %.2f ms, %llu matrix bytes, %zu batch(es)\n",
+                                     k, ms, h_off[k], batches.size());
+    return launches;
+}
+
 // packed MODE 7 for the plan tb_P3 (built in pair order): H bytes of the box's diagonal band (tb_band_of) + walk kernel; queries beyond the
 // systolic classes take int32 MODE 3.  Returns the launches.
 //
@@ -1273,7 +1486,8 @@ static uint64_t tb_run_bytes(Engine &E, int band, const TbBudget &budget) {
     double tb_ms = 0;
     unsigned long long total = 0;
     uint32_t nbatch = 0;
-    if (P3.n > n_pk3) {                                   // long queries: int32 MODE 3 (no matrices)
+    if (P3.n > n_pk3 && E.emit_bt) launches += tb_run_plain(E, n_pk3, P3.n, budget);   // -a: long queries need a stored matrix
+    else if (P3.n > n_pk3) {                              // long queries: int32 MODE 3 (no matrices)
         E.timed_ms_begin();
         launches += launch_plan(E, P3, 7, A.tb_pack3.p, nullptr, nullptr, A.work, nullptr, /*only_long=*/true);
         if (E.p.want_tb) launches += launch_plan(E, P3, 3, A.tb_gaps3.p, nullptr, nullptr, A.work, TB_GAPS, /*only_long=*/true);
@@ -1324,8 +1538,7 @@ static uint64_t tb_run_bytes(Engine &E, int band, const TbBudget &budget) {
             P3.tbm = tbm.p - base; P3.tboff = tboff.p; P3.tb_band = band;      // (a pair's offset counts from the start of the WHOLE plan)
             E.timed_ms_begin();
             launches += launch_plan(E, P3, 7, A.tb_pack3.p, nullptr, nullptr, A.work, nullptr, false, t0, t1, /*skip_long=*/true);
-            hipLaunchKernelGGL(tb_walk_kernel, grid_for(p1 - p0), dim3(256), 0, s, p0, p1, E.ddb, P3.key2.p, P3.st.p, P3.sqs.p, P3.sqe.p,
-                               P3.sts.p, P3.ste.p, P3.saux.p, E.p.gap_open, E.p.gap_ext, band, 1, tbm.p - base, tboff.p, A.tb_pack3.p, A.tb_gaps3.p);
+            tb_walk<0>(E, p0, p1, band, tbm.p - base, tboff.p);
             tb_ms += E.timed_ms_end();
             nbatch++;
         }
@@ -1353,7 +1566,15 @@ static void tb_batch(Engine &E, const AlignBatch &B, const uint32_t *flag, bool 
     SwPlan &P3 = A.tb_P3;
     uint64_t launches = 0;
     int passes = 1;
-    if (!pk) {
+    if (E.emit_bt) {
+        A.bt_cnt3.reserve(nt); A.bt_off3.reserve(nt); A.bt_plain3.reserve(nt); A.bt_pos3.reserve(nt); A.bt_err.reserve(1);
+        UC_HIP(hipMemsetAsync(A.bt_cnt3.p, 0, (size_t)nt * 4, s));
+        UC_HIP(hipMemsetAsync(A.bt_err.p, 0, 4, s));
+    }
+    if (!pk && E.emit_bt) {   // -a: MODE 3 has no path to give; every pair takes the stored int32 matrix and the walk
+        build_plan(E, P3, A.tmp, nt, A.tb_q3.p, A.tb_t3.p, A.tb_qe3.p, A.tb_te3.p, 1, A.tb_qs3.p, A.tb_ts3.p, A.tb_sc3.p, /*lpt=*/false);
+        launches = tb_run_plain(E, 0, P3.n, budget);
+    } else if (!pk) {
         build_plan(E, P3, A.tmp, nt, A.tb_q3.p, A.tb_t3.p, A.tb_qe3.p, A.tb_te3.p, 2, A.tb_qs3.p, A.tb_ts3.p);
         E.timed_ms_begin();
         launches = launch_plan(E, P3, 3, A.tb_pack3.p, nullptr, nullptr, A.work);
@@ -1373,6 +1594,15 @@ static void tb_batch(Engine &E, const AlignBatch &B, const uint32_t *flag, bool 
     hipLaunchKernelGGL(tb_apply_kernel, grid_for(nt), dim3(256), 0, s, nt, P3.idx.p, A.tb_src3.p, A.tb_pack3.p,
                        E.p.want_tb ? A.tb_gaps3.p : (const int32_t *)nullptr, A.iota2.p, A.link.p, B.Lidx, E.p.min_seq_id, B.alns_b,
                        A.eflag.p, A.tb_ttie.p, (pk && band > 0) ? A.tb_tmiss.p : (uint32_t *)nullptr);
+    if (E.emit_bt) {
+        if (!B.bt_pos_b) fail(UC_ERR_GENERIC, "backtraces: the batch has no place for them");
+        hipLaunchKernelGGL(bt_apply_kernel, grid_for(nt), dim3(256), 0, s, nt, P3.idx.p, A.tb_src3.p, A.bt_cnt3.p, A.bt_pos3.p, A.bt_plain3.p,
+                           A.iota2.p, A.link.p, B.Lidx, B.bt_pos_b, B.bt_n_b);
+        uint32_t err = 0;
+        UC_HIP(hipMemcpyAsync(&err, A.bt_err.p, 4, hipMemcpyDeviceToHost, s));
+        UC_HIP(hipStreamSynchronize(s));
+        if (err) fail(UC_ERR_GENERIC, "backtraces: a path did not fit the slice its own count had sized");
+    }
 }
 
 // packed MODE 7 for the flagged pairs, in segments of budget.segment_pairs() pairs (TbBudget)
@@ -1431,13 +1661,64 @@ static bool sw_pass_allowed(int tab, int mode) {
     }
 }
 
-void Engine::sw_pass(int tab, int mode, int band, bool raw, const std::vector<SwPassPair> &pairs, const SwPassOut &o) {
+// slices of records (pos, n) cut from the host copy `hruns` of the run buffer from element `base` on; bit 31 of n exchanges I and D
+static void bt_assemble(size_t n, const unsigned long long *pos, const uint32_t *cnt, const uc_aln *alns /* null: every record counts */,
+                        const uint32_t *hruns, uint64_t base, uint64_t *run_off, std::vector<uint32_t> &runs) {
+    runs.clear();
+    for (size_t i = 0; i < n; i++) {
+        run_off[i] = runs.size();
+        if (alns && !alns[i].accepted) continue;
+        const uint32_t k = cnt[i] & 0x3FFFFFFFu;
+        const bool swap = (cnt[i] >> 31) != 0;
+        const uint32_t *r = k ? hruns + (pos[i] - base) : nullptr;
+        for (uint32_t x = 0; x < k; x++) {
+            uint32_t v = r[x];
+            if (swap && (v & 3u)) v ^= 3u;                 // I (1) <-> D (2)
+            runs.push_back(v);
+        }
+    }
+    run_off[n] = runs.size();
+}
+
+void Engine::get_backtraces(uint64_t begin, uint64_t n, uint64_t *run_off, std::vector<uint32_t> &runs) const {
+    runs.clear();
+    if (!n) { run_off[0] = 0; return; }
+    if (!emit_bt || !alns_valid || !d_bt_n.p) fail(UC_ERR_ARGS, "backtraces: this engine has not aligned with -a");
+    UC_HIP(hipSetDevice(device));
+    std::vector<unsigned long long> pos(n);
+    std::vector<uint32_t> cnt(n), hr(std::max<uint64_t>(bt_used, 1));
+    std::vector<uc_aln> al(n);
+    UC_HIP(hipMemcpy(pos.data(), d_bt_pos.p + begin, n * 8, hipMemcpyDeviceToHost));
+    UC_HIP(hipMemcpy(cnt.data(), d_bt_n.p + begin, n * 4, hipMemcpyDeviceToHost));
+    UC_HIP(hipMemcpy(al.data(), d_alns.p + begin, n * sizeof(uc_aln), hipMemcpyDeviceToHost));
+    if (bt_used) UC_HIP(hipMemcpy(hr.data(), d_bt_runs.p, bt_used * 4, hipMemcpyDeviceToHost));
+    for (uint64_t i = 0; i < n; i++)
+        if (al[i].accepted && ((cnt[i] & 0x3FFFFFFFu) == 0 || pos[i] + (cnt[i] & 0x3FFFFFFFu) > bt_used))
+            fail(UC_ERR_GENERIC, "backtraces: accepted hit %llu has no path", (unsigned long long)(begin + i));
+    bt_assemble(n, pos.data(), cnt.data(), al.data(), hr.data(), 0, run_off, runs);
+}
+
+void Engine::tb_emit_pass(int route, int band, const std::vector<SwPassPair> &pairs, const SwPassOut &o, BtPassOut &bt) {
+    if (route < 0 || route > 3) fail(UC_ERR_ARGS, "tb_emit_pass: route must be 0..3");
+    if (!have_db) fail(UC_ERR_ARGS, "no database loaded");
+    const uint32_t sys_cap = (uint32_t)h_tab[1].cap[h_tab[1].n - 1];
+    for (const SwPassPair &x : pairs) {
+        if (x.q >= hdb.n) fail(UC_ERR_ARGS, "tb_emit_pass: sequence id out of range");
+        if (route == 3 && h_len[x.q] <= sys_cap) fail(UC_ERR_ARGS, "tb_emit_pass: the long-query route takes queries of more than %u residues", sys_cap);
+        if (route <= 1 && h_len[x.q] > sys_cap) fail(UC_ERR_ARGS, "tb_emit_pass: the packed route takes queries of up to %u residues", sys_cap);
+    }
+    if (route == 2) sw_pass(2, 3, 0, true, pairs, o, &bt);
+    else sw_pass(1, 7, route == 1 ? 0 : band, true, pairs, o, &bt);
+}
+
+void Engine::sw_pass(int tab, int mode, int band, bool raw, const std::vector<SwPassPair> &pairs, const SwPassOut &o, BtPassOut *bt) {
     PressureScope ps(*this, 1);
     if (!have_db) fail(UC_ERR_ARGS, "no database loaded");
     if (!sw_pass_allowed(tab, mode)) fail(UC_ERR_ARGS, "sw_pass: no such (table, mode)");
     if (mode == 7 && (!tb_bytes_ok(p) || !p.sw_pk)) fail(UC_ERR_ARGS, "sw_pass: MODE 7 needs the byte walk's score range and the packed kernel");
     if (band < 0) fail(UC_ERR_ARGS, "sw_pass: negative band");
     const size_t n = pairs.size();
+    if (bt) { bt->run_off.assign(n + 1, 0); bt->runs.clear(); bt->plain.assign(n, 0); }
     if (n == 0) return;
     if (n >= (1ull << 31)) fail(UC_ERR_ARGS, "sw_pass: too many pairs");
     const bool ends = mode == 2 || mode == 6, box = mode == 3 || mode == 7, known = mode == 4 || mode == 6 || mode == 7;
@@ -1504,6 +1785,16 @@ void Engine::sw_pass(int tab, int mode, int band, bool raw, const std::vector<Sw
     AlignBatch B{};
     B.n = nn; B.n2 = nn; B.dq = dq.p; B.dt = dt.p; B.alns_b = recs.p; B.alns_list = recs.p; B.tab = tab; B.Lidx = iota.p;
     struct Keep { Params &p; Params saved; ~Keep() { p = saved; } } keep{p, p};
+    // with emission: the slices go behind whatever the engine's run buffer holds and are given back at the end; the per-record arrays are the pass's own
+    struct KeepBt { Engine &E; bool emit; uint64_t used; ~KeepBt() { E.emit_bt = emit; E.bt_used = used; } } keep_bt{*this, emit_bt, bt_used};
+    DevBuf<unsigned long long> bpos;
+    DevBuf<uint32_t> bn;
+    emit_bt = bt != nullptr;
+    if (bt) {
+        bpos.reserve(n); bn.reserve(n);
+        UC_HIP(hipMemsetAsync(bn.p, 0, n * 4, stream));
+        B.bt_pos_b = bpos.p; B.bt_n_b = bn.p;
+    }
     p.want_tb = 1;         // both statistics: (alignment length, identities) and the gap count (the TB_GAPS weighting of MODE 3)
     p.min_seq_id = 0.0f;   // no gate on the result
     const TbBudget budget;
@@ -1517,6 +1808,15 @@ void Engine::sw_pass(int tab, int mode, int band, bool raw, const std::vector<Sw
     UC_HIP(hipStreamSynchronize(stream));
     UC_HIP(hipGetLastError());
     if (o.miss && (mode != 7 || band == 0)) memset(o.miss, 0, n * 4);
+    if (bt) {
+        std::vector<unsigned long long> pos(n);
+        std::vector<uint32_t> cnt(n), hr(std::max<uint64_t>(bt_used - keep_bt.used, 1));
+        UC_HIP(hipMemcpy(pos.data(), bpos.p, n * 8, hipMemcpyDeviceToHost));
+        UC_HIP(hipMemcpy(cnt.data(), bn.p, n * 4, hipMemcpyDeviceToHost));
+        if (bt_used > keep_bt.used) UC_HIP(hipMemcpy(hr.data(), d_bt_runs.p + keep_bt.used, (bt_used - keep_bt.used) * 4, hipMemcpyDeviceToHost));
+        bt_assemble(n, pos.data(), cnt.data(), nullptr, hr.data(), keep_bt.used, bt->run_off.data(), bt->runs);
+        for (size_t i = 0; i < n; i++) bt->plain[i] = (cnt[i] >> 30) & 1;
+    }
     for (size_t i = 0; i < n; i++) {
         if (o.score) o.score[i] = h[i].score;
         if (o.aln_len) o.aln_len[i] = h[i].aln_len;
@@ -1561,6 +1861,7 @@ static void traceback_stats(Engine &E, const AlignBatch &B) {
         run_tb(E, B, A.tb_trun.p, band_w, budget);
         hipLaunchKernelGGL(tbm_resolve_kernel, grid_for(n2), dim3(256), 0, s, n2, A.tb_tpart.p, A.tb_ttie.p, A.link.p, B.Lidx, E.p.min_seq_id,
                            B.alns_b, A.eflag.p, A.tb_trun.p);
+        if (E.emit_bt) hipLaunchKernelGGL(bt_mirror_kernel, grid_for(n2), dim3(256), 0, s, n2, A.tb_tpart.p, A.tb_ttie.p, A.link.p, B.Lidx, B.bt_pos_b, B.bt_n_b);
         run_tb(E, B, A.tb_trun.p, band_w, budget);   // mirrors whose representative had a gap-direction tie on its traceback
     } else {
         UC_HIP(hipMemcpyAsync(A.tb_trun.p, A.eflag.p, (size_t)n2 * 4, hipMemcpyDeviceToDevice, s));
@@ -1598,6 +1899,7 @@ static void finish_batch(Engine &E, const AlignBatch &B) {
     E.stats.n_start_alignments += B.n2;
     if (B.alns_b != B.alns_list) {
         hipLaunchKernelGGL(len_gate_putback_kernel, grid_for(B.n), dim3(256), 0, s, B.n, A.lg_map.p, (const uc_aln *)B.alns_b, B.alns_list);
+        if (B.bt_pos_b) hipLaunchKernelGGL(bt_putback_kernel, grid_for(B.n), dim3(256), 0, s, B.n, A.lg_map.p, A.lg_btpos.p, A.lg_btn.p, E.d_bt_pos.p + E.hit_off[B.qa], E.d_bt_n.p + E.hit_off[B.qa]);
         UC_HIP(hipStreamSynchronize(s));
     }
 }
@@ -1614,6 +1916,14 @@ void Engine::align(uint32_t qbegin, uint32_t qend) {
     // list: the array is cleared whenever the hit lists changed since the last align (0.2 ms at 14 M records)
     d_alns.reserve(std::max<uint64_t>(n_hits, 1));
     if (!alns_valid && n_hits) UC_HIP(hipMemsetAsync(d_alns.p, 0, n_hits * sizeof(uc_aln), s));
+    if (emit_bt) {   // -a: slice position and run count per hit, parallel to d_alns; the runs of earlier calls on these hit lists stay
+        if (!alns_valid) { bt_used = 0; d_bt_pos.release(); d_bt_n.release(); }
+        if (!d_bt_n.p) {
+            d_bt_pos.reserve(std::max<uint64_t>(n_hits, 1)); d_bt_n.reserve(std::max<uint64_t>(n_hits, 1));
+            UC_HIP(hipMemsetAsync(d_bt_n.p, 0, std::max<uint64_t>(n_hits, 1) * 4, s));
+        }
+        if (hit_off[qend] > hit_off[qbegin]) UC_HIP(hipMemsetAsync(d_bt_n.p + hit_off[qbegin], 0, (hit_off[qend] - hit_off[qbegin]) * 4, s));
+    }
     // E-value gate as an integer threshold per query length (host; exp() evaluated once per distinct length)
     std::vector<int32_t> ms_by_len(65536, -1), h_ms(qend - qbegin);
     if (!p.min_score_table.empty() && p.min_score_table.size() != hdb.n)
@@ -1637,6 +1947,7 @@ void Engine::align(uint32_t qbegin, uint32_t qend) {
         while (qb < qend && (qb == qa || hit_off[qb + 1] - hit_off[qa] <= CHUNK)) qb++;
         const uint64_t b = hit_off[qa];
         AlignBatch B{qbegin, qa, qb, (uint32_t)(hit_off[qb] - b), d_hq.p + b, d_ht.p + b, d_alns.p + b, d_alns.p + b, false, p.sw_pk ? 1 : 0};
+        if (emit_bt) { B.bt_pos_b = d_bt_pos.p + b; B.bt_n_b = d_bt_n.p + b; }
         qa = qb;
         if (p.len_gate && p.cov > 0.0f && B.n) length_gate(*this, B);
         if (!B.n) continue;

@@ -190,8 +190,10 @@ int uc_engine_create(const uc_opts *o, uc_engine **out) {
         require(out, "out");
         *out = nullptr;
         Params p = params_from(o);
+        if (p.want_bt) p.want_tb = 1;
         auto h = std::make_unique<uc_engine>();
         h->e = std::make_unique<Engine>(p, o ? o->device : -1);
+        h->e->emit_bt = p.want_bt != 0;      // the staged API reads them back (uc_engine_backtraces_get)
         *out = h.release();
     });
 }
@@ -328,6 +330,77 @@ int uc_engine_alns_get(const uc_engine *e, uint32_t qbegin, uint32_t qend, uc_al
         if (qbegin > qend || qend > E.hdb.n) fail(UC_ERR_ARGS, "alns_get: bad query range");
         const uint64_t b = E.hit_off[qbegin], n = E.hit_off[qend] - b;
         if (n) { require(out, "out"); E.get_alns(b, n, out); }
+    });
+}
+
+static void backtraces_of(const uc_engine *e, uint32_t qbegin, uint32_t qend, std::vector<uint64_t> &off, std::vector<uint32_t> &runs) {
+    require(e, "engine");
+    const Engine &E = *e->e;
+    if (!E.have_db) fail(UC_ERR_ARGS, "backtraces: no database loaded");
+    if (qbegin > qend || qend > E.hdb.n) fail(UC_ERR_ARGS, "backtraces: bad query range");
+    const uint64_t b = E.hit_off[qbegin], n = E.hit_off[qend] - b;
+    off.assign(n + 1, 0);
+    E.get_backtraces(b, n, off.data(), runs);
+}
+
+int uc_engine_backtraces_size(const uc_engine *e, uint32_t qbegin, uint32_t qend, uint64_t *n_runs) {
+    return guard([&] {
+        require(n_runs, "n_runs");
+        std::vector<uint64_t> off;
+        std::vector<uint32_t> runs;
+        backtraces_of(e, qbegin, qend, off, runs);
+        *n_runs = runs.size();
+    });
+}
+
+int uc_engine_backtraces_get(const uc_engine *e, uint32_t qbegin, uint32_t qend, uint64_t *run_off, uint32_t *runs_out) {
+    return guard([&] {
+        require(run_off, "run_off");
+        std::vector<uint64_t> off;
+        std::vector<uint32_t> runs;
+        backtraces_of(e, qbegin, qend, off, runs);
+        memcpy(run_off, off.data(), off.size() * 8);
+        if (!runs.empty()) { require(runs_out, "runs"); memcpy(runs_out, runs.data(), runs.size() * 4); }
+    });
+}
+
+int uc_backtrace_render(const uint32_t *runs, uint64_t n_runs, char *out, uint64_t out_capacity, uint64_t *len_out) {
+    return guard([&] {
+        if (n_runs) require(runs, "runs");
+        const std::string s = render_backtrace(runs, n_runs);
+        if (len_out) *len_out = s.size();
+        if (s.size() + 1 > out_capacity) fail(UC_ERR_ARGS, "uc_backtrace_render: %zu characters do not fit a buffer of %llu", s.size() + 1, (unsigned long long)out_capacity);
+        require(out, "out");
+        memcpy(out, s.c_str(), s.size() + 1);
+    });
+}
+
+int uc_format_output_check(const char *list, uint32_t *n_columns) {
+    return guard([&] {
+        const std::vector<std::string> c = parse_format_output(list ? list : "");
+        if (n_columns) *n_columns = (uint32_t)c.size();
+    });
+}
+
+int uc_engine_tb_emit_pass(uc_engine *e, int route, int band, uint64_t n, const uint32_t *q, const uint32_t *t, const int32_t *box, const int32_t *known,
+                           int32_t *class_out, int32_t *aln_len_out, int32_t *idents_out, int32_t *gaps_out, int32_t *miss_out, int32_t *plain_out,
+                           uint64_t *run_off, uint32_t *runs, uint64_t runs_capacity, uint64_t *n_runs) {
+    return guard([&] {
+        require(e, "engine"); require(run_off, "run_off");
+        if (n_runs) *n_runs = 0;
+        run_off[0] = 0;
+        if (!n) return;
+        require(q, "q"); require(t, "t"); require(box, "box");
+        if (route != 2) require(known, "known");
+        std::vector<SwPassPair> pairs(n);
+        for (uint64_t i = 0; i < n; i++) pairs[i] = {q[i], t[i], box[4 * i], box[4 * i + 1], box[4 * i + 2], box[4 * i + 3], known ? known[i] : 0};
+        BtPassOut bt;
+        e->e->tb_emit_pass(route, band, pairs, {nullptr, nullptr, nullptr, class_out, aln_len_out, idents_out, gaps_out, miss_out}, bt);
+        if (n_runs) *n_runs = bt.runs.size();
+        if (bt.runs.size() > runs_capacity) fail(UC_ERR_ARGS, "tb_emit_pass: %zu runs, room for %llu", bt.runs.size(), (unsigned long long)runs_capacity);
+        memcpy(run_off, bt.run_off.data(), (n + 1) * 8);
+        if (!bt.runs.empty()) { require(runs, "runs"); memcpy(runs, bt.runs.data(), bt.runs.size() * 4); }
+        if (plain_out) memcpy(plain_out, bt.plain.data(), n * 4);
     });
 }
 
@@ -785,6 +858,7 @@ int uc_search(const char *query_db, const char *target_db, const char *out_aln_d
         p.want_tb = 1;
         if (tmp && *tmp) mkdir_p(tmp);
         Engine E(p, o ? o->device : -1);
+        E.emit_bt = p.want_bt != 0;
         Timer tl;
         HostDb T, Q;
         read_seq_db(target_db, T, false);
@@ -819,6 +893,12 @@ int uc_search(const char *query_db, const char *target_db, const char *out_aln_d
         std::vector<uc_hit> hits(std::max<uint64_t>(E.n_hits, 1));
         std::vector<uc_aln> alns(std::max<uint64_t>(E.n_hits, 1));
         if (E.n_hits) { E.get_hits(hits.data()); E.get_alns(0, E.n_hits, alns.data()); }
+        std::vector<uint64_t> bt_off(E.n_hits + 1, 0);
+        std::vector<uint32_t> bt_runs;
+        if (p.want_bt && E.n_hits) {
+            E.get_backtraces(0, E.n_hits, bt_off.data(), bt_runs);
+            logf(3, "unicore-search: backtraces: %llu runs in a device buffer of %llu (%.1f MB)\n", (unsigned long long)bt_runs.size(), (unsigned long long)E.bt_used, E.bt_used * 4 / 1e6);
+        }
         std::vector<std::vector<AlnRow>> rows(nq);
         uint64_t n_acc = 0;
         for (uint32_t q = 0; q < nq; q++) {
@@ -837,7 +917,8 @@ int uc_search(const char *query_db, const char *target_db, const char *out_aln_d
                 r.fident = a.aln_len > 0 ? (double)a.idents / (double)a.aln_len : 0.0;
                 r.qstart = a.qstart; r.qend = a.qend; r.qlen = lq; r.tstart = a.tstart; r.tend = a.tend; r.tlen = (int32_t)T.len(t);
                 r.aln_len = a.aln_len; r.idents = a.idents; r.gap_opens = a.gap_opens;
-                rv.push_back(r);
+                if (p.want_bt) r.bt = render_backtrace(bt_runs.data() + bt_off[k], bt_off[k + 1] - bt_off[k]);
+                rv.push_back(std::move(r));
             }
             std::sort(rv.begin(), rv.end(), [](const AlnRow &x, const AlnRow &y) { return x.corrected != y.corrected ? x.corrected > y.corrected : x.tkey < y.tkey; });
             n_acc += rv.size();
@@ -854,7 +935,9 @@ int uc_convertalis(const char *query_db, const char *target_db, const char *aln_
     return guard([&] {
         require(query_db, "query_db"); require(target_db, "target_db"); require(aln_db, "aln_db"); require(out_m8, "out_m8");
         if (o) g_verbosity = o->verbosity;
-        convert_alis(query_db, target_db, aln_db, out_m8);
+        Params p;
+        if (o && o->cluster_options) parse_cluster_options(o->cluster_options, p);
+        convert_alis(query_db, target_db, aln_db, out_m8, p.format_output);
     });
 }
 

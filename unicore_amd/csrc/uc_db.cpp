@@ -257,6 +257,7 @@ void write_aln_db(const std::string &prefix, const std::vector<uint64_t> &qkeys,
                 const int k = snprintf(buf, sizeof buf, "%llu\t%d\t%.3f\t%.3E\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\n", (unsigned long long)r.tkey, r.bits,
                                        r.fident, r.evalue, r.qstart, r.qend, r.qlen, r.tstart, r.tend, r.tlen, r.aln_len, r.idents, r.gap_opens, r.corrected);
                 if (k > 0) out.append(buf, (size_t)std::min<int>(k, (int)sizeof buf - 1));
+                if (!r.bt.empty()) { out.back() = '\t'; out.append(r.bt).push_back('\n'); }     // 15th field, as long as the path needs
             }
             out.push_back('\0');
             lens[t][q - qb] = out.size() - start;
@@ -299,7 +300,62 @@ static std::unordered_map<uint64_t, std::string> header_names(const std::string 
     return name;
 }
 
-void convert_alis(const std::string &query_db, const std::string &target_db, const std::string &aln_db, const std::string &out_m8) {
+std::string render_backtrace(const uint32_t *runs, size_t n) {
+    std::string out;
+    char buf[16];
+    for (size_t i = 0; i < n; i++) {
+        const uint32_t op = runs[i] & 3u;
+        if (op > 2u || (runs[i] >> 2) == 0) fail(UC_ERR_ARGS, "backtrace: run %zu (0x%x) is not a run of M, I or D", i, runs[i]);
+        const int k = snprintf(buf, sizeof buf, "%u%c", runs[i] >> 2, "MID"[op]);
+        out.append(buf, (size_t)k);
+    }
+    return out;
+}
+
+static const char *const kFormatColumns[] = {"query", "target", "fident", "pident", "nident", "alnlen", "mismatch", "gapopen", "qstart", "qend", "qlen", "tstart",
+                                             "tend", "tlen", "evalue", "bits", "qcov", "tcov", "cigar", "qaln", "taln", "qseq", "tseq"};
+std::vector<std::string> parse_format_output(const std::string &list) {
+    std::vector<std::string> cols;
+    if (list.empty()) return {"query", "target", "fident", "alnlen", "mismatch", "gapopen", "qstart", "qend", "tstart", "tend", "evalue", "bits"};
+    for (size_t b = 0; b <= list.size();) {
+        size_t e = list.find(',', b);
+        if (e == std::string::npos) e = list.size();
+        const std::string name = list.substr(b, e - b);
+        bool known = false;
+        for (const char *c : kFormatColumns) known |= name == c;
+        if (!known) fail(UC_ERR_ARGS, "--format-output: unknown column '%s'", name.c_str());
+        cols.push_back(name);
+        b = e + 1;
+    }
+    return cols;
+}
+
+// the amino-acid letters of every entry of a sequence DB, by key
+static std::unordered_map<uint64_t, std::string> aa_letters(const std::string &db_prefix) {
+    std::vector<IndexEntry> ix = read_index(db_prefix + ".index");
+    const std::string d = read_whole_file(db_prefix);
+    std::unordered_map<uint64_t, std::string> seq;
+    seq.reserve(ix.size() * 2);
+    for (const IndexEntry &e : ix) {
+        const size_t l = e.len >= 2 ? e.len - 2 : 0;
+        if (e.off + l > d.size()) fail(UC_ERR_IO, "index entry beyond data file %s (key %llu)", db_prefix.c_str(), (unsigned long long)e.key);
+        seq[e.key] = d.substr(e.off, l);
+    }
+    return seq;
+}
+
+void convert_alis(const std::string &query_db, const std::string &target_db, const std::string &aln_db, const std::string &out_m8,
+                  const std::string &format_output) {
+    const bool custom = !format_output.empty();
+    const std::vector<std::string> cols = parse_format_output(format_output);
+    bool need_bt = false, need_seq = false;
+    for (const std::string &c : cols) {
+        need_bt |= c == "cigar" || c == "qaln" || c == "taln";
+        need_seq |= c == "qaln" || c == "taln" || c == "qseq" || c == "tseq";
+    }
+    const auto qseq = need_seq ? aa_letters(query_db) : std::unordered_map<uint64_t, std::string>();
+    const auto tseq_own = need_seq && query_db != target_db ? aa_letters(target_db) : std::unordered_map<uint64_t, std::string>();
+    const auto &tseq = query_db == target_db ? qseq : tseq_own;
     const auto qname = header_names(query_db);
     const auto tname_own = query_db == target_db ? std::unordered_map<uint64_t, std::string>() : header_names(target_db);
     const auto &tname = query_db == target_db ? qname : tname_own;
@@ -322,18 +378,22 @@ void convert_alis(const std::string &query_db, const std::string &target_db, con
             while (p < end && da[p]) {
                 size_t eol = p;
                 while (eol < end && da[eol] && da[eol] != '\n') eol++;
-                // 14 tab-separated fields; fields 2 and 3 (fident, evalue) are passed through as text
-                const char *fld[14];
-                size_t flen[14];
+                // 14 tab-separated fields (15 with the backtrace of -a); fields 2 and 3 (fident, evalue) are passed through as text
+                const char *fld[15];
+                size_t flen[15];
                 int nf = 0;
-                for (size_t b = p; nf < 14;) {
+                for (size_t b = p; nf < 15;) {
                     size_t x = b;
                     while (x < eol && da[x] != '\t') x++;
                     fld[nf] = da.data() + b; flen[nf] = x - b; nf++;
                     if (x >= eol) break;
                     b = x + 1;
                 }
-                if (nf != 14) { err[t] = "malformed row in alignment DB " + aln_db + ": '" + da.substr(p, eol - p) + "'"; return; }
+                if (nf == 15) {   // the 15th field must be the last one
+                    const char *e15 = fld[14] + flen[14];
+                    if (e15 != da.data() + eol) nf = 16;
+                }
+                if (nf != 14 && nf != 15) { err[t] = "malformed row in alignment DB " + aln_db + ": '" + da.substr(p, eol - p) + "'"; return; }
                 auto num = [&](int k) { return strtoll(fld[k], nullptr, 10); };
                 const unsigned long long tkey = strtoull(fld[0], nullptr, 10);
                 const int bits = (int)num(1), qs = (int)num(4), qe = (int)num(5), ts = (int)num(7), te = (int)num(8), alen = (int)num(10),
@@ -342,6 +402,60 @@ void convert_alis(const std::string &query_db, const std::string &target_db, con
                 auto tit = tname.find(tkey);
                 if (tit == tname.end()) { err[t] = "alignment DB target key " + std::to_string(tkey) + " not in " + target_db + "_h"; return; }
                 const int pairs = (qe - qs + 1) + (te - ts + 1) - alen;
+                if (custom) {
+                    if (need_bt && nf != 15) { err[t] = "alignment DB " + aln_db + " has no backtraces: cigar, qaln and taln need a search run with -a"; return; }
+                    const std::string *qs_l = nullptr, *ts_l = nullptr;
+                    if (need_seq) {
+                        auto a = qseq.find(e.key), b2 = tseq.find(tkey);
+                        if (a == qseq.end() || b2 == tseq.end()) { err[t] = "alignment DB key not in the sequence DBs"; return; }
+                        qs_l = &a->second; ts_l = &b2->second;
+                        if (qe >= (int)qs_l->size() || te >= (int)ts_l->size() || qs < 0 || ts < 0) { err[t] = "alignment positions beyond the sequences of " + aln_db; return; }
+                    }
+                    const int qlen = (int)num(6), tlen = (int)num(9);
+                    for (size_t c = 0; c < cols.size(); c++) {
+                        const std::string &nm = cols[c];
+                        if (c) out.push_back('\t');
+                        int k = 0;
+                        if (nm == "query") out.append(qit->second);
+                        else if (nm == "target") out.append(tit->second);
+                        else if (nm == "fident") out.append(fld[2], flen[2]);
+                        else if (nm == "pident") k = snprintf(buf, sizeof buf, "%.1f", alen > 0 ? 100.0 * idents / alen : 0.0);
+                        else if (nm == "nident") k = snprintf(buf, sizeof buf, "%d", idents);
+                        else if (nm == "alnlen") k = snprintf(buf, sizeof buf, "%d", alen);
+                        else if (nm == "mismatch") k = snprintf(buf, sizeof buf, "%d", pairs - idents);
+                        else if (nm == "gapopen") k = snprintf(buf, sizeof buf, "%d", gaps);
+                        else if (nm == "qstart") k = snprintf(buf, sizeof buf, "%d", qs + 1);
+                        else if (nm == "qend") k = snprintf(buf, sizeof buf, "%d", qe + 1);
+                        else if (nm == "qlen") k = snprintf(buf, sizeof buf, "%d", qlen);
+                        else if (nm == "tstart") k = snprintf(buf, sizeof buf, "%d", ts + 1);
+                        else if (nm == "tend") k = snprintf(buf, sizeof buf, "%d", te + 1);
+                        else if (nm == "tlen") k = snprintf(buf, sizeof buf, "%d", tlen);
+                        else if (nm == "evalue") out.append(fld[3], flen[3]);
+                        else if (nm == "bits") k = snprintf(buf, sizeof buf, "%d", bits);
+                        else if (nm == "qcov") k = snprintf(buf, sizeof buf, "%.3f", qlen > 0 ? (double)(qe - qs + 1) / qlen : 0.0);
+                        else if (nm == "tcov") k = snprintf(buf, sizeof buf, "%.3f", tlen > 0 ? (double)(te - ts + 1) / tlen : 0.0);
+                        else if (nm == "cigar") out.append(fld[14], flen[14]);
+                        else if (nm == "qseq") out.append(*qs_l);
+                        else if (nm == "tseq") out.append(*ts_l);
+                        else {   // qaln / taln: the residues of the aligned stretch with '-' where the other sequence alone advances
+                            const bool isq = nm == "qaln";
+                            const std::string &sq = isq ? *qs_l : *ts_l;
+                            size_t at = (size_t)(isq ? qs : ts), stop = (size_t)(isq ? qe : te) + 1;
+                            for (size_t x = 0; x < flen[14];) {
+                                size_t len = 0, d0 = x;
+                                while (x < flen[14] && fld[14][x] >= '0' && fld[14][x] <= '9') len = len * 10 + (size_t)(fld[14][x++] - '0');
+                                const char op = x < flen[14] ? fld[14][x++] : '?';
+                                const bool own = op == 'M' || op == (isq ? 'I' : 'D'), other = op == (isq ? 'D' : 'I');
+                                if (x == d0 + 1 || len == 0 || (!own && !other) || (own && at + len > stop)) { err[t] = "malformed backtrace in alignment DB " + aln_db; return; }
+                                if (own) { out.append(sq, at, len); at += len; } else out.append(len, '-');
+                            }
+                            if (at != stop) { err[t] = "backtrace and positions disagree in alignment DB " + aln_db; return; }
+                        }
+                        if (k > 0) out.append(buf, (size_t)k);
+                    }
+                    out.push_back('\n');
+                    continue;
+                }
                 out.append(qit->second).push_back('\t');
                 out.append(tit->second);
                 const int k = snprintf(buf, sizeof buf, "\t%.*s\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%.*s\t%d\n", (int)std::min<size_t>(flen[2], 64), fld[2], alen,

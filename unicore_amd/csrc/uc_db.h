@@ -37,11 +37,18 @@ struct AlnRow {
     uint64_t tkey;
     int32_t bits, qstart, qend, qlen, tstart, tend, tlen, aln_len, idents, gap_opens, corrected;
     double fident, evalue;
+    std::string bt;     // -a: the backtrace as text ("35M2D110M"), the 15th field of the row; empty = a 14-field row
 };
+// a slice of runs (length << 2 | op; 0 M, 1 I, 2 D) as the run-length text of the alignment DB and of convertalis' `cigar` column
+std::string render_backtrace(const uint32_t *runs, size_t n);
+// the column names of --format-output LIST in order (empty LIST = the 12 BLAST-tab columns); an unknown name is UC_ERR_ARGS
+std::vector<std::string> parse_format_output(const std::string &list);
 void write_aln_db(const std::string &prefix, const std::vector<uint64_t> &qkeys, const std::vector<std::vector<AlnRow>> &rows);
 // == foldseek convertalis (search.rs:52-57): BLAST-tab "query target fident alnlen mismatch gapopen qstart qend tstart
 // tend evalue bits", positions 1-based; names = first token of the header entries of the two DBs
-void convert_alis(const std::string &query_db, const std::string &target_db, const std::string &aln_db, const std::string &out_m8);
+// format_output: --format-output LIST; empty = the 12 columns above, byte for byte.  Rows have 14 fields, or 15 when uc_search ran with -a
+void convert_alis(const std::string &query_db, const std::string &target_db, const std::string &aln_db, const std::string &out_m8,
+                  const std::string &format_output = "");
 // == foldseek rmdb (cluster.rs:67-76)
 void remove_db(const std::string &prefix);
 

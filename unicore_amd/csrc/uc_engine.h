@@ -142,6 +142,9 @@ struct SwPassPair { uint32_t q, t; int32_t qs, qe, ts, te, known; };
 // its outputs in list order (any may be null): score, qe, te (MODE 0 / 2 / 4 / 6; te keeps SW_TE_UNIQUE), class id of the table,
 // traceback statistics (MODE 3 / 7) and the band-miss mark of the MODE 7 walk
 struct SwPassOut { int32_t *score, *qe, *te, *cls, *aln_len, *idents, *gaps, *miss; };
+// backtraces of a traceback pass run with emission (Engine::tb_emit_pass): slice i is runs[run_off[i] .. run_off[i + 1]), a run is length << 2 | op
+// (0 M, 1 I, 2 D), from the start of the alignment to its end; empty for a pair whose walk left the band.  plain[i]: the stored-int32-matrix pass served it
+struct BtPassOut { std::vector<uint64_t> run_off; std::vector<uint32_t> runs; std::vector<int32_t> plain; };
 struct PrefilterScratch;                                  // uc_prefilter.hip
 void free_scratch(PrefilterScratch *p);
 struct AlignScratch;                                      // uc_align.hip
@@ -215,6 +218,15 @@ struct Engine {
     DevBuf<int32_t> d_hs, d_hd;        // ungapped score / diagonal per hit
     DevBuf<uc_aln> d_alns;             // parallel to the hit arrays
     bool alns_valid = false;
+    // backtraces (-a): one ragged buffer of runs (length << 2 | op) that the emitting walks append to, and per hit (parallel to d_alns) where its
+    // slice lies and how many runs it has (bit 31: read with I and D exchanged - a mutual hit that shares its partner's path; bit 30: stored-matrix pass).
+    // Filled only while emit_bt is set: uc_search, the staged API of an engine created with -a, tb_emit_pass; a uc_cluster call never reads them.
+    bool emit_bt = false;
+    DevBuf<uint32_t> d_bt_runs, d_bt_n;
+    DevBuf<unsigned long long> d_bt_pos;
+    uint64_t bt_used = 0;
+    // hits [begin, begin + n): run_off[n + 1] and the runs themselves; pairs that were not accepted get an empty slice
+    void get_backtraces(uint64_t begin, uint64_t n, uint64_t *run_off, std::vector<uint32_t> &runs) const;
     // accepted edges (E6): appended on the DEVICE by align(); the host copy is made only when somebody asks for it (getters,
     // multi-rank gather) - a single-rank step builds the set-cover graph straight from the device list
     DevBuf<uint32_t> d_edges;          // 2 x n_edges_dev
@@ -286,7 +298,10 @@ struct Engine {
     // kernel-level
     void ungapped_batch(uint64_t n, const uint32_t *q, const uint32_t *t, const int32_t *diag, int32_t *out);
     void sw_batch(int mode, const std::vector<PairIn> &pairs, int32_t *score, int32_t *qe, int32_t *te);
-    void sw_pass(int tab, int mode, int band, bool raw, const std::vector<SwPassPair> &pairs, const SwPassOut &out);
+    void sw_pass(int tab, int mode, int band, bool raw, const std::vector<SwPassPair> &pairs, const SwPassOut &out, BtPassOut *bt = nullptr);
+    // one traceback pass WITH emission on the listed boxes, by route: 0 = packed MODE 7 + walk with band `band`, 1 = the same with the whole box stored,
+    // 2 = the stored int32 matrix for every pair, 3 = the long-query route of the packed pass (every query beyond the systolic classes)
+    void tb_emit_pass(int route, int band, const std::vector<SwPassPair> &pairs, const SwPassOut &out, BtPassOut &bt);
 
     double timed_ms_begin();   // records ev0 on the stream
     double timed_ms_end();     // records ev1, syncs, returns elapsed ms

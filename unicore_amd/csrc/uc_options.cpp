@@ -118,9 +118,9 @@ int option_arity(const std::string &f) {
         "--gap-open", "--gap-extend", "--spaced-kmer-pattern", "--rev-correction", "--linclust", "--kmer-per-seq", "--sym-dedup",
         "--sw-kernel", "--evalue-lambda", "--evalue-k", "--mat3di", "--mat-aa", "--cluster-mode", "--cluster-steps",
         "--alignment-type", "--alignment-mode", "--threads", "-v", "--remove-tmp-files", "--db-load-mode", "--compressed",
-        "--gpus", "--target-shards", "--mat-bit-factor-3di", "--mat-bit-factor-aa", "--comp-bias-corr", "--comp-bias-corr-scale", "--min-score-table", "--length-gate"};
+        "--gpus", "--target-shards", "--mat-bit-factor-3di", "--mat-bit-factor-aa", "--comp-bias-corr", "--comp-bias-corr-scale", "--min-score-table", "--length-gate", "--format-output"};
     for (const char *v : valued) if (f == v) return 1;
-    if (f == "--single-step-clustering") return 2;
+    if (f == "--single-step-clustering" || f == "-a") return 2;
     return -1;
 }
 
@@ -167,6 +167,8 @@ void parse_cluster_options(const std::string &opts, Params &p) {
         else if (f == "--length-gate") { p.len_gate = to_int(f, value()) != 0; }
         else if (f == "--cluster-mode") { p.cluster_mode = to_int(f, value()); if (p.cluster_mode != 0) fail(UC_ERR_ARGS, "--cluster-mode %d unsupported (only 0 = greedy set cover)", p.cluster_mode); }
         else if (f == "--single-step-clustering") { p.single_step = opt_bool(); p.single_step_given = true; }
+        else if (f == "-a") { p.want_bt = opt_bool(); /* implies want_tb where alignments are kept: uc_search, uc_engine_create */ }
+        else if (f == "--format-output") { p.format_output = value(); /* read by convertalis only */ }
         else if (f == "--cluster-steps") { p.cluster_steps = to_int(f, value()); p.cluster_steps_given = true; }
         else if (f == "--gpus") { p.num_gpus = to_int(f, value()); if (p.num_gpus < 0 || p.num_gpus > 64) fail(UC_ERR_ARGS, "--gpus must be in [0,64] (0 = all visible)"); }
         else if (f == "--target-shards") { p.target_shards = to_int(f, value()); if (p.target_shards < 0 || p.target_shards > 64) fail(UC_ERR_ARGS, "--target-shards must be in [0,64] (0 = one shard per GPU)"); }

@@ -36,6 +36,8 @@ struct Params {
     int gap_open = 10, gap_ext = 1;
     int rev_correction = 1;
     int want_tb = 0;            // 1: traceback statistics (alnlen, idents, gaps) for every accepted pair (search path)
+    int want_bt = 0;            // 1 (-a): the alignment backtrace (run-length M/I/D) of every accepted pair as well (uc_search and the staged API, where it implies want_tb; no effect in uc_cluster)
+    std::string format_output;  // convertalis --format-output LIST (empty = the 12 BLAST-tab columns); accepted and ignored elsewhere
     int sym_dedup = 1;          // 1: mutual hits (q,t)/(t,q) share one forward and one reversed-query DP (needs symmetric matrices)
     bool mat_symmetric = false; // set by finalize_params
     int sw_pk = 1;              // 1: packed 16-bit DP kernel for queries <= 1024 rows (int32 re-run when flagged)
