@@ -837,18 +837,12 @@ struct SwPlan {
 
 // running maximum (inclusive) of a u32 array
 static void max_scan_u32(Engine &E, DevBuf<char> &tmp, const uint32_t *in, uint32_t *out, uint32_t n) {
-    size_t tb = 0;
-    UC_HIP(rocprim::inclusive_scan(nullptr, tb, in, out, (size_t)n, MaxU32(), E.stream));
-    tmp.reserve(tb + 256);
-    UC_HIP(rocprim::inclusive_scan(tmp.p, tb, in, out, (size_t)n, MaxU32(), E.stream));
+    rocprim_call(tmp, [&](void *t, size_t &b) { return rocprim::inclusive_scan(t, b, in, out, (size_t)n, MaxU32(), E.stream); });
 }
 
 // a 0/1 flag array -> its exclusive scan in pos (where each flagged entry goes) -> the number of flagged entries (one host synchronisation)
 static uint32_t compact(Engine &E, DevBuf<char> &tmp, const uint32_t *flag, uint32_t *pos, uint32_t n) {
-    size_t tb = 0;
-    UC_HIP(rocprim::exclusive_scan(nullptr, tb, flag, pos, 0u, (size_t)n, rocprim::plus<uint32_t>(), E.stream));
-    tmp.reserve(tb + 256);
-    UC_HIP(rocprim::exclusive_scan(tmp.p, tb, flag, pos, 0u, (size_t)n, rocprim::plus<uint32_t>(), E.stream));
+    rocprim_call(tmp, [&](void *t, size_t &b) { return rocprim::exclusive_scan(t, b, flag, pos, 0u, (size_t)n, rocprim::plus<uint32_t>(), E.stream); });
     if (!n) return 0;
     uint32_t a = 0, b = 0;
     UC_HIP(hipMemcpyAsync(&a, pos + (n - 1), 4, hipMemcpyDeviceToHost, E.stream));
@@ -894,10 +888,7 @@ static void build_plan(Engine &E, SwPlan &P, DevBuf<char> &tmp, uint32_t n, cons
     P.bytes.reserve(2); P.bounds.reserve(2 * NB);
     UC_HIP(hipMemsetAsync(P.bytes.p, 0, 16, s));
     hipLaunchKernelGGL(plan_key_kernel, grid_for(n), dim3(256), 0, s, n, q, t, qe, te, qs, ts, E.ddb.len, tab, P.key.p, P.idx_in.p, P.bytes.p);
-    size_t tb = 0;
-    UC_HIP(rocprim::radix_sort_pairs(nullptr, tb, P.key.p, P.key2.p, P.idx_in.p, P.idx.p, (size_t)n, 0u, 45u, s));
-    tmp.reserve(tb + 256);
-    UC_HIP(rocprim::radix_sort_pairs(tmp.p, tb, P.key.p, P.key2.p, P.idx_in.p, P.idx.p, (size_t)n, 0u, 45u, s));
+    rocprim_call(tmp, [&](void *t, size_t &b) { return rocprim::radix_sort_pairs(t, b, P.key.p, P.key2.p, P.idx_in.p, P.idx.p, (size_t)n, 0u, 45u, s); });
     hipLaunchKernelGGL(plan_gather_kernel, grid_for(n), dim3(256), 0, s, n, P.key2.p, P.idx.p, t, qe, te, qs, ts, P.sq.p, P.st.p, P.sqe.p, P.ste.p, P.sqs.p, P.sts.p, P.head.p);
     if (aux) {
         P.saux.reserve(n);
@@ -912,9 +903,7 @@ static void build_plan(Engine &E, SwPlan &P, DevBuf<char> &tmp, uint32_t n, cons
     P.tasks_in.reserve(P.ntasks); P.tkey.reserve(P.ntasks); P.tkey2.reserve(P.ntasks); P.tidx.reserve(P.ntasks); P.tidx2.reserve(P.ntasks);
     hipLaunchKernelGGL(plan_taskcount_kernel, grid_for(P.ntasks), dim3(256), 0, s, P.ntasks, n, P.tasks.p, P.tcls.p, P.key2.p, P.tkey.p, P.tidx.p);
     if (lpt) {
-        UC_HIP(rocprim::radix_sort_pairs(nullptr, tb, P.tkey.p, P.tkey2.p, P.tidx.p, P.tidx2.p, (size_t)P.ntasks, 0u, 37u, s));
-        tmp.reserve(tb + 256);
-        UC_HIP(rocprim::radix_sort_pairs(tmp.p, tb, P.tkey.p, P.tkey2.p, P.tidx.p, P.tidx2.p, (size_t)P.ntasks, 0u, 37u, s));
+        rocprim_call(tmp, [&](void *t, size_t &b) { return rocprim::radix_sort_pairs(t, b, P.tkey.p, P.tkey2.p, P.tidx.p, P.tidx2.p, (size_t)P.ntasks, 0u, 37u, s); });
         UC_HIP(hipMemcpyAsync(P.tasks_in.p, P.tasks.p, (size_t)P.ntasks * sizeof(SwTask), hipMemcpyDeviceToDevice, s));
         hipLaunchKernelGGL(plan_taskgather_kernel, grid_for(P.ntasks), dim3(256), 0, s, P.ntasks, P.tidx2.p, P.tasks_in.p, P.tasks.p);
     }
@@ -1249,10 +1238,7 @@ static void forward_pass(Engine &E, AlignBatch &B) {
     A.ukey.reserve(n); A.ukey2.reserve(n); A.uidx_in.reserve(n); A.uidx.reserve(n);
     A.fq.reserve(n); A.ft.reserve(n); A.mirror.reserve(n); A.rep.reserve(n); A.rpos.reserve(n);
     hipLaunchKernelGGL(ukey_kernel, grid_for(n), dim3(256), 0, s, n, B.dq, B.dt, E.ddb.len, A.ukey.p, A.uidx_in.p);
-    size_t tb = 0;
-    UC_HIP(rocprim::radix_sort_pairs(nullptr, tb, A.ukey.p, A.ukey2.p, A.uidx_in.p, A.uidx.p, (size_t)n, 0u, 49u, s));
-    A.tmp.reserve(tb + 256);
-    UC_HIP(rocprim::radix_sort_pairs(A.tmp.p, tb, A.ukey.p, A.ukey2.p, A.uidx_in.p, A.uidx.p, (size_t)n, 0u, 49u, s));
+    rocprim_call(A.tmp, [&](void *t, size_t &b) { return rocprim::radix_sort_pairs(t, b, A.ukey.p, A.ukey2.p, A.uidx_in.p, A.uidx.p, (size_t)n, 0u, 49u, s); });
     hipLaunchKernelGGL(umark_kernel, grid_for(n), dim3(256), 0, s, n, A.ukey2.p, A.uidx.p, B.dq, B.dt, A.fq.p, A.ft.p, A.mirror.p, A.rep.p);
     const uint32_t nu = compact(E, A.tmp, A.rep.p, A.rpos.p, n);
     A.qr.reserve(nu); A.tr.reserve(nu); A.jrep.reserve(nu); A.su.reserve(nu); A.qeu.reserve(nu); A.teu.reserve(nu);
@@ -1405,10 +1391,7 @@ static void tb_walk(Engine &E, uint32_t p0, uint32_t p1, int band, const uint8_t
     }
     UC_TB_WALK(1, 0);
     const size_t k = p1 - p0;
-    size_t tb = 0;
-    UC_HIP(rocprim::exclusive_scan(nullptr, tb, A.bt_cnt3.p + p0, A.bt_off3.p + p0, 0u, k, rocprim::plus<uint32_t>(), s));
-    A.tmp.reserve(tb + 256);
-    UC_HIP(rocprim::exclusive_scan(A.tmp.p, tb, A.bt_cnt3.p + p0, A.bt_off3.p + p0, 0u, k, rocprim::plus<uint32_t>(), s));
+    rocprim_call(A.tmp, [&](void *t, size_t &b) { return rocprim::exclusive_scan(t, b, A.bt_cnt3.p + p0, A.bt_off3.p + p0, 0u, k, rocprim::plus<uint32_t>(), s); });
     uint32_t lo = 0, lc = 0;
     UC_HIP(hipMemcpyAsync(&lo, A.bt_off3.p + (p1 - 1), 4, hipMemcpyDeviceToHost, s));
     UC_HIP(hipMemcpyAsync(&lc, A.bt_cnt3.p + (p1 - 1), 4, hipMemcpyDeviceToHost, s));
@@ -1481,7 +1464,8 @@ static uint64_t tb_run_bytes(Engine &E, int band, const TbBudget &budget) {
     AlignScratch &A = scratch_of(E);
     SwPlan &P3 = A.tb_P3;
     hipStream_t s = E.stream;
-    const auto [n_pk3, nt_pk] = packed_prefix(P3);       // every systolic class of table 1 is packed, and their tasks come first, in pair order
+    const PackedPrefix pk = packed_prefix(P3);           // every systolic class of table 1 is packed, and their tasks come first, in pair order
+    const uint32_t n_pk3 = pk.pairs, nt_pk = pk.tasks;
     uint64_t launches = 0;
     double tb_ms = 0;
     unsigned long long total = 0;
@@ -1499,10 +1483,7 @@ static uint64_t tb_run_bytes(Engine &E, int band, const TbBudget &budget) {
         tbsize.reserve((size_t)n_pk3 + 1); tboff.reserve((size_t)n_pk3 + 1);
         hipLaunchKernelGGL(tb_size_kernel, grid_for(n_pk3), dim3(256), 0, s, n_pk3, P3.key2.p, P3.segstart.p, P3.ste.p,
                            P3.sts.p, P3.sqs.p, P3.sqe.p, band, 1, tbsize.p);
-        size_t tbb = 0;
-        UC_HIP(rocprim::exclusive_scan(nullptr, tbb, tbsize.p, tboff.p, 0ull, (size_t)n_pk3, rocprim::plus<unsigned long long>(), s));
-        A.tmp.reserve(tbb + 256);
-        UC_HIP(rocprim::exclusive_scan(A.tmp.p, tbb, tbsize.p, tboff.p, 0ull, (size_t)n_pk3, rocprim::plus<unsigned long long>(), s));
+        rocprim_call(A.tmp, [&](void *t, size_t &b) { return rocprim::exclusive_scan(t, b, tbsize.p, tboff.p, 0ull, (size_t)n_pk3, rocprim::plus<unsigned long long>(), s); });
         // where every task's matrices begin, and its first pair: the host cuts the batches at task boundaries
         toff.reserve((size_t)nt_pk + 1);
         hipLaunchKernelGGL(tb_taskoff_kernel, grid_for(nt_pk), dim3(256), 0, s, nt_pk, P3.tasks.p, tboff.p, toff.p);
@@ -2149,10 +2130,7 @@ void Engine::set_cover_graph(uint32_t n, const uint32_t *h_edges, const uint32_t
         }
         UC_HIP(hipMemsetAsync(bad.p, 0, 4, stream));
         hipLaunchKernelGGL(edge_key_kernel, grid_for(n_edges), dim3(256), 0, stream, n_edges, e_in, n, key.p, bad.p);
-        size_t tb = 0;
-        UC_HIP(rocprim::radix_sort_keys(nullptr, tb, key.p, key2.p, (size_t)m, 0u, 64u, stream));
-        tmp.reserve(tb + 256);
-        UC_HIP(rocprim::radix_sort_keys(tmp.p, tb, key.p, key2.p, (size_t)m, 0u, 64u, stream));
+        rocprim_call(tmp, [&](void *t, size_t &b) { return rocprim::radix_sort_keys(t, b, key.p, key2.p, (size_t)m, 0u, 64u, stream); });
         hipLaunchKernelGGL(edge_uniq_kernel, grid_for(m), dim3(256), 0, stream, m, key2.p, flag.p);
         const uint32_t mu = compact(*this, tmp, flag.p, pos.p, (uint32_t)m);
         uint32_t hbad = 0;

@@ -136,6 +136,16 @@ inline dim3 grid_for(uint64_t n, uint32_t cap = 16384) {
     return dim3((uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(b, cap)));
 }
 
+// one rocPRIM device call: size query (host only, launches nothing), temporary storage reserved with 256 B to spare, the run.
+// `call` is (void *tmp, size_t &bytes) -> hipError_t and holds the argument list, so that it is written once and its iterator types are deduced once
+template <class F>
+inline void rocprim_call(DevBuf<char> &tmp, F &&call) {
+    size_t bytes = 0;
+    UC_HIP(call(nullptr, bytes));
+    tmp.reserve(bytes + 256);
+    UC_HIP(call((void *)tmp.p, bytes));
+}
+
 struct PairIn { uint32_t q, t; int32_t qe, te; };
 // one pair of a single gapped pass (Engine::sw_pass): box [qs..qe] x [ts..te] (MODE 3 / 7; MODE 2 / 6 read qe, te only), known optimum (MODE 4 / 6 / 7)
 struct SwPassPair { uint32_t q, t; int32_t qs, qe, ts, te, known; };
@@ -250,9 +260,6 @@ struct Engine {
     // and against the queries of `others` (disjoint from the shard), every pair of the latter also mirrored (the candidate of the pair the other
     // way round, diag_select_kernel); installs the merged lists of all queries touched
     void prefilter_cells(uint32_t tbegin, uint32_t tend, const std::vector<std::pair<uint32_t, uint32_t>> &others);
-    void prefilter_impl(uint32_t tbegin, uint32_t tend, uint32_t qbegin, uint32_t qend, bool mirror_all);
-    bool prefilter_one(uint32_t tbegin, uint32_t tend, uint32_t qbegin, uint32_t qend, bool count_sims, double density_limit = 0.0,
-                       double *density_out = nullptr, uint32_t mirror_q0 = UINT32_MAX);   // one target chunk (mirror_q0: symmetric pass, uc_prefilter.hip)
     PrefilterScratch *pre = nullptr;                       // work buffers kept between prefilter calls
     AlignScratch *aln = nullptr;                           // ... and between align calls
     uint64_t last_align_hits = 0;                          // listed pairs of the last align() whose buffers `aln` still holds (0 after the set was given back)
@@ -285,7 +292,7 @@ struct Engine {
     // the installed lists regrouped by owner rank of each pair (stable; counts[world] on the host) into caller-owned device arrays
     void partition_hits_by_owner(uint32_t world, uint32_t *dq, uint32_t *dt, int32_t *ds, int32_t *dd, uint64_t *counts);
     void get_alns(uint64_t begin, uint64_t n, uc_aln *out) const;
-    void finish_hit_lists();                                  // counts/offsets from the device arrays
+    void finish_hit_lists(const char *who);                   // counts/offsets from the device arrays (who: prefix of the error message)
     void align(uint32_t qbegin, uint32_t qend);
     // E7: adjacency (sort + unique of both edge directions) on the device, greedy cover on the host
     void set_cover_device(uint32_t n, const uint32_t *h_edges, uint64_t n_edges, uint32_t *assign);

@@ -142,23 +142,16 @@ std::vector<uint32_t> Engine::linclust_pairs_impl(uint64_t *install) {
     ent.reserve(cap); ent2.reserve(cap); cnt.reserve(1);
     UC_HIP(hipMemsetAsync(cnt.p, 0, 8, stream));
     hipLaunchKernelGGL(lc_select_kernel, dim3((uint32_t)std::min<uint64_t>((n + 3) / 4, 8192)), dim3(256), 0, stream, ddb, cfg, ent.p, cnt.p);
-    size_t tb = 0;
-    UC_HIP(rocprim::radix_sort_keys(nullptr, tb, ent.p, ent2.p, (size_t)cap, 0u, 58u, stream));
-    tmp.reserve(tb + 256);
-    UC_HIP(rocprim::radix_sort_keys(tmp.p, tb, ent.p, ent2.p, (size_t)cap, 0u, 58u, stream));
+    rocprim_call(tmp, [&](void *t, size_t &b) { return rocprim::radix_sort_keys(t, b, ent.p, ent2.p, (size_t)cap, 0u, 58u, stream); });
     unsigned long long ne = 0;
     UC_HIP(hipMemcpyAsync(&ne, cnt.p, 8, hipMemcpyDeviceToHost, stream));
     UC_HIP(hipStreamSynchronize(stream));
     if (ne == 0) return out;
     pr.reserve(ne); pr2.reserve(ne); flag.reserve(ne); pos.reserve(ne);
     hipLaunchKernelGGL(lc_group_kernel, lc_grid(ne), dim3(256), 0, stream, ent2.p, (uint64_t)ne, ddb.len, pr.p);
-    UC_HIP(rocprim::radix_sort_keys(nullptr, tb, pr.p, pr2.p, (size_t)ne, 0u, pbits, stream));
-    tmp.reserve(tb + 256);
-    UC_HIP(rocprim::radix_sort_keys(tmp.p, tb, pr.p, pr2.p, (size_t)ne, 0u, pbits, stream));
+    rocprim_call(tmp, [&](void *t, size_t &b) { return rocprim::radix_sort_keys(t, b, pr.p, pr2.p, (size_t)ne, 0u, pbits, stream); });
     hipLaunchKernelGGL(lc_flag_kernel, lc_grid(ne), dim3(256), 0, stream, pr2.p, (uint64_t)ne, flag.p);
-    UC_HIP(rocprim::exclusive_scan(nullptr, tb, flag.p, pos.p, 0u, (size_t)ne, rocprim::plus<uint32_t>(), stream));
-    tmp.reserve(tb + 256);
-    UC_HIP(rocprim::exclusive_scan(tmp.p, tb, flag.p, pos.p, 0u, (size_t)ne, rocprim::plus<uint32_t>(), stream));
+    rocprim_call(tmp, [&](void *t, size_t &b) { return rocprim::exclusive_scan(t, b, flag.p, pos.p, 0u, (size_t)ne, rocprim::plus<uint32_t>(), stream); });
     uint32_t lp = 0, lf = 0;
     UC_HIP(hipMemcpyAsync(&lp, pos.p + (ne - 1), 4, hipMemcpyDeviceToHost, stream));
     UC_HIP(hipMemcpyAsync(&lf, flag.p + (ne - 1), 4, hipMemcpyDeviceToHost, stream));

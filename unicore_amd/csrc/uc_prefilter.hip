@@ -1322,7 +1322,7 @@ struct PrefilterScratch {
     DevBuf<uint64_t> d_keys, d_keys2, d_pos, d_skey, d_skey2, d_rval2, d_qbase, d_soff, d_qr;
     DevBuf<int32_t> d_cd, d_cd2, d_score, d_mval;      // d_mkey / d_mval: output of the sorted-run merge (merge_hits_dev)
     DevBuf<uint64_t> d_mkey;
-    DevBuf<uint32_t> acc_q, acc_t, pass_q, pass_t;     // chunk loop of prefilter_impl: running top-M accumulator and the pass's lists (swapped in and out of the engine)
+    DevBuf<uint32_t> acc_q, acc_t, pass_q, pass_t;     // chunk loop (prefilter_chunks): running top-M accumulator and the pass's lists (swapped in and out of the engine)
     DevBuf<int32_t> acc_s, acc_d, pass_s, pass_d;
     // distinct-k-mer enumeration (E2)
     DevBuf<uint8_t> d_kflag, d_wflag;
@@ -1389,13 +1389,585 @@ static size_t scratch_release_target(bool gapped_stage_sizes_by_free_memory, uin
                                             : (size_t)600 * (size_t)std::min<uint64_t>(n_hits, 256ull << 20) + (size_t)44 * (size_t)n_hits + ((size_t)8 << 30);
     return fr >= need ? 0 : std::min(scratch_bytes, need - fr);
 }
+// gives prefilter scratch back before the gapped stage starts on the installed lists, as far as the rule above asks
+static void release_scratch_for_gapped_stage(Engine &E) {
+    if (!E.pre) return;
+    E.pre->release_bytes(scratch_release_target(E.p.min_seq_id > 0.0f || E.p.want_tb, E.n_hits, E.pre->bytes(),
+                                                E.aln != nullptr && (double)E.last_align_hits >= 0.9 * (double)E.n_hits));
+}
+// the engine's four hit arrays (query, target, score, diagonal) as a unit: exchanged with another set (no copy) ...
+static void swap_hits(Engine &E, DevBuf<uint32_t> &q, DevBuf<uint32_t> &t, DevBuf<int32_t> &s, DevBuf<int32_t> &d) {
+    q.swap(E.d_hq); t.swap(E.d_ht); s.swap(E.d_hs); d.swap(E.d_hd);
+}
+// ... and copied on the device into arrays with room for n_hits records (complete on return)
+static void copy_hits_dev(const Engine &E, uint32_t *dq, uint32_t *dt, int32_t *ds, int32_t *dd) {
+    UC_HIP(hipMemcpyAsync(dq, E.d_hq.p, E.n_hits * 4, hipMemcpyDeviceToDevice, E.stream));
+    UC_HIP(hipMemcpyAsync(dt, E.d_ht.p, E.n_hits * 4, hipMemcpyDeviceToDevice, E.stream));
+    UC_HIP(hipMemcpyAsync(ds, E.d_hs.p, E.n_hits * 4, hipMemcpyDeviceToDevice, E.stream));
+    UC_HIP(hipMemcpyAsync(dd, E.d_hd.p, E.n_hits * 4, hipMemcpyDeviceToDevice, E.stream));
+    UC_HIP(hipStreamSynchronize(E.stream));
+}
+// per-query counts / offsets of the installed (query-grouped) device lists: the host only keeps these two small arrays (hit_cnt is all zero on entry)
+void Engine::finish_hit_lists(const char *who) {
+    const uint32_t n = hdb.n;
+    if (n_hits) {
+        pre->d_cnt.reserve(n);
+        hipLaunchKernelGGL(hit_count_kernel, grid_for(n), dim3(256), 0, stream, d_hq.p, n_hits, n, pre->d_cnt.p);
+        UC_HIP(hipMemcpyAsync(hit_cnt.data(), pre->d_cnt.p, (size_t)n * 4, hipMemcpyDeviceToHost, stream));
+        UC_HIP(hipStreamSynchronize(stream));
+    }
+    for (uint32_t q = 0; q < n; q++) hit_off[q + 1] = hit_off[q] + hit_cnt[q];
+    if (hit_off[n] != n_hits) fail(UC_ERR_GENERIC, "%s: hit list bookkeeping mismatch", who);
+}
 
-// E1-E4 for a target range.  Large ranges are processed as several index chunks whose per-query top-M lists are
+// ---- E1-E4 for ONE target chunk (prefilter_one): a short driver over passes that share this state ----------
+constexpr uint64_t RUN_MAX = 1ull << 29;       // runs per batch (6 GiB + 6 GiB sort double buffer)
+struct PrefilterPass {
+    KmerCfg cfg;
+    KeyFmt fmt;
+    uint32_t tbegin = 0, tend = 0;             // the target chunk
+    uint32_t qbegin = 0, qend = 0;             // the queries matched against it
+    uint32_t mirror_q0 = UINT32_MAX;           // symmetric pass (diag_select_kernel): queries from here on also yield the pair the other way round
+    bool count_sims = false;
+    double density_limit = 0.0, *density_out = nullptr;
+    const void *ent_p = nullptr;               // the chunk's n_entries index entries sorted by k-mer (compact or wide, fmt.compact)
+    uint32_t n_entries = 0;
+    uint64_t HIT_CAP = 0, HIT_CAP_BIG = 0, DRUN_MAX = 0;
+    uint64_t n_hits_total = 0, n_cand_total = 0, cand_cap = 0, run_cap = 1ull << 20;
+    double t_kmer = 0, t_ung = 0, t_sel = 0, gpu_ms = 0;   // host seconds of E2 / E3 / E4 and the event time of everything
+};
+// a query "super-batch" [begin, end) of the chunk with what its plan leaves for the exact batches
+struct SuperBatch {
+    uint32_t begin = 0, end = 0;
+    uint32_t P0 = 0, NP = 0;                   // its residue positions [P0, P0 + NP)
+    std::vector<uint64_t> h_qh, h_qr;          // k-mer hits / runs per query of the super-batch
+    uint64_t hit_cap = 0;                      // keys per exact batch
+    double frac = 1.0;                         // share of the remaining queries to try as the next super-batch
+};
+// one exact batch of queries [qa, qb): as many as fit the key and run buffers
+struct QueryBatch {
+    uint32_t qa = 0, qb = 0;
+    uint64_t total_hits = 0, n_runs = 0;
+    uint32_t qp0 = 0, qp1 = 0, nq_res = 0;     // its residue positions
+    unsigned kbits = 0;                        // significant bits of its keys [query - qa | target | diagonal]
+    const uint64_t *sorted = nullptr;          // the n_sort keys in that order
+    uint64_t n_sort = 0;
+};
+// consumes max_len, the sequence count and the chunk's target range; produces the layout of the (query, target, diagonal) keys
+static KeyFmt key_format(const Engine &E, uint32_t tbegin, uint32_t tend) {
+    KeyFmt fmt;
+    const uint32_t m = std::min<uint32_t>(std::max<uint32_t>(E.max_len, 2), 65536u);
+    fmt.dbits = 1;
+    while ((1u << (fmt.dbits - 1)) < m) fmt.dbits++;
+    fmt.dbias = 1 << (fmt.dbits - 1);
+    fmt.tbits = 1;
+    while ((1u << fmt.tbits) < E.hdb.n) fmt.tbits++;
+    int rbits = 1;                                   // bits of a target id relative to this chunk
+    while ((1ull << rbits) < (uint64_t)std::max<uint32_t>(tend - tbegin, 1)) rbits++;
+    fmt.compact = rbits + fmt.dbits <= 32 && !getenv("UC_PREFILTER_WIDE");
+    fmt.tbase = tbegin;
+    return fmt;
+}
+
+// E1.  consumes the target chunk; produces its k-mer index (d_koff offsets, d_kbits presence bitmap, entries sorted by k-mer: d_ent wide [sequence : 32 |
+// position : 16] or d_ent32 compact [sequence - tbegin | position : dbits - 1]), PP.fmt / ent_p / n_entries and the E1 stats
+static void build_index(Engine &E, PrefilterPass &PP) {
+    PrefilterScratch &S = *E.pre;
+    Timer t_index;
+    E.timed_ms_begin();
+    const uint32_t tp0 = E.h_poff[PP.tbegin], tp1 = E.h_poff[PP.tend];
+    const uint32_t nres = tp1 - tp0;
+    S.d_koff.reserve((size_t)KSPACE + 1);
+    PP.fmt = key_format(E, PP.tbegin, PP.tend);
+    const KeyFmt &fmt = PP.fmt;
+    const size_t cap = std::max<uint32_t>(nres, 1);
+    S.k_in.reserve(cap); S.k_out.reserve(cap);
+    if (fmt.compact) { S.v_in32.reserve(cap); S.d_ent32.reserve(cap); PP.ent_p = S.d_ent32.p; }
+    else { S.v_in.reserve(cap); S.d_ent.reserve(cap); PP.ent_p = S.d_ent.p; }
+    if (nres) {
+        hipLaunchKernelGGL(kmer_extract_kernel, grid_for(nres), dim3(256), 0, E.stream, E.ddb, PP.tbegin, PP.tend, PP.cfg, tp0, tp1, S.k_in.p,
+                           fmt.compact ? nullptr : S.v_in.p, fmt.compact ? S.v_in32.p : nullptr, fmt.dbits - 1);
+        if (fmt.compact)
+            rocprim_call(S.d_temp, [&](void *t, size_t &b) { return rocprim::radix_sort_pairs(t, b, S.k_in.p, S.k_out.p, S.v_in32.p, S.d_ent32.p, (size_t)nres, 0u, 32u, E.stream); });
+        else
+            rocprim_call(S.d_temp, [&](void *t, size_t &b) { return rocprim::radix_sort_pairs(t, b, S.k_in.p, S.k_out.p, S.v_in.p, S.d_ent.p, (size_t)nres, 0u, 32u, E.stream); });
+    }
+    // number of valid entries = first index with key >= KSPACE: the offsets kernel's last slot
+    hipLaunchKernelGGL(kmer_offsets_kernel, grid_for((uint64_t)KSPACE + 1), dim3(256), 0, E.stream, S.k_out.p, nres, S.d_koff.p);
+    S.d_kbits.reserve((KSPACE + 31) / 32);
+    hipLaunchKernelGGL(kmer_bits_kernel, grid_for((KSPACE + 31) / 32), dim3(256), 0, E.stream, (const uint32_t *)S.d_koff.p, S.d_kbits.p);
+    UC_HIP(hipMemcpyAsync(&PP.n_entries, S.d_koff.p + KSPACE, 4, hipMemcpyDeviceToHost, E.stream));
+    UC_HIP(hipStreamSynchronize(E.stream));
+    UC_HIP(hipGetLastError());
+    PP.gpu_ms = E.timed_ms_end();
+    E.stats.n_index_entries += PP.n_entries;
+    E.stats.algorithmic_bytes[UC_ST_INDEX] += 6ull * PP.n_entries + 8ull * KSPACE;
+    E.stats.stage_seconds[UC_ST_INDEX] += t_index.seconds();
+}
+
+static dim3 sim_grid(uint64_t items) {
+    return dim3((uint32_t)std::min<uint64_t>(std::max<uint64_t>(1, (items + 4 * SIM_MIN_WAVE_POS - 1) / (4 * SIM_MIN_WAVE_POS)), SIM_MAX_BLOCKS));
+}
+
+// consumes the nd distinct k-mers; produces the index ranges ("runs") of their similar k-mers tagged with the k-mer's rank (d_drk / d_drv, n_druns of
+// them in buffers of drun_cap) and d_nsimk.  Returns 0, or the run count (estimated or exact) that exceeds DRUN_MAX: the super-batch has to be cut
+static uint64_t distinct_runs(Engine &E, PrefilterPass &PP, const SuperBatch &SB, uint32_t nd, uint64_t &n_druns, uint64_t &drun_cap) {
+    PrefilterScratch &S = *E.pre;
+    const uint32_t nqa = SB.end - SB.begin;
+    if (nqa > 1 && nd > (1u << 16)) {   // run-count estimate from every 64th distinct k-mer: cut the super-batch BEFORE the full enumeration
+        const uint32_t st = 64;
+        UC_HIP(hipMemsetAsync(S.d_counters.p + 3, 0, 32, E.stream));
+        UC_HIP(hipMemsetAsync(S.d_counters.p, 0, 8, E.stream));
+        hipLaunchKernelGGL(sim_runs_kernel, sim_grid((nd + st - 1) / st), dim3(256), 0, E.stream, E.ddb, PP.cfg, 0u, 0u, 0u, nd, S.d_koff.p, RunList{nullptr, nullptr, 0},
+                           S.d_counters.p, S.d_dk.p, (uint32_t *)nullptr, st, (const uint32_t *)S.d_kbits.p);
+        unsigned long long c5[5];
+        UC_HIP(hipMemcpyAsync(c5, S.d_counters.p, 40, hipMemcpyDeviceToHost, E.stream));
+        UC_HIP(hipStreamSynchronize(E.stream));
+        if ((double)c5[3] * st > 0.9 * (double)PP.DRUN_MAX) return (uint64_t)((double)c5[3] * st / 0.9);
+    }
+    n_druns = 0; drun_cap = S.d_drk.cap;
+    for (;;) {   // runs of the distinct k-mers, tagged with the k-mer's rank
+        drun_cap = std::min<uint64_t>(1ull << 32, std::max<uint64_t>(drun_cap, std::max<uint64_t>(1u << 20, std::min<uint64_t>(PP.DRUN_MAX, (uint64_t)nd * 16))));
+        S.d_drk.reserve(drun_cap); S.d_drv.reserve(drun_cap);
+        UC_HIP(hipMemsetAsync(S.d_counters.p + 3, 0, 32, E.stream));
+        UC_HIP(hipMemsetAsync(S.d_counters.p, 0, 8, E.stream));
+        const RunList rl{S.d_drk.p, S.d_drv.p, drun_cap};
+        hipLaunchKernelGGL(sim_runs_kernel, sim_grid(nd), dim3(256), 0, E.stream, E.ddb, PP.cfg, 0u, 0u, 0u, nd, S.d_koff.p, rl, S.d_counters.p, S.d_dk.p, S.d_nsimk.p, 1u,
+                           (const uint32_t *)S.d_kbits.p);
+        unsigned long long c5[5];
+        UC_HIP(hipMemcpyAsync(c5, S.d_counters.p, 40, hipMemcpyDeviceToHost, E.stream));
+        UC_HIP(hipStreamSynchronize(E.stream));
+        n_druns = c5[3];
+        if (n_druns > PP.DRUN_MAX && nqa > 1) return n_druns;
+        if (n_druns > drun_cap) {
+            if (n_druns >= (1ull << 32)) fail(UC_ERR_GENERIC, "%u distinct k-mers of query %u produce %llu index ranges", nd, SB.begin, (unsigned long long)n_druns);
+            drun_cap = n_druns;
+            UC_HIP(hipMemsetAsync(S.d_nsimk.p, 0, (size_t)std::max<uint32_t>(nd, 1) * 4, E.stream));
+            continue;
+        }
+        return 0;
+    }
+}
+
+enum class PlanStatus { planned, too_dense /* density limit exceeded (first super-batch only) */, too_many_runs /* over_runs says how many */ };
+struct PlanResult { PlanStatus status; uint64_t over_runs; };
+// ---- distinct mode, once per target chunk and query "super-batch" [sa, sb) (normally all queries; cut when the run lists
+//      of its distinct k-mers exceed DRUN_MAX, i.e. at high sensitivity): similar k-mers and index ranges of every
+//      DISTINCT query k-mer, then per query position the length and source of its run list and its k-mer hits; exact
+//      per-query totals for the batch plan ----
+// consumes the index and queries [sa, sb); produces SB and the sorted runs (d_drv2) with d_nr / d_src / d_cumr per position, which cut_batch expands
+static PlanResult plan_superbatch(Engine &E, PrefilterPass &PP, SuperBatch &SB, uint32_t sa, uint32_t sb) {
+    PrefilterScratch &S = *E.pre;
+    uint64_t plan_hits = 0;
+    SB.begin = sa; SB.end = sb;
+    SB.P0 = E.h_poff[sa]; SB.NP = E.h_poff[sb] - SB.P0;
+    const uint32_t NP = SB.NP, nqa = sb - sa;
+    Timer t_p;
+    E.timed_ms_begin();
+    S.d_qk.reserve((size_t)NP + 1); S.d_kflag.reserve((size_t)KSPACE + 1); S.d_kid.reserve((size_t)KSPACE + 1);
+    UC_HIP(hipMemsetAsync(S.d_kflag.p, 0, (size_t)KSPACE + 1, E.stream));
+    hipLaunchKernelGGL(query_kmer_kernel, grid_for(NP), dim3(256), 0, E.stream, E.ddb, PP.cfg, sa, sb, SB.P0, SB.P0 + NP, S.d_qk.p, S.d_kflag.p);
+    auto fin = rocprim::make_transform_iterator(S.d_kflag.p, FlagToU32());
+    rocprim_call(S.d_temp, [&](void *t, size_t &b) { return rocprim::exclusive_scan(t, b, fin, S.d_kid.p, 0u, (size_t)KSPACE + 1, rocprim::plus<uint32_t>(), E.stream); });
+    uint32_t nd = 0;                           // distinct k-mers of the super-batch: d_kid ranks every k-mer among them, d_dk lists them
+    UC_HIP(hipMemcpyAsync(&nd, S.d_kid.p + KSPACE, 4, hipMemcpyDeviceToHost, E.stream));
+    UC_HIP(hipStreamSynchronize(E.stream));
+    S.d_dk.reserve(std::max<uint32_t>(nd, 1)); S.d_nsimk.reserve(std::max<uint32_t>(nd, 1));
+    UC_HIP(hipMemsetAsync(S.d_nsimk.p, 0, (size_t)std::max<uint32_t>(nd, 1) * 4, E.stream));
+    hipLaunchKernelGGL(distinct_kmer_kernel, grid_for(KSPACE), dim3(256), 0, E.stream, S.d_kflag.p, S.d_kid.p, S.d_dk.p);
+    uint64_t n_druns = 0, drun_cap = 0;
+    if (const uint64_t over_runs = distinct_runs(E, PP, SB, nd, n_druns, drun_cap)) {
+        PP.gpu_ms += E.timed_ms_end();
+        PP.t_kmer += t_p.seconds();
+        return {PlanStatus::too_many_runs, over_runs};
+    }
+    unsigned dbits = 1;
+    while ((1ull << dbits) < nd) dbits++;
+    S.d_drk2.reserve(drun_cap); S.d_drv2.reserve(drun_cap);
+    if (n_druns)
+        rocprim_call(S.d_temp, [&](void *t, size_t &b) { return rocprim::radix_sort_pairs(t, b, S.d_drk.p, S.d_drk2.p, S.d_drv.p, S.d_drv2.p, (size_t)n_druns, 0u, dbits, E.stream); });
+    S.d_roff.reserve((size_t)nd + 1); S.d_rec.reserve(std::max<uint32_t>(nd, 1));
+    hipLaunchKernelGGL(rank_offsets_kernel, grid_for((uint64_t)nd + 1), dim3(256), 0, E.stream, S.d_drk2.p, (uint32_t)n_druns, nd, S.d_roff.p);
+    if (nd) hipLaunchKernelGGL(rank_rec_kernel, grid_for(nd), dim3(256), 0, E.stream, S.d_roff.p, S.d_drv2.p, S.d_nsimk.p, nd, S.d_rec.p);
+    // per position (one trailing zero element so that the exclusive sums end with the totals)
+    S.d_nr.reserve((size_t)NP + 1); S.d_src.reserve((size_t)NP + 1); S.d_ph.reserve((size_t)NP + 1);
+    S.d_cumh.reserve((size_t)NP + 1); S.d_cumr.reserve((size_t)NP + 1);
+    UC_HIP(hipMemsetAsync(S.d_counters.p, 0, 8, E.stream));
+    UC_HIP(hipMemsetAsync(S.d_nr.p + NP, 0, 4, E.stream));
+    UC_HIP(hipMemsetAsync(S.d_ph.p + NP, 0, 4, E.stream));
+    hipLaunchKernelGGL(position_runs_kernel, grid_for(NP), dim3(256), 0, E.stream, S.d_qk.p, NP, S.d_kid.p, S.d_rec.p, S.d_nr.p, S.d_src.p, S.d_ph.p, S.d_counters.p);
+    auto hin = rocprim::make_transform_iterator(S.d_ph.p, WidenU32());
+    auto rin = rocprim::make_transform_iterator(S.d_nr.p, WidenU32());
+    rocprim_call(S.d_temp, [&](void *t, size_t &b) { return rocprim::exclusive_scan(t, b, hin, S.d_cumh.p, (uint64_t)0, (size_t)NP + 1, rocprim::plus<uint64_t>(), E.stream); });
+    rocprim_call(S.d_temp, [&](void *t, size_t &b) { return rocprim::exclusive_scan(t, b, rin, S.d_cumr.p, (uint64_t)0, (size_t)NP + 1, rocprim::plus<uint64_t>(), E.stream); });
+    S.d_qh.reserve(nqa); S.d_qrn.reserve(nqa);
+    hipLaunchKernelGGL(query_totals_kernel, grid_for(nqa), dim3(256), 0, E.stream, E.ddb.off, sa, nqa, SB.P0, S.d_cumh.p, S.d_cumr.p, S.d_qh.p, S.d_qrn.p);
+    SB.h_qh.resize(nqa); SB.h_qr.resize(nqa);
+    unsigned long long c0 = 0;
+    UC_HIP(hipMemcpyAsync(SB.h_qh.data(), S.d_qh.p, (size_t)nqa * 8, hipMemcpyDeviceToHost, E.stream));
+    UC_HIP(hipMemcpyAsync(SB.h_qr.data(), S.d_qrn.p, (size_t)nqa * 8, hipMemcpyDeviceToHost, E.stream));
+    UC_HIP(hipMemcpyAsync(&c0, S.d_counters.p, 8, hipMemcpyDeviceToHost, E.stream));
+    UC_HIP(hipStreamSynchronize(E.stream));
+    for (uint32_t i = 0; i < nqa; i++) plan_hits += SB.h_qh[i];
+    SB.hit_cap = plan_hits > 16 * PP.HIT_CAP ? PP.HIT_CAP_BIG : PP.HIT_CAP;
+    PP.gpu_ms += E.timed_ms_end();
+    PP.t_kmer += t_p.seconds();
+    if (sa == PP.qbegin) {
+        if (PP.density_out) *PP.density_out = (double)plan_hits / std::max<uint32_t>(1, NP);
+        if (PP.density_limit > 0 && E.p.min_diag_hits >= 2 && PP.tend - PP.tbegin > 1 && (double)plan_hits / std::max<uint32_t>(1, NP) > PP.density_limit)
+            return {PlanStatus::too_dense, 0};
+    }
+    if (PP.count_sims) E.stats.n_sim_kmers += c0;
+    return {PlanStatus::planned, 0};
+}
+
+// consumes the first query qa without a plan; produces the plan of the next super-batch, as large as the run lists allow.  false: the chunk is too dense
+static bool choose_superbatch(Engine &E, PrefilterPass &PP, SuperBatch &SB, uint32_t qa) {
+    for (;;) {
+        const uint32_t left = PP.qend - qa;
+        const uint32_t sb = SB.frac >= 1.0 ? PP.qend : qa + std::max<uint32_t>(1, std::min<uint32_t>(left, (uint32_t)(left * SB.frac)));
+        const PlanResult r = plan_superbatch(E, PP, SB, qa, sb);
+        if (r.status == PlanStatus::too_dense) {   // undo what this abandoned attempt counted
+            E.stats.n_index_entries -= PP.n_entries;
+            E.stats.algorithmic_bytes[UC_ST_INDEX] -= 6ull * PP.n_entries + 8ull * KSPACE;
+            E.stats.prefilter_kernel_ms += PP.gpu_ms;
+            return false;
+        }
+        if (r.status == PlanStatus::too_many_runs) {   // distinct k-mers grow sublinearly with the queries: cut a little deeper than proportionally
+            SB.frac = (double)(sb - qa) / left * 0.8 * (double)PP.DRUN_MAX / (double)r.over_runs;
+            continue;
+        }
+        if (SB.frac < 1.0) SB.frac = std::min(1.0, (double)(sb - qa) / std::max<uint32_t>(1, PP.qend - sb));   // the same number of queries again
+        return true;
+    }
+}
+
+// consumes the plan of SB and the first query qa; produces the exact batch [qa, qb) and its runs per query position (d_rpidx2 / d_rval2)
+static QueryBatch cut_batch(Engine &E, PrefilterPass &PP, const SuperBatch &SB, uint32_t qa) {
+    PrefilterScratch &S = *E.pre;
+    QueryBatch B;
+    B.qa = B.qb = qa;
+    uint64_t mirror_hits = 0;
+    // exact plan: as many queries as fit the key and run buffers (a single query may exceed them and takes the wide path)
+    while (B.qb < SB.end && B.qb - qa < (1u << 23) - 1) {
+        const uint64_t h = SB.h_qh[B.qb - SB.begin], r = SB.h_qr[B.qb - SB.begin];
+        if (B.qb > qa && (B.total_hits + h > SB.hit_cap || B.n_runs + r > RUN_MAX)) break;
+        B.total_hits += h; B.n_runs += r;
+        if (B.qb >= PP.mirror_q0) mirror_hits += h;       // these hits stand for the hits of the pairs the other way round as well
+        B.qb++;
+    }
+    if (B.n_runs >= (1ull << 32)) fail(UC_ERR_GENERIC, "query %u alone produces %llu index ranges", qa, (unsigned long long)B.n_runs);
+    B.qp0 = E.h_poff[qa]; B.qp1 = E.h_poff[B.qb]; B.nq_res = B.qp1 - B.qp0;
+    PP.run_cap = std::max<uint64_t>(PP.run_cap, B.n_runs);
+    S.d_rpidx2.reserve(PP.run_cap); S.d_rval2.reserve(PP.run_cap);
+    UC_HIP(hipMemsetAsync(S.d_counters.p + 3, 0, 32, E.stream));   // run cursor, batch hits, key cursor, candidate cursor
+    if (B.n_runs)
+        hipLaunchKernelGGL(position_expand_kernel, grid_for(B.nq_res), dim3(256), 0, E.stream, B.qp0 - SB.P0, B.qp1 - SB.P0, S.d_nr.p, S.d_src.p, S.d_cumr.p, S.d_drv2.p,
+                           S.d_rpidx2.p, S.d_rval2.p);
+    if (B.total_hits > (1ull << 34)) fail(UC_ERR_GENERIC, "query %u alone produces %llu k-mer hits", qa, (unsigned long long)B.total_hits);
+    PP.n_hits_total += B.total_hits + mirror_hits;
+    unsigned qbits = 1;
+    while ((1u << qbits) < B.qb - qa) qbits++;
+    B.kbits = (unsigned)(PP.fmt.dbits + PP.fmt.tbits) + qbits;
+    return B;
+}
+
+// n > 0 counts (0/1 flags, survivors per query) -> their exclusive scan in u64 positions (where each entry's share goes) -> the total (one host
+// synchronisation, the u64 form of uc_align.hip's compact(); it also fetches the u32 at `also` for a caller that has one more value to read)
+static uint64_t compact_u64(Engine &E, DevBuf<char> &tmp, uint32_t *cnt, uint64_t *pos, uint64_t n, const uint32_t *also = nullptr, uint32_t *also_out = nullptr) {
+    auto in = rocprim::make_transform_iterator(cnt, WidenU32());
+    rocprim_call(tmp, [&](void *t, size_t &b) { return rocprim::exclusive_scan(t, b, in, pos, (uint64_t)0, (size_t)n, rocprim::plus<uint64_t>(), E.stream); });
+    uint64_t lp = 0; uint32_t lc = 0;
+    UC_HIP(hipMemcpyAsync(&lp, pos + (n - 1), 8, hipMemcpyDeviceToHost, E.stream));
+    UC_HIP(hipMemcpyAsync(&lc, cnt + (n - 1), 4, hipMemcpyDeviceToHost, E.stream));
+    if (also) UC_HIP(hipMemcpyAsync(also_out, also, 4, hipMemcpyDeviceToHost, E.stream));
+    UC_HIP(hipStreamSynchronize(E.stream));
+    return lp + lc;
+}
+
+// pass 2 with the double-hit filter.  consumes the batch's runs; produces its keys that survive filter_kernel<C>, dense and sorted (B.sorted / n_sort)
+static void expand_keys_filtered(Engine &E, PrefilterPass &PP, QueryBatch &B) {
+    PrefilterScratch &S = *E.pre;
+    const KeyFmt &fmt = PP.fmt;
+    const uint32_t qa = B.qa, qp0 = B.qp0, nq = B.qb - B.qa;
+    S.d_qbase.reserve(nq); S.d_qsurv.reserve(nq); S.d_soff.reserve((size_t)nq + 1);
+    // the query regions hold (target, diagonal) keys: u32 in compact mode (half of the u64 buffer stays unused),
+    // every region rounded up to KPT keys
+    const uint64_t region_cap = B.total_hits + (uint64_t)KPT * nq;
+    S.d_keys.reserve(fmt.compact ? region_cap : 2 * region_cap);       // regions + survivor area of the same size
+    S.d_qr.reserve((size_t)nq + 1);
+    hipLaunchKernelGGL(run_range_kernel, grid_for((uint64_t)nq + 1), dim3(256), 0, E.stream, E.ddb, qa, nq, qp0, S.d_rpidx2.p, B.n_runs, S.d_qr.p);
+    S.d_okey.reserve(nq); S.d_okey2.reserve(nq); S.d_oidx.reserve(nq); S.d_order.reserve(nq);
+    hipLaunchKernelGGL(run_order_key_kernel, grid_for(nq), dim3(256), 0, E.stream, nq, S.d_qr.p, S.d_okey.p, S.d_oidx.p);
+    rocprim_call(S.d_temp, [&](void *t, size_t &b) { return rocprim::radix_sort_pairs(t, b, S.d_okey.p, S.d_okey2.p, S.d_oidx.p, S.d_order.p, (size_t)nq, 0u, 32u, E.stream); });
+    auto launch = [&](auto kern) {
+        static PerDeviceOnce once[2];
+        once[fmt.compact ? 1 : 0]([&] { UC_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)filter_lds(FILTER_RPT))); });
+        hipLaunchKernelGGL(kern, dim3(nq), dim3(FT), filter_lds(FILTER_RPT), E.stream, E.ddb, qa, qp0, S.d_rpidx2.p, S.d_rval2.p, S.d_qr.p, S.d_order.p, PP.ent_p, fmt,
+                           S.d_counters.p + 5, (void *)S.d_keys.p, region_cap, S.d_qbase.p, S.d_qsurv.p);
+    };
+    if (fmt.compact) launch(filter_kernel<true>);
+    else launch(filter_kernel<false>);
+    const uint64_t n_sort = compact_u64(E, S.d_temp, S.d_qsurv.p, S.d_soff.p, nq);
+    if (n_sort) {
+        S.d_keys2.reserve(2 * n_sort);              // dense keys + the sort's output
+        hipLaunchKernelGGL(fmt.compact ? compact_kernel<true> : compact_kernel<false>, dim3(std::min<uint32_t>(nq, 65535u)), dim3(256), 0, E.stream,
+                           (const void *)S.d_keys.p, S.d_qbase.p, S.d_qsurv.p, S.d_soff.p, nq, fmt, S.d_keys2.p);
+        rocprim_call(S.d_temp, [&](void *t, size_t &b) { return rocprim::radix_sort_keys(t, b, S.d_keys2.p, S.d_keys2.p + n_sort, (size_t)n_sort, 0u, B.kbits, E.stream); });
+    }
+    B.sorted = S.d_keys2.p + n_sort; B.n_sort = n_sort;
+    E.stats.n_filtered_hits += n_sort;
+}
+
+// pass 2 without the filter (min_diag_hits < 2, or a single query beyond 2^32 hits).  consumes the batch's runs; produces all its keys, sorted
+static void expand_keys_plain(Engine &E, PrefilterPass &PP, QueryBatch &B) {
+    PrefilterScratch &S = *E.pre;
+    S.d_keys.reserve(B.total_hits); S.d_keys2.reserve(B.total_hits);
+    const RunList rl{S.d_rpidx2.p, S.d_rval2.p, PP.run_cap};
+    hipLaunchKernelGGL(expand_kernel, grid_for(B.n_runs), dim3(256), 0, E.stream, E.ddb, B.qa, B.qb, B.qp0, rl, B.n_runs, PP.ent_p, PP.fmt,
+                       S.d_counters.p + 5, S.d_keys.p, B.total_hits);
+    rocprim_call(S.d_temp, [&](void *t, size_t &b) { return rocprim::radix_sort_keys(t, b, S.d_keys.p, S.d_keys2.p, (size_t)B.total_hits, 0u, B.kbits, E.stream); });
+    B.sorted = S.d_keys2.p; B.n_sort = B.total_hits;
+    E.stats.n_filtered_hits += B.n_sort;
+}
+
+// consumes the batch's sorted keys; produces its candidates (d_cq / d_ct / d_cd: query, target, best diagonal; mirrored pairs twice) and their number
+static uint64_t select_diagonals(Engine &E, PrefilterPass &PP, const QueryBatch &B) {
+    PrefilterScratch &S = *E.pre;
+    PP.cand_cap = std::max<uint64_t>(PP.cand_cap, std::max<uint64_t>(1u << 20, B.total_hits / 32));
+    for (;;) {
+        S.d_cq.reserve(PP.cand_cap); S.d_ct.reserve(PP.cand_cap); S.d_cd.reserve(PP.cand_cap);
+        UC_HIP(hipMemsetAsync(S.d_counters.p + 6, 0, 8, E.stream));
+        if (B.n_sort) {
+            S.d_wflag.reserve((B.n_sort + 63) / 64 + 64);
+            hipLaunchKernelGGL(diag_select_kernel, grid_for(B.n_sort), dim3(256), 0, E.stream, B.sorted, B.n_sort, E.p.min_diag_hits, PP.fmt, B.qa,
+                               S.d_counters.p + 6, PP.cand_cap, S.d_cq.p, S.d_ct.p, S.d_cd.p, PP.mirror_q0, S.d_wflag.p);
+            hipLaunchKernelGGL(diag_long_kernel, grid_for((B.n_sort + 63) / 64), dim3(256), 0, E.stream, B.sorted, B.n_sort, E.p.min_diag_hits, PP.fmt, B.qa,
+                               S.d_counters.p + 6, PP.cand_cap, S.d_cq.p, S.d_ct.p, S.d_cd.p, PP.mirror_q0, (const uint8_t *)S.d_wflag.p);
+        }
+        unsigned long long nc = 0;
+        UC_HIP(hipMemcpyAsync(&nc, S.d_counters.p + 6, 8, hipMemcpyDeviceToHost, E.stream));
+        UC_HIP(hipStreamSynchronize(E.stream));
+        if (nc <= PP.cand_cap) return nc;
+        PP.cand_cap = nc;     // rare: more candidates than provisioned, run the selection again
+    }
+}
+
+// E3.  consumes the n_cand candidates; produces their ungapped scores (d_score) and the overlap residue count in d_counters[2]
+static void rescore_ungapped(Engine &E, PrefilterPass &PP, uint64_t n_cand) {
+    PrefilterScratch &S = *E.pre;
+    Timer t_u;
+    E.timed_ms_begin();
+    S.d_score.reserve(n_cand);
+    launch_ungapped(E.ddb, n_cand, S.d_cq.p, S.d_ct.p, S.d_cd.p, S.d_score.p, S.d_counters.p + 2, E.stream);
+    UC_HIP(hipGetLastError());
+    PP.gpu_ms += E.timed_ms_end();
+    PP.t_ung += t_u.seconds();
+}
+
+// E4.  consumes the scored candidates; produces the batch's hits (score >= min_ungapped, rank < max_seqs in their query's run) appended to the device lists
+static void select_and_append(Engine &E, PrefilterPass &PP, uint64_t n_cand) {
+    PrefilterScratch &S = *E.pre;
+    Timer t_s;
+    E.timed_ms_begin();
+    S.d_skey.reserve(n_cand); S.d_skey2.reserve(n_cand); S.d_cd2.reserve(n_cand);
+    UC_HIP(hipMemsetAsync(S.d_counters.p + 1, 0, 8, E.stream));
+    hipLaunchKernelGGL(select_key_kernel, grid_for(n_cand), dim3(256), 0, E.stream, n_cand, S.d_cq.p, S.d_ct.p, S.d_score.p, E.p.min_ungapped, S.d_skey.p, S.d_counters.p + 1);
+    rocprim_call(S.d_temp, [&](void *t, size_t &b) { return rocprim::radix_sort_pairs(t, b, S.d_skey.p, S.d_skey2.p, S.d_cd.p, S.d_cd2.p, (size_t)n_cand, 0u, 64u, E.stream); });
+    unsigned long long kept = 0;
+    UC_HIP(hipMemcpyAsync(&kept, S.d_counters.p + 1, 8, hipMemcpyDeviceToHost, E.stream));
+    UC_HIP(hipStreamSynchronize(E.stream));
+    if (kept) {   // rank inside each query's run, keep the first max_seqs, append to the device hit lists
+        S.d_flag.reserve(kept); S.d_pos.reserve(kept);
+        hipLaunchKernelGGL(rank_flag_kernel, grid_for(kept), dim3(256), 0, E.stream, S.d_skey2.p, (uint64_t)kept, (uint32_t)E.p.max_seqs, S.d_flag.p);
+        const uint64_t add = compact_u64(E, S.d_temp, S.d_flag.p, S.d_pos.p, kept), n_hits = E.n_hits;
+        E.d_hq.grow_preserve(n_hits + add, n_hits, E.stream); E.d_ht.grow_preserve(n_hits + add, n_hits, E.stream);
+        E.d_hs.grow_preserve(n_hits + add, n_hits, E.stream); E.d_hd.grow_preserve(n_hits + add, n_hits, E.stream);
+        hipLaunchKernelGGL(hit_scatter_kernel, grid_for(kept), dim3(256), 0, E.stream, S.d_skey2.p, S.d_cd2.p, (uint64_t)kept, S.d_flag.p, S.d_pos.p,
+                           E.d_hq.p + n_hits, E.d_ht.p + n_hits, E.d_hs.p + n_hits, E.d_hd.p + n_hits);
+        E.n_hits += add;
+    }
+    UC_HIP(hipGetLastError());
+    PP.gpu_ms += E.timed_ms_end();
+    PP.t_sel += t_s.seconds();
+}
+
+// consumes the totals of the chunk; produces the per-query counts / offsets (unless the lists leave ungrouped) and the chunk's share of the statistics
+static void finish_chunk(Engine &E, const PrefilterPass &PP, uint64_t sims_before) {
+    if (PP.mirror_q0 == UINT32_MAX) E.finish_hit_lists("prefilter");
+    uc_stats &stats = E.stats;
+    unsigned long long ovl = 0;
+    UC_HIP(hipMemcpy(&ovl, E.pre->d_counters.p + 2, 8, hipMemcpyDeviceToHost));
+    stats.n_kmer_hits += PP.n_hits_total;
+    stats.n_candidates += PP.n_cand_total;
+    stats.algorithmic_bytes[UC_ST_KMER] += 8ull * (stats.n_sim_kmers - sims_before) + 6ull * PP.n_hits_total + 8ull * PP.n_cand_total;
+    stats.algorithmic_bytes[UC_ST_UNGAPPED] += ovl + 16ull * PP.n_cand_total;   // (overlap + 16) B per candidate, SURVEY.md 8(d)
+    stats.algorithmic_bytes[UC_ST_SELECT] += 16ull * PP.n_cand_total;
+    stats.stage_seconds[UC_ST_KMER] += PP.t_kmer;
+    stats.stage_seconds[UC_ST_UNGAPPED] += PP.t_ung;
+    stats.stage_seconds[UC_ST_SELECT] += PP.t_sel;
+    stats.prefilter_kernel_ms += PP.gpu_ms;
+}
+
+// one target chunk [tbegin, tend) against queries [qbegin, qend).  Returns false (nothing installed) if density_limit > 0 and the first query batch
+// exceeds it; *density_out = k-mer hits per query residue of that batch.  mirror_q0 != UINT32_MAX: symmetric pass (diag_select_kernel): the lists
+// leave this function ungrouped, the caller merges them
+static bool prefilter_one(Engine &E, uint32_t tbegin, uint32_t tend, uint32_t qbegin, uint32_t qend, bool count_sims, double density_limit,
+                          double *density_out, uint32_t mirror_q0) {
+    UC_HIP(hipSetDevice(E.device));
+    const uint32_t n = E.hdb.n;
+    PrefilterPass PP;
+    for (int m = 0; m < K; m++) PP.cfg.koff[m] = E.p.koff[m];
+    PP.cfg.span = E.p.span; PP.cfg.thr = E.p.kmer_thr;
+    PP.tbegin = tbegin; PP.tend = tend; PP.qbegin = qbegin; PP.qend = qend; PP.mirror_q0 = mirror_q0;
+    PP.count_sims = count_sims; PP.density_limit = density_limit; PP.density_out = density_out;
+    // keys per batch (the filter's regions hold < 2^32 keys).  1.5 G keys = 12 GiB of regions: a one-shot `foldseek cluster` process
+    // pays for every byte it allocates (34 GiB of regions at 3.75 G keys: 5.2 s from process start to clust.tsv at configs[1]
+    // instead of 1.25 s), and a resident engine loses nothing measurable (681 vs 681 ms per step; UC_HIT_CAP overrides)
+    const char *hc = getenv("UC_HIT_CAP");
+    PP.HIT_CAP = hc ? std::max<uint64_t>(1u << 20, strtoull(hc, nullptr, 10)) : (3ull << 29);
+    // ... unless the chunk has so many hits that the batches would run into the hundreds (2.5 M sequences: 1.5e12 hits): then the
+    // per-batch costs outweigh the allocation and the regions take 3.75 G keys (30 GiB)
+    PP.HIT_CAP_BIG = hc ? PP.HIT_CAP : (15ull << 28);
+    const char *dm = getenv("UC_DRUN_MAX");
+    PP.DRUN_MAX = dm ? std::max<uint64_t>(1, strtoull(dm, nullptr, 10)) : (1ull << 31);   // 24 GiB + 24 GiB sort double buffer (env: tests)
+
+    E.hit_cnt.assign(n, 0);
+    E.hit_off.assign((size_t)n + 1, 0);
+    E.n_hits = 0;
+    E.alns_valid = false;
+    E.clear_edges();
+    const uint64_t sims_before = E.stats.n_sim_kmers;   // stats accumulate over calls: the byte count below needs THIS call's share
+
+    if (n > (1u << 24)) fail(UC_ERR_GENERIC, "prefilter: %u sequences exceed the 2^24 limit of the hit keys", n);
+    // counters: [0] similar k-mers, [1] kept candidates, [2] ungapped overlap residues, [3] run cursor,
+    //           [4] k-mer hits of the batch, [5] key cursor, [6] candidate cursor
+    if (!E.pre) E.pre = ParkedScratch<PrefilterScratch>::take_or_new(E.device);
+    E.pre->d_counters.reserve(8);
+    UC_HIP(hipMemsetAsync(E.pre->d_counters.p, 0, 64, E.stream));
+
+    build_index(E, PP);                        // E1: index of targets [tbegin, tend)
+    // E2-E4 over query batches
+    SuperBatch SB;
+    SB.begin = SB.end = qbegin;                // nothing planned yet
+    for (uint32_t qa = qbegin; qa < qend;) {
+        if (qa >= SB.end && !choose_superbatch(E, PP, SB, qa)) return false;
+        Timer t_b;
+        E.timed_ms_begin();
+        QueryBatch B = cut_batch(E, PP, SB, qa);
+        uint64_t n_cand = 0;
+        if (B.total_hits) {
+            // pass 2: expand runs into keys (filtered to double hits when the rule allows), sort them
+            if (E.p.min_diag_hits >= 2 && B.total_hits < (1ull << 32)) expand_keys_filtered(E, PP, B);
+            else expand_keys_plain(E, PP, B);
+            n_cand = select_diagonals(E, PP, B);
+        }
+        UC_HIP(hipGetLastError());
+        PP.gpu_ms += E.timed_ms_end();
+        PP.t_kmer += t_b.seconds();
+        PP.n_cand_total += n_cand;
+        if (n_cand) {
+            rescore_ungapped(E, PP, n_cand);
+            select_and_append(E, PP, n_cand);
+        }
+        qa = B.qb;
+    }
+    finish_chunk(E, PP, sims_before);
+    return true;
+}
+
+// ---- E1-E4 for a target range ---------------------------------------------------------------------------------
+// The chunks of a range, one prefilter_one pass each, their lists merged into a running top-M accumulator; false: the first chunk was too dense
+// (density says by how much), nothing is installed.
+// All-vs-all over several chunks under a symmetric matrix (triangle): the k-mer hit relation is symmetric, so the chunk x chunk grid needs only its
+// upper triangle.  The pass over chunk c matches the queries FROM chunk c onwards; the pairs (query behind the chunk, target in it) also
+// yield the candidates of the pairs the other way round (diag_select_kernel), i.e. what the skipped passes (query in c, target chunk
+// behind it) would have found: ~(1 + 1/C) / 2 of the k-mer hits are expanded.  The lists of a pass come back ungrouped and are merged
+// like the chunk lists always were (lossless: per-pass top-M of disjoint candidate sets).  UC_PREFILTER_SYMMETRIC=0: every pass matches all queries.
+static bool prefilter_chunks(Engine &E, const std::vector<std::pair<uint32_t, uint32_t>> &chunks, uint32_t qbegin, uint32_t qend, bool triangle,
+                             bool mirror_all, double limit, double *density) {
+    // (Measured and reverted in r04: concatenating the per-pass lists and merging ONCE at the end — 1.5-2 G records in one sort instead of a
+    // running top-M accumulator of <= max_seqs x queries — made configs[2] SLOWER, 35.7 -> 39.3 s per pass: the single merge needs ~64 B per
+    // record of work buffers at the moment the key regions are largest.  The accumulator is merged after every pass.)
+    // (r06: the accumulator / pass arrays live in the scratch set - up to 4 x 7 GB at configs[2] were allocated and freed by every call)
+    if (!E.pre) E.pre = ParkedScratch<PrefilterScratch>::take_or_new(E.device);
+    PrefilterScratch &S = *E.pre;
+    const auto swap_acc = [&] { swap_hits(E, S.acc_q, S.acc_t, S.acc_s, S.acc_d); };
+    uint64_t acc_n = 0;
+    bool installed = false;       // the last pass's merge leaves its result installed in the engine: no second merge of the accumulator
+    for (size_t c = 0; c < chunks.size(); c++) {
+        const bool mir = mirror_all || (triangle && c + 1 < chunks.size());       // (the last chunk has no queries behind it: a plain pass over its own queries)
+        if (!prefilter_one(E, chunks[c].first, chunks[c].second, triangle ? chunks[c].first : qbegin, qend, c == 0, c == 0 ? limit : 0.0, density,
+                           mirror_all ? qbegin : mir ? chunks[c].second : UINT32_MAX))
+            return false;
+        if (!mir && (c == 0 || acc_n == 0)) {
+            swap_acc();
+            acc_n = E.n_hits;
+        } else if (E.n_hits) {       // (a mirrored pass always comes here: its lists are ungrouped)
+            // the pass's lists leave the engine (swap, no copy), the merge installs accumulator + pass in their place.  The accumulator is in key
+            // order, a plain pass's lists are too: only a mirrored pass's records are sorted before the two runs are merged (merge_hits_dev)
+            const uint64_t n_pass = E.n_hits;
+            swap_hits(E, S.pass_q, S.pass_t, S.pass_s, S.pass_d);
+            acc_n = E.merge_hits_dev(acc_n, S.acc_q.p, S.acc_t.p, S.acc_s.p, S.acc_d.p, n_pass, S.pass_q.p, S.pass_t.p, S.pass_s.p, S.pass_d.p, /*sorted2=*/!mir, 0, 1);      // merge + truncate to max_seqs
+            if (c + 1 == chunks.size()) installed = true;
+            else swap_acc();
+        }
+    }
+    // install the accumulated lists (also rebuilds the per-query counts) unless the last merge already did
+    if (!installed) E.merge_hits_dev(acc_n, S.acc_q.p, S.acc_t.p, S.acc_s.p, S.acc_d.p, 0, nullptr, nullptr, nullptr, nullptr, true, 0, 1);     // (in key order already: counts only)
+    return true;
+}
+
+// Large ranges are processed as several index chunks whose per-query top-M lists are
 // merged on the device (lossless, same argument as the multi-GPU shards): the double-hit filter keeps one query's
 // (target, diagonal) hashes in 2 x 2^19 LDS bits, which only works while a query has well under ~500 k k-mer hits,
 // i.e. up to ~100 M target residues per chunk at default sensitivity (at 760 M residues in one chunk 75 % of the
 // hits survived the filter and the key sort took 2/3 of the run).
-void Engine::prefilter(uint32_t tbegin, uint32_t tend, uint32_t qbegin, uint32_t qend) { prefilter_impl(tbegin, tend, qbegin, qend, false); }
+// (mirror_all — prefilter_cells only: every query lies outside the shard and yields the pair the other way round as well; the lists come
+// back ungrouped and are merged by the caller)
+static void prefilter_impl(Engine &E, uint32_t tbegin, uint32_t tend, uint32_t qbegin, uint32_t qend, bool mirror_all) {
+    Engine::PressureScope ps(E, 0);
+    if (!E.have_db) fail(UC_ERR_ARGS, "no database loaded");
+    if (tbegin > tend || tend > E.hdb.n) fail(UC_ERR_ARGS, "prefilter: bad target range");
+    if (qend == UINT32_MAX) qend = E.hdb.n;
+    if (qbegin > qend || qend > E.hdb.n) fail(UC_ERR_ARGS, "prefilter: bad query range");
+    uint64_t chunk_res = E.prefilter_chunk_residues;
+    if (const char *ev = getenv("UC_PREFILTER_CHUNK_RES")) chunk_res = std::max<uint64_t>(1, strtoull(ev, nullptr, 10));
+    const char *sym = getenv("UC_PREFILTER_SYMMETRIC");
+    const bool symmetric = E.p.mat_symmetric && !(sym && atoi(sym) == 0);
+    // The chunk size that keeps a query's hits inside the LDS filter depends on how many k-mer hits a target residue
+    // attracts, i.e. on the sensitivity (-s 7.5 gives ~30x the hits of the default 4): prefilter_one measures the density
+    // (k-mer hits per query residue) of its first batch and gives up before expanding anything if the chunk is too dense;
+    // the range is then re-cut into proportionally smaller chunks (one wasted enumeration pass).
+    const double DENSITY_LIMIT = 400.0;   // hits per query residue and chunk (C2 whole DB at -s 4: 124)
+    for (int attempt = 0;; attempt++) {
+        std::vector<std::pair<uint32_t, uint32_t>> chunks;
+        for (uint32_t b = tbegin; b < tend;) {
+            uint32_t e = b;
+            uint64_t res = 0;
+            while (e < tend && (e == b || res + E.h_len[e] <= chunk_res)) res += E.h_len[e++];
+            chunks.emplace_back(b, e);
+            b = e;
+        }
+        double density = 0;
+        const double limit = attempt < 6 ? DENSITY_LIMIT : 0.0;      // after 6 re-cuts: run with what we have
+        const bool triangle = chunks.size() > 1 && tbegin == qbegin && tend == qend && symmetric;
+        const bool ok = chunks.size() <= 1 ? prefilter_one(E, tbegin, tend, qbegin, qend, true, limit, &density, mirror_all ? qbegin : UINT32_MAX)
+                                           : prefilter_chunks(E, chunks, qbegin, qend, triangle, mirror_all, limit, &density);
+        if (ok) {
+            E.stats.n_prefilter_hits += E.n_hits;
+            if (chunks.size() > 1 || !mirror_all) release_scratch_for_gapped_stage(E);
+            return;
+        }
+        // too dense: smaller chunks, proportionally (and a little more)
+        const uint64_t cur = std::min<uint64_t>(chunk_res, std::max<uint64_t>(1, (uint64_t)E.h_poff[chunks[0].second] - E.h_poff[chunks[0].first]));
+        chunk_res = std::max<uint64_t>(1u << 16, (uint64_t)((double)cur * DENSITY_LIMIT / density * 0.75));
+        logf(3, "unicore-cluster: prefilter: %.0f k-mer hits per query residue in a chunk of %llu residues; re-cutting the targets into chunks of %llu\n",
+             density, (unsigned long long)cur, (unsigned long long)chunk_res);
+    }
+}
+
+void Engine::prefilter(uint32_t tbegin, uint32_t tend, uint32_t qbegin, uint32_t qend) { prefilter_impl(*this, tbegin, tend, qbegin, qend, false); }
 
 // A rank of a symmetric N-rank pass: the shard's own block (with its inner triangle if it spans several chunks) and one mirrored block per other
 // query range; the lists of the blocks (disjoint candidate sets, each truncated to its own top-M) are concatenated and merged once.
@@ -1408,551 +1980,27 @@ void Engine::prefilter_cells(uint32_t tbegin, uint32_t tend, const std::vector<s
         if (!n_hits) return;
         const uint64_t tot = cat_n + n_hits;
         cq.grow_preserve(tot, cat_n, stream); ct.grow_preserve(tot, cat_n, stream); cs.grow_preserve(tot, cat_n, stream); cd.grow_preserve(tot, cat_n, stream);
-        UC_HIP(hipMemcpyAsync(cq.p + cat_n, d_hq.p, n_hits * 4, hipMemcpyDeviceToDevice, stream));
-        UC_HIP(hipMemcpyAsync(ct.p + cat_n, d_ht.p, n_hits * 4, hipMemcpyDeviceToDevice, stream));
-        UC_HIP(hipMemcpyAsync(cs.p + cat_n, d_hs.p, n_hits * 4, hipMemcpyDeviceToDevice, stream));
-        UC_HIP(hipMemcpyAsync(cd.p + cat_n, d_hd.p, n_hits * 4, hipMemcpyDeviceToDevice, stream));
-        UC_HIP(hipStreamSynchronize(stream));
+        copy_hits_dev(*this, cq.p + cat_n, ct.p + cat_n, cs.p + cat_n, cd.p + cat_n);
         cat_n = tot;
     };
     const uint64_t before = stats.n_prefilter_hits;
-    prefilter_impl(tbegin, tend, tbegin, tend, false);
+    prefilter_impl(*this, tbegin, tend, tbegin, tend, false);
     take();
     for (const auto &r : others) {
         if (r.first >= r.second) continue;
         if (r.first < tend && r.second > tbegin) fail(UC_ERR_GENERIC, "prefilter_cells: a mirrored query range overlaps the target shard");
-        prefilter_impl(tbegin, tend, r.first, r.second, true);
+        prefilter_impl(*this, tbegin, tend, r.first, r.second, true);
         take();
     }
     const uint64_t kept = import_hits_dev(cat_n, cq.p, ct.p, cs.p, cd.p, 0, 1);
     stats.n_prefilter_hits = before + kept;
-    if (pre) pre->release_bytes(scratch_release_target(p.min_seq_id > 0.0f || p.want_tb, n_hits, pre->bytes(), aln != nullptr && (double)last_align_hits >= 0.9 * (double)n_hits));
-}
-
-void Engine::prefilter_impl(uint32_t tbegin, uint32_t tend, uint32_t qbegin, uint32_t qend, bool mirror_all) {
-    PressureScope ps(*this, 0);
-    if (!have_db) fail(UC_ERR_ARGS, "no database loaded");
-    if (tbegin > tend || tend > hdb.n) fail(UC_ERR_ARGS, "prefilter: bad target range");
-    if (qend == UINT32_MAX) qend = hdb.n;
-    if (qbegin > qend || qend > hdb.n) fail(UC_ERR_ARGS, "prefilter: bad query range");
-    uint64_t chunk_res = prefilter_chunk_residues;
-    if (const char *ev = getenv("UC_PREFILTER_CHUNK_RES")) chunk_res = std::max<uint64_t>(1, strtoull(ev, nullptr, 10));
-    // The chunk size that keeps a query's hits inside the LDS filter depends on how many k-mer hits a target residue
-    // attracts, i.e. on the sensitivity (-s 7.5 gives ~30x the hits of the default 4): prefilter_one measures the density
-    // (k-mer hits per query residue) of its first batch and gives up before expanding anything if the chunk is too dense;
-    // the range is then re-cut into proportionally smaller chunks (one wasted enumeration pass).
-    const double DENSITY_LIMIT = 400.0;   // hits per query residue and chunk (C2 whole DB at -s 4: 124)
-    for (int attempt = 0;; attempt++) {
-        std::vector<std::pair<uint32_t, uint32_t>> chunks;
-        for (uint32_t b = tbegin; b < tend;) {
-            uint32_t e = b;
-            uint64_t res = 0;
-            while (e < tend && (e == b || res + h_len[e] <= chunk_res)) res += h_len[e++];
-            chunks.emplace_back(b, e);
-            b = e;
-        }
-        double density = 0;
-        const double limit = attempt < 6 ? DENSITY_LIMIT : 0.0;      // after 6 re-cuts: run with what we have
-        bool ok = true;
-        // All-vs-all over several chunks under a symmetric matrix: the k-mer hit relation is symmetric, so the chunk x chunk grid needs only its
-        // upper triangle.  The pass over chunk c matches the queries FROM chunk c onwards; the pairs (query behind the chunk, target in it) also
-        // yield the candidates of the pairs the other way round (diag_select_kernel), i.e. what the skipped passes (query in c, target chunk
-        // behind it) would have found: ~(1 + 1/C) / 2 of the k-mer hits are expanded.  The lists of a pass come back ungrouped and are merged
-        // like the chunk lists always were (lossless: per-pass top-M of disjoint candidate sets).  UC_PREFILTER_SYMMETRIC=0: every pass matches all queries.
-        const bool triangle = chunks.size() > 1 && tbegin == qbegin && tend == qend && p.mat_symmetric &&
-                              !(getenv("UC_PREFILTER_SYMMETRIC") && atoi(getenv("UC_PREFILTER_SYMMETRIC")) == 0);
-        if (chunks.size() <= 1) {
-            // (mirror_all — prefilter_cells only: every query lies outside the shard and yields the pair the other way round as well; the lists come
-            // back ungrouped and are merged by the caller)
-            ok = prefilter_one(tbegin, tend, qbegin, qend, true, limit, &density, mirror_all ? qbegin : UINT32_MAX);
-            if (ok) { stats.n_prefilter_hits += n_hits; if (pre && !mirror_all) pre->release_bytes(scratch_release_target(p.min_seq_id > 0.0f || p.want_tb, n_hits, pre->bytes(), aln != nullptr && (double)last_align_hits >= 0.9 * (double)n_hits)); return; }
-        } else {
-            // (Measured and reverted in r04: concatenating the per-pass lists and merging ONCE at the end — 1.5-2 G records in one sort instead of a
-            // running top-M accumulator of <= max_seqs x queries — made configs[2] SLOWER, 35.7 -> 39.3 s per pass: the single merge needs ~64 B per
-            // record of work buffers at the moment the key regions are largest.  The accumulator is merged after every pass.)
-            // (r06: the accumulator / pass arrays live in the scratch set - up to 4 x 7 GB at configs[2] were allocated and freed by every call)
-            if (!pre) pre = ParkedScratch<PrefilterScratch>::take_or_new(device);
-            DevBuf<uint32_t> &aq = pre->acc_q, &at = pre->acc_t, &tq = pre->pass_q, &tt = pre->pass_t;
-            DevBuf<int32_t> &as = pre->acc_s, &ad = pre->acc_d, &ts = pre->pass_s, &td = pre->pass_d;
-            uint64_t acc_n = 0;
-            bool installed = false;       // the last pass's merge leaves its result installed in the engine: no second merge of the accumulator
-            for (size_t c = 0; c < chunks.size() && ok; c++) {
-                const bool mir = mirror_all || (triangle && c + 1 < chunks.size());       // (the last chunk has no queries behind it: a plain pass over its own queries)
-                ok = prefilter_one(chunks[c].first, chunks[c].second, triangle ? chunks[c].first : qbegin, qend, c == 0, c == 0 ? limit : 0.0, &density,
-                                   mirror_all ? qbegin : mir ? chunks[c].second : UINT32_MAX);
-                if (!ok) break;
-                if (!mir && (c == 0 || acc_n == 0)) {
-                    aq.swap(d_hq); at.swap(d_ht); as.swap(d_hs); ad.swap(d_hd);
-                    acc_n = n_hits;
-                } else if (n_hits) {       // (a mirrored pass always comes here: its lists are ungrouped)
-                    // the pass's lists leave the engine (swap, no copy), the merge installs accumulator + pass in their place.  The accumulator is in key
-                    // order, a plain pass's lists are too: only a mirrored pass's records are sorted before the two runs are merged (merge_hits_dev)
-                    const uint64_t n_pass = n_hits;
-                    tq.swap(d_hq); tt.swap(d_ht); ts.swap(d_hs); td.swap(d_hd);
-                    acc_n = merge_hits_dev(acc_n, aq.p, at.p, as.p, ad.p, n_pass, tq.p, tt.p, ts.p, td.p, /*sorted2=*/!mir, 0, 1);      // merge + truncate to max_seqs
-                    if (c + 1 == chunks.size()) installed = true;
-                    else { aq.swap(d_hq); at.swap(d_ht); as.swap(d_hs); ad.swap(d_hd); }
-                }
-            }
-            if (ok) {
-                // install the accumulated lists (also rebuilds the per-query counts) unless the last merge already did
-                if (!installed) merge_hits_dev(acc_n, aq.p, at.p, as.p, ad.p, 0, nullptr, nullptr, nullptr, nullptr, true, 0, 1);     // (in key order already: counts only)
-                stats.n_prefilter_hits += n_hits;
-                if (pre) pre->release_bytes(scratch_release_target(p.min_seq_id > 0.0f || p.want_tb, n_hits, pre->bytes(), aln != nullptr && (double)last_align_hits >= 0.9 * (double)n_hits));
-                return;
-            }
-        }
-        // too dense: smaller chunks, proportionally (and a little more)
-        const uint64_t cur = std::min<uint64_t>(chunk_res, std::max<uint64_t>(1, (uint64_t)h_poff[chunks[0].second] - h_poff[chunks[0].first]));
-        chunk_res = std::max<uint64_t>(1u << 16, (uint64_t)((double)cur * DENSITY_LIMIT / density * 0.75));
-        logf(3, "unicore-cluster: prefilter: %.0f k-mer hits per query residue in a chunk of %llu residues; re-cutting the targets into chunks of %llu\n",
-             density, (unsigned long long)cur, (unsigned long long)chunk_res);
-    }
-}
-
-// returns false (nothing installed) if density_limit > 0 and the first query batch exceeds it; *density_out = k-mer hits
-// per query residue of that batch
-bool Engine::prefilter_one(uint32_t tbegin, uint32_t tend, uint32_t qbegin, uint32_t qend, bool count_sims, double density_limit,
-                           double *density_out, uint32_t mirror_q0) {
-    const bool mirrored = mirror_q0 != UINT32_MAX;    // symmetric pass (diag_select_kernel): the lists leave this function ungrouped, the caller merges them
-    UC_HIP(hipSetDevice(device));
-    const uint32_t n = hdb.n;
-    KmerCfg cfg;
-    for (int m = 0; m < K; m++) cfg.koff[m] = p.koff[m];
-    cfg.span = p.span;
-    cfg.thr = p.kmer_thr;
-
-    hit_cnt.assign(n, 0);
-    hit_off.assign((size_t)n + 1, 0);
-    n_hits = 0;
-    alns_valid = false;
-    clear_edges();
-    const uint64_t sims_before = stats.n_sim_kmers;   // stats accumulate over calls: the byte count below needs THIS call's share
-
-    if (n > (1u << 24)) fail(UC_ERR_GENERIC, "prefilter: %u sequences exceed the 2^24 limit of the hit keys", n);
-    // counters: [0] similar k-mers, [1] kept candidates, [2] ungapped overlap residues, [3] run cursor,
-    //           [4] k-mer hits of the batch, [5] key cursor, [6] candidate cursor
-    if (!pre) pre = ParkedScratch<PrefilterScratch>::take_or_new(device);
-    PrefilterScratch &S = *pre;
-    DevBuf<unsigned long long> &d_counters = S.d_counters;
-    d_counters.reserve(8);
-    UC_HIP(hipMemsetAsync(d_counters.p, 0, 64, stream));
-    DevBuf<char> &d_temp = S.d_temp;
-    auto temp_reserve = [&](size_t bytes) { d_temp.reserve(bytes + 256); };
-
-    // ------------------------------------------------------------ E1: index of targets [tbegin, tend)
-    Timer t_index;
-    timed_ms_begin();
-    const uint32_t tp0 = h_poff[tbegin], tp1 = h_poff[tend];
-    const uint32_t nres = tp1 - tp0;
-    DevBuf<uint32_t> &d_koff = S.d_koff;
-    DevBuf<uint64_t> &d_ent = S.d_ent;      // wide index entries sorted by k-mer: [sequence : 32 | position : 16]
-    DevBuf<uint32_t> &d_ent32 = S.d_ent32;  // compact index entries: [sequence - tbegin | position : dbits - 1]
-    d_koff.reserve((size_t)KSPACE + 1);
-    KeyFmt fmt;
-    {
-        const uint32_t m = std::min<uint32_t>(std::max<uint32_t>(max_len, 2), 65536u);
-        fmt.dbits = 1;
-        while ((1u << (fmt.dbits - 1)) < m) fmt.dbits++;
-        fmt.dbias = 1 << (fmt.dbits - 1);
-        fmt.tbits = 1;
-        while ((1u << fmt.tbits) < n) fmt.tbits++;
-        int rbits = 1;                                   // bits of a target id relative to this chunk
-        while ((1ull << rbits) < (uint64_t)std::max<uint32_t>(tend - tbegin, 1)) rbits++;
-        fmt.compact = rbits + fmt.dbits <= 32 && !getenv("UC_PREFILTER_WIDE");
-        fmt.tbase = tbegin;
-    }
-    const void *ent_p = nullptr;
-    uint32_t n_entries = 0;
-    {
-        DevBuf<uint32_t> &k_in = S.k_in, &k_out = S.k_out, &v_in32 = S.v_in32;
-        DevBuf<uint64_t> &v_in = S.v_in;
-        const size_t cap = std::max<uint32_t>(nres, 1);
-        k_in.reserve(cap); k_out.reserve(cap);
-        if (fmt.compact) { v_in32.reserve(cap); d_ent32.reserve(cap); ent_p = d_ent32.p; }
-        else { v_in.reserve(cap); d_ent.reserve(cap); ent_p = d_ent.p; }
-        if (nres) {
-            hipLaunchKernelGGL(kmer_extract_kernel, grid_for(nres), dim3(256), 0, stream, ddb, tbegin, tend, cfg, tp0, tp1, k_in.p,
-                               fmt.compact ? nullptr : v_in.p, fmt.compact ? v_in32.p : nullptr, fmt.dbits - 1);
-            size_t tb = 0;
-            if (fmt.compact) {
-                UC_HIP(rocprim::radix_sort_pairs(nullptr, tb, k_in.p, k_out.p, v_in32.p, d_ent32.p, (size_t)nres, 0u, 32u, stream));
-                temp_reserve(tb);
-                UC_HIP(rocprim::radix_sort_pairs(d_temp.p, tb, k_in.p, k_out.p, v_in32.p, d_ent32.p, (size_t)nres, 0u, 32u, stream));
-            } else {
-                UC_HIP(rocprim::radix_sort_pairs(nullptr, tb, k_in.p, k_out.p, v_in.p, d_ent.p, (size_t)nres, 0u, 32u, stream));
-                temp_reserve(tb);
-                UC_HIP(rocprim::radix_sort_pairs(d_temp.p, tb, k_in.p, k_out.p, v_in.p, d_ent.p, (size_t)nres, 0u, 32u, stream));
-            }
-        }
-        // number of valid entries = first index with key >= KSPACE: the offsets kernel's last slot
-        hipLaunchKernelGGL(kmer_offsets_kernel, grid_for((uint64_t)KSPACE + 1), dim3(256), 0, stream, k_out.p, nres, d_koff.p);
-        S.d_kbits.reserve((KSPACE + 31) / 32);
-        hipLaunchKernelGGL(kmer_bits_kernel, grid_for((KSPACE + 31) / 32), dim3(256), 0, stream, (const uint32_t *)d_koff.p, S.d_kbits.p);
-        UC_HIP(hipMemcpyAsync(&n_entries, d_koff.p + KSPACE, 4, hipMemcpyDeviceToHost, stream));
-        UC_HIP(hipStreamSynchronize(stream));
-    }
-    UC_HIP(hipGetLastError());
-    double gpu_ms = timed_ms_end();
-    stats.n_index_entries += n_entries;
-    stats.algorithmic_bytes[UC_ST_INDEX] += 6ull * n_entries + 8ull * KSPACE;
-    stats.stage_seconds[UC_ST_INDEX] += t_index.seconds();
-
-    // ------------------------------------------------------------ E2-E4 over query batches
-    // keys per batch (the filter's regions hold < 2^32 keys).  1.5 G keys = 12 GiB of regions: a one-shot `foldseek cluster` process
-    // pays for every byte it allocates (34 GiB of regions at 3.75 G keys: 5.2 s from process start to clust.tsv at configs[1]
-    // instead of 1.25 s), and a resident engine loses nothing measurable (681 vs 681 ms per step; UC_HIT_CAP overrides)
-    const uint64_t HIT_CAP = getenv("UC_HIT_CAP") ? std::max<uint64_t>(1u << 20, strtoull(getenv("UC_HIT_CAP"), nullptr, 10)) : (3ull << 29);
-    // ... unless the chunk has so many hits that the batches would run into the hundreds (2.5 M sequences: 1.5e12 hits): then the
-    // per-batch costs outweigh the allocation and the regions take 3.75 G keys (30 GiB)
-    const uint64_t HIT_CAP_BIG = getenv("UC_HIT_CAP") ? HIT_CAP : (15ull << 28);
-    uint64_t hit_cap = HIT_CAP;
-    const uint64_t RUN_MAX = 1ull << 29;       // runs per batch (6 GiB + 6 GiB sort double buffer)
-    uint64_t run_cap = 1ull << 20;
-    DevBuf<uint32_t> &d_cnt = S.d_cnt, &d_flag = S.d_flag, &d_cq = S.d_cq, &d_ct = S.d_ct, &d_rpidx2 = S.d_rpidx2, &d_qsurv = S.d_qsurv;
-    DevBuf<uint64_t> &d_keys = S.d_keys, &d_keys2 = S.d_keys2, &d_pos = S.d_pos, &d_skey = S.d_skey, &d_skey2 = S.d_skey2, &d_rval2 = S.d_rval2,
-                     &d_qbase = S.d_qbase, &d_soff = S.d_soff;
-    DevBuf<int32_t> &d_cd = S.d_cd, &d_cd2 = S.d_cd2, &d_score = S.d_score;
-    uint64_t n_hits_total = 0, n_cand_total = 0, cand_cap = 0;
-    double t_kmer = 0, t_ung = 0, t_sel = 0;
-    const auto sim_grid = [](uint64_t items) {
-        return dim3((uint32_t)std::min<uint64_t>(std::max<uint64_t>(1, (items + 4 * SIM_MIN_WAVE_POS - 1) / (4 * SIM_MIN_WAVE_POS)), SIM_MAX_BLOCKS));
-    };
-
-    // ---- distinct mode, once per target chunk and query "super-batch" [sa, sb) (normally all queries; cut when the run lists
-    //      of its distinct k-mers exceed DRUN_MAX, i.e. at high sensitivity): similar k-mers and index ranges of every
-    //      DISTINCT query k-mer, then per query position the length and source of its run list and its k-mer hits; exact
-    //      per-query totals for the batch plan ----
-    const uint32_t first_query = qbegin;
-    const uint64_t DRUN_MAX = getenv("UC_DRUN_MAX") ? std::max<uint64_t>(1, strtoull(getenv("UC_DRUN_MAX"), nullptr, 10)) : (1ull << 31);   // 24 GiB + 24 GiB sort double buffer (env: tests)
-    uint32_t P0 = 0, NP = 0;
-    std::vector<uint64_t> h_qh, h_qr;          // k-mer hits / runs per query of the super-batch
-    uint64_t over_runs = 0;
-    // 0 = planned, 1 = density limit exceeded (first super-batch only), 2 = too many runs (over_runs says how many)
-    const auto plan_superbatch = [&](uint32_t sa, uint32_t sb) -> int {
-        uint64_t plan_sims = 0, plan_hits = 0;
-        P0 = h_poff[sa]; NP = h_poff[sb] - P0;
-        const uint32_t qbegin = sa, qend = sb;   // this block works on the super-batch only
-        Timer t_p;
-        timed_ms_begin();
-        const uint32_t nqa = qend - qbegin;
-        S.d_qk.reserve((size_t)NP + 1); S.d_kflag.reserve((size_t)KSPACE + 1); S.d_kid.reserve((size_t)KSPACE + 1);
-        UC_HIP(hipMemsetAsync(S.d_kflag.p, 0, (size_t)KSPACE + 1, stream));
-        hipLaunchKernelGGL(query_kmer_kernel, grid_for(NP), dim3(256), 0, stream, ddb, cfg, qbegin, qend, P0, P0 + NP, S.d_qk.p, S.d_kflag.p);
-        size_t tb = 0;
-        auto fin = rocprim::make_transform_iterator(S.d_kflag.p, FlagToU32());
-        UC_HIP(rocprim::exclusive_scan(nullptr, tb, fin, S.d_kid.p, 0u, (size_t)KSPACE + 1, rocprim::plus<uint32_t>(), stream));
-        temp_reserve(tb);
-        UC_HIP(rocprim::exclusive_scan(d_temp.p, tb, fin, S.d_kid.p, 0u, (size_t)KSPACE + 1, rocprim::plus<uint32_t>(), stream));
-        uint32_t nd = 0;
-        UC_HIP(hipMemcpyAsync(&nd, S.d_kid.p + KSPACE, 4, hipMemcpyDeviceToHost, stream));
-        UC_HIP(hipStreamSynchronize(stream));
-        S.d_dk.reserve(std::max<uint32_t>(nd, 1)); S.d_nsimk.reserve(std::max<uint32_t>(nd, 1));
-        UC_HIP(hipMemsetAsync(S.d_nsimk.p, 0, (size_t)std::max<uint32_t>(nd, 1) * 4, stream));
-        hipLaunchKernelGGL(distinct_kmer_kernel, grid_for(KSPACE), dim3(256), 0, stream, S.d_kflag.p, S.d_kid.p, S.d_dk.p);
-        if (nqa > 1 && nd > (1u << 16)) {   // run-count estimate from every 64th distinct k-mer: cut the super-batch BEFORE the full enumeration
-            const uint32_t st = 64;
-            UC_HIP(hipMemsetAsync(d_counters.p + 3, 0, 32, stream));
-            UC_HIP(hipMemsetAsync(d_counters.p, 0, 8, stream));
-            hipLaunchKernelGGL(sim_runs_kernel, sim_grid((nd + st - 1) / st), dim3(256), 0, stream, ddb, cfg, 0u, 0u, 0u, nd, d_koff.p, RunList{nullptr, nullptr, 0},
-                               d_counters.p, S.d_dk.p, (uint32_t *)nullptr, st, (const uint32_t *)S.d_kbits.p);
-            unsigned long long c5[5];
-            UC_HIP(hipMemcpyAsync(c5, d_counters.p, 40, hipMemcpyDeviceToHost, stream));
-            UC_HIP(hipStreamSynchronize(stream));
-            if ((double)c5[3] * st > 0.9 * (double)DRUN_MAX) { over_runs = (uint64_t)((double)c5[3] * st / 0.9); gpu_ms += timed_ms_end(); t_kmer += t_p.seconds(); return 2; }
-        }
-        uint64_t n_druns = 0, drun_cap = S.d_drk.cap;
-        for (;;) {   // runs of the distinct k-mers, tagged with the k-mer's rank
-            drun_cap = std::min<uint64_t>(1ull << 32, std::max<uint64_t>(drun_cap, std::max<uint64_t>(1u << 20, std::min<uint64_t>(DRUN_MAX, (uint64_t)nd * 16))));
-            S.d_drk.reserve(drun_cap); S.d_drv.reserve(drun_cap);
-            UC_HIP(hipMemsetAsync(d_counters.p + 3, 0, 32, stream));
-            UC_HIP(hipMemsetAsync(d_counters.p, 0, 8, stream));
-            const RunList rl{S.d_drk.p, S.d_drv.p, drun_cap};
-            hipLaunchKernelGGL(sim_runs_kernel, sim_grid(nd), dim3(256), 0, stream, ddb, cfg, 0u, 0u, 0u, nd, d_koff.p, rl, d_counters.p, S.d_dk.p, S.d_nsimk.p, 1u,
-                               (const uint32_t *)S.d_kbits.p);
-            unsigned long long c5[5];
-            UC_HIP(hipMemcpyAsync(c5, d_counters.p, 40, hipMemcpyDeviceToHost, stream));
-            UC_HIP(hipStreamSynchronize(stream));
-            n_druns = c5[3];
-            if (n_druns > DRUN_MAX && nqa > 1) { over_runs = n_druns; gpu_ms += timed_ms_end(); t_kmer += t_p.seconds(); return 2; }
-            if (n_druns > drun_cap) {
-                if (n_druns >= (1ull << 32)) fail(UC_ERR_GENERIC, "%u distinct k-mers of query %u produce %llu index ranges", nd, qbegin, (unsigned long long)n_druns);
-                drun_cap = n_druns;
-                UC_HIP(hipMemsetAsync(S.d_nsimk.p, 0, (size_t)std::max<uint32_t>(nd, 1) * 4, stream));
-                continue;
-            }
-            break;
-        }
-        unsigned dbits = 1;
-        while ((1ull << dbits) < nd) dbits++;
-        S.d_drk2.reserve(drun_cap); S.d_drv2.reserve(drun_cap);
-        if (n_druns) {
-            UC_HIP(rocprim::radix_sort_pairs(nullptr, tb, S.d_drk.p, S.d_drk2.p, S.d_drv.p, S.d_drv2.p, (size_t)n_druns, 0u, dbits, stream));
-            temp_reserve(tb);
-            UC_HIP(rocprim::radix_sort_pairs(d_temp.p, tb, S.d_drk.p, S.d_drk2.p, S.d_drv.p, S.d_drv2.p, (size_t)n_druns, 0u, dbits, stream));
-        }
-        S.d_roff.reserve((size_t)nd + 1); S.d_rec.reserve(std::max<uint32_t>(nd, 1));
-        hipLaunchKernelGGL(rank_offsets_kernel, grid_for((uint64_t)nd + 1), dim3(256), 0, stream, S.d_drk2.p, (uint32_t)n_druns, nd, S.d_roff.p);
-        if (nd) hipLaunchKernelGGL(rank_rec_kernel, grid_for(nd), dim3(256), 0, stream, S.d_roff.p, S.d_drv2.p, S.d_nsimk.p, nd, S.d_rec.p);
-        // per position (one trailing zero element so that the exclusive sums end with the totals)
-        S.d_nr.reserve((size_t)NP + 1); S.d_src.reserve((size_t)NP + 1); S.d_ph.reserve((size_t)NP + 1);
-        S.d_cumh.reserve((size_t)NP + 1); S.d_cumr.reserve((size_t)NP + 1);
-        UC_HIP(hipMemsetAsync(d_counters.p, 0, 8, stream));
-        UC_HIP(hipMemsetAsync(S.d_nr.p + NP, 0, 4, stream));
-        UC_HIP(hipMemsetAsync(S.d_ph.p + NP, 0, 4, stream));
-        hipLaunchKernelGGL(position_runs_kernel, grid_for(NP), dim3(256), 0, stream, S.d_qk.p, NP, S.d_kid.p, S.d_rec.p, S.d_nr.p, S.d_src.p, S.d_ph.p, d_counters.p);
-        auto hin = rocprim::make_transform_iterator(S.d_ph.p, WidenU32());
-        auto rin = rocprim::make_transform_iterator(S.d_nr.p, WidenU32());
-        UC_HIP(rocprim::exclusive_scan(nullptr, tb, hin, S.d_cumh.p, (uint64_t)0, (size_t)NP + 1, rocprim::plus<uint64_t>(), stream));
-        temp_reserve(tb);
-        UC_HIP(rocprim::exclusive_scan(d_temp.p, tb, hin, S.d_cumh.p, (uint64_t)0, (size_t)NP + 1, rocprim::plus<uint64_t>(), stream));
-        UC_HIP(rocprim::exclusive_scan(d_temp.p, tb, rin, S.d_cumr.p, (uint64_t)0, (size_t)NP + 1, rocprim::plus<uint64_t>(), stream));
-        S.d_qh.reserve(nqa); S.d_qrn.reserve(nqa);
-        hipLaunchKernelGGL(query_totals_kernel, grid_for(nqa), dim3(256), 0, stream, ddb.off, qbegin, nqa, P0, S.d_cumh.p, S.d_cumr.p, S.d_qh.p, S.d_qrn.p);
-        h_qh.resize(nqa); h_qr.resize(nqa);
-        unsigned long long c0 = 0;
-        UC_HIP(hipMemcpyAsync(h_qh.data(), S.d_qh.p, (size_t)nqa * 8, hipMemcpyDeviceToHost, stream));
-        UC_HIP(hipMemcpyAsync(h_qr.data(), S.d_qrn.p, (size_t)nqa * 8, hipMemcpyDeviceToHost, stream));
-        UC_HIP(hipMemcpyAsync(&c0, d_counters.p, 8, hipMemcpyDeviceToHost, stream));
-        UC_HIP(hipStreamSynchronize(stream));
-        plan_sims = c0;
-        for (uint32_t i = 0; i < nqa; i++) plan_hits += h_qh[i];
-        hit_cap = plan_hits > 16 * HIT_CAP ? HIT_CAP_BIG : HIT_CAP;
-        gpu_ms += timed_ms_end();
-        t_kmer += t_p.seconds();
-        if (sa == first_query) {
-            if (density_out) *density_out = (double)plan_hits / std::max<uint32_t>(1, NP);
-            if (density_limit > 0 && p.min_diag_hits >= 2 && tend - tbegin > 1 && (double)plan_hits / std::max<uint32_t>(1, NP) > density_limit) return 1;
-        }
-        if (count_sims) stats.n_sim_kmers += plan_sims;
-        return 0;
-    };
-    uint32_t sb_end = qbegin;                  // end of the planned super-batch
-    double sb_frac = 1.0;                      // share of the remaining queries to try next
-
-    uint32_t sb_begin = qbegin;
-    for (uint32_t qa = qbegin; qa < qend;) {
-        if (qa >= sb_end) {
-            for (;;) {
-                const uint32_t left = qend - qa;
-                const uint32_t sb = sb_frac >= 1.0 ? qend : qa + std::max<uint32_t>(1, std::min<uint32_t>(left, (uint32_t)(left * sb_frac)));
-                const int rc = plan_superbatch(qa, sb);
-                if (rc == 1) {   // undo what this abandoned attempt counted
-                    stats.n_index_entries -= n_entries;
-                    stats.algorithmic_bytes[UC_ST_INDEX] -= 6ull * n_entries + 8ull * KSPACE;
-                    stats.prefilter_kernel_ms += gpu_ms;
-                    return false;
-                }
-                if (rc == 2) {   // distinct k-mers grow sublinearly with the queries: cut a little deeper than proportionally
-                    sb_frac = (double)(sb - qa) / left * 0.8 * (double)DRUN_MAX / (double)over_runs;
-                    continue;
-                }
-                sb_begin = qa; sb_end = sb;
-                if (sb_frac < 1.0) sb_frac = std::min(1.0, (double)(sb - qa) / std::max<uint32_t>(1, qend - sb));   // the same number of queries again
-                break;
-            }
-        }
-        Timer t_b;
-        timed_ms_begin();
-        uint32_t qb = qa;
-        uint64_t total_hits = 0, n_runs = 0, mirror_hits = 0;
-        uint32_t qp0 = 0, qp1 = 0, nq_res = 0;
-        {
-            // exact plan: as many queries as fit the key and run buffers (a single query may exceed them and takes the wide path)
-            while (qb < sb_end && qb - qa < (1u << 23) - 1) {
-                const uint64_t h = h_qh[qb - sb_begin], r = h_qr[qb - sb_begin];
-                if (qb > qa && (total_hits + h > hit_cap || n_runs + r > RUN_MAX)) break;
-                total_hits += h; n_runs += r;
-                if (qb >= mirror_q0) mirror_hits += h;       // these hits stand for the hits of the pairs the other way round as well
-                qb++;
-            }
-            if (n_runs >= (1ull << 32)) fail(UC_ERR_GENERIC, "query %u alone produces %llu index ranges", qa, (unsigned long long)n_runs);
-            qp0 = h_poff[qa]; qp1 = h_poff[qb]; nq_res = qp1 - qp0;
-            run_cap = std::max<uint64_t>(run_cap, n_runs);
-            d_rpidx2.reserve(run_cap); d_rval2.reserve(run_cap);
-            UC_HIP(hipMemsetAsync(d_counters.p + 3, 0, 32, stream));   // run cursor, batch hits, key cursor, candidate cursor
-            if (n_runs)
-                hipLaunchKernelGGL(position_expand_kernel, grid_for(nq_res), dim3(256), 0, stream, qp0 - P0, qp1 - P0, S.d_nr.p, S.d_src.p, S.d_cumr.p, S.d_drv2.p,
-                                   d_rpidx2.p, d_rval2.p);
-        }
-        if (total_hits > (1ull << 34)) fail(UC_ERR_GENERIC, "query %u alone produces %llu k-mer hits", qa, (unsigned long long)total_hits);
-        n_hits_total += total_hits + mirror_hits;
-        uint64_t n_cand = 0;
-        if (total_hits) {
-            // pass 2: expand runs into keys (filtered to double hits when the rule allows), sort them
-            unsigned qbits = 1;
-            while ((1u << qbits) < qb - qa) qbits++;
-            const unsigned kbits = (unsigned)(fmt.dbits + fmt.tbits) + qbits;
-            const uint64_t *sorted = nullptr;
-            uint64_t n_sort = 0;
-            size_t tb = 0;
-            if (p.min_diag_hits >= 2 && total_hits < (1ull << 32)) {
-                const uint32_t nq = qb - qa;
-                unsigned pbits = 1;
-                while ((1ull << pbits) < nq_res) pbits++;
-                d_rpidx2.reserve(run_cap); d_rval2.reserve(run_cap);
-                d_qbase.reserve(nq); d_qsurv.reserve(nq); d_soff.reserve((size_t)nq + 1);
-                // the query regions hold (target, diagonal) keys: u32 in compact mode (half of the u64 buffer stays unused),
-                // every region rounded up to KPT keys
-                const uint64_t region_cap = total_hits + (uint64_t)KPT * nq;
-                d_keys.reserve(fmt.compact ? region_cap : 2 * region_cap);       // regions + survivor area of the same size
-                S.d_qr.reserve((size_t)nq + 1);
-                hipLaunchKernelGGL(run_range_kernel, grid_for((uint64_t)nq + 1), dim3(256), 0, stream, ddb, qa, nq, qp0, d_rpidx2.p, n_runs, S.d_qr.p);
-                S.d_okey.reserve(nq); S.d_okey2.reserve(nq); S.d_oidx.reserve(nq); S.d_order.reserve(nq);
-                hipLaunchKernelGGL(run_order_key_kernel, grid_for(nq), dim3(256), 0, stream, nq, S.d_qr.p, S.d_okey.p, S.d_oidx.p);
-                UC_HIP(rocprim::radix_sort_pairs(nullptr, tb, S.d_okey.p, S.d_okey2.p, S.d_oidx.p, S.d_order.p, (size_t)nq, 0u, 32u, stream));
-                temp_reserve(tb);
-                UC_HIP(rocprim::radix_sort_pairs(d_temp.p, tb, S.d_okey.p, S.d_okey2.p, S.d_oidx.p, S.d_order.p, (size_t)nq, 0u, 32u, stream));
-                {
-                    auto launch = [&](auto kern) {
-                        static PerDeviceOnce once[2];
-                        once[fmt.compact ? 1 : 0]([&] { UC_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)filter_lds(FILTER_RPT))); });
-                        hipLaunchKernelGGL(kern, dim3(nq), dim3(FT), filter_lds(FILTER_RPT), stream, ddb, qa, qp0, d_rpidx2.p, d_rval2.p, S.d_qr.p, S.d_order.p, ent_p, fmt,
-                                           d_counters.p + 5, (void *)d_keys.p, region_cap, d_qbase.p, d_qsurv.p);
-                    };
-                    if (fmt.compact) launch(filter_kernel<true>);
-                    else launch(filter_kernel<false>);
-                }
-                auto sin = rocprim::make_transform_iterator(d_qsurv.p, WidenU32());
-                UC_HIP(rocprim::exclusive_scan(nullptr, tb, sin, d_soff.p, (uint64_t)0, (size_t)nq, rocprim::plus<uint64_t>(), stream));
-                temp_reserve(tb);
-                UC_HIP(rocprim::exclusive_scan(d_temp.p, tb, sin, d_soff.p, (uint64_t)0, (size_t)nq, rocprim::plus<uint64_t>(), stream));
-                uint64_t lo = 0; uint32_t ls = 0;
-                UC_HIP(hipMemcpyAsync(&lo, d_soff.p + (nq - 1), 8, hipMemcpyDeviceToHost, stream));
-                UC_HIP(hipMemcpyAsync(&ls, d_qsurv.p + (nq - 1), 4, hipMemcpyDeviceToHost, stream));
-                UC_HIP(hipStreamSynchronize(stream));
-                n_sort = lo + ls;
-                if (n_sort) {
-                    d_keys2.reserve(2 * n_sort);              // dense keys + the sort's output
-                    if (fmt.compact)
-                        hipLaunchKernelGGL(compact_kernel<true>, dim3(std::min<uint32_t>(nq, 65535u)), dim3(256), 0, stream, (const void *)d_keys.p, d_qbase.p,
-                                           d_qsurv.p, d_soff.p, nq, fmt, d_keys2.p);
-                    else
-                        hipLaunchKernelGGL(compact_kernel<false>, dim3(std::min<uint32_t>(nq, 65535u)), dim3(256), 0, stream, (const void *)d_keys.p, d_qbase.p,
-                                           d_qsurv.p, d_soff.p, nq, fmt, d_keys2.p);
-                    UC_HIP(rocprim::radix_sort_keys(nullptr, tb, d_keys2.p, d_keys2.p + n_sort, (size_t)n_sort, 0u, kbits, stream));
-                    temp_reserve(tb);
-                    UC_HIP(rocprim::radix_sort_keys(d_temp.p, tb, d_keys2.p, d_keys2.p + n_sort, (size_t)n_sort, 0u, kbits, stream));
-                }
-                sorted = d_keys2.p + n_sort;
-                stats.n_filtered_hits += n_sort;
-            } else {
-                d_keys.reserve(total_hits);
-                d_keys2.reserve(total_hits);
-                const RunList rl{d_rpidx2.p, d_rval2.p, run_cap};
-                hipLaunchKernelGGL(expand_kernel, grid_for(n_runs), dim3(256), 0, stream, ddb, qa, qb, qp0, rl, n_runs, ent_p, fmt,
-                                   d_counters.p + 5, d_keys.p, total_hits);
-                UC_HIP(rocprim::radix_sort_keys(nullptr, tb, d_keys.p, d_keys2.p, (size_t)total_hits, 0u, kbits, stream));
-                temp_reserve(tb);
-                UC_HIP(rocprim::radix_sort_keys(d_temp.p, tb, d_keys.p, d_keys2.p, (size_t)total_hits, 0u, kbits, stream));
-                sorted = d_keys2.p;
-                n_sort = total_hits;
-                stats.n_filtered_hits += n_sort;
-            }
-            cand_cap = std::max<uint64_t>(cand_cap, std::max<uint64_t>(1u << 20, total_hits / 32));
-            for (;;) {
-                d_cq.reserve(cand_cap); d_ct.reserve(cand_cap); d_cd.reserve(cand_cap);
-                UC_HIP(hipMemsetAsync(d_counters.p + 6, 0, 8, stream));
-                if (n_sort) {
-                    S.d_wflag.reserve((n_sort + 63) / 64 + 64);
-                    hipLaunchKernelGGL(diag_select_kernel, grid_for(n_sort), dim3(256), 0, stream, sorted, n_sort, p.min_diag_hits, fmt, qa,
-                                       d_counters.p + 6, cand_cap, d_cq.p, d_ct.p, d_cd.p, mirror_q0, S.d_wflag.p);
-                    hipLaunchKernelGGL(diag_long_kernel, grid_for((n_sort + 63) / 64), dim3(256), 0, stream, sorted, n_sort, p.min_diag_hits, fmt, qa,
-                                       d_counters.p + 6, cand_cap, d_cq.p, d_ct.p, d_cd.p, mirror_q0, (const uint8_t *)S.d_wflag.p);
-                }
-                unsigned long long nc = 0;
-                UC_HIP(hipMemcpyAsync(&nc, d_counters.p + 6, 8, hipMemcpyDeviceToHost, stream));
-                UC_HIP(hipStreamSynchronize(stream));
-                n_cand = nc;
-                if (n_cand <= cand_cap) break;
-                cand_cap = n_cand;     // rare: more candidates than provisioned, run the selection again
-            }
-        }
-        UC_HIP(hipGetLastError());
-        gpu_ms += timed_ms_end();
-        t_kmer += t_b.seconds();
-        n_cand_total += n_cand;
-
-        if (n_cand) {
-            // -------------------------------------------------------- E3: ungapped rescoring
-            Timer t_u;
-            timed_ms_begin();
-            d_score.reserve(n_cand);
-            launch_ungapped(ddb, n_cand, d_cq.p, d_ct.p, d_cd.p, d_score.p, d_counters.p + 2, stream);
-            UC_HIP(hipGetLastError());
-            gpu_ms += timed_ms_end();
-            t_ung += t_u.seconds();
-            // -------------------------------------------------------- E4: select
-            Timer t_s;
-            timed_ms_begin();
-            d_skey.reserve(n_cand); d_skey2.reserve(n_cand); d_cd2.reserve(n_cand);
-            UC_HIP(hipMemsetAsync(d_counters.p + 1, 0, 8, stream));
-            hipLaunchKernelGGL(select_key_kernel, grid_for(n_cand), dim3(256), 0, stream, n_cand, d_cq.p, d_ct.p, d_score.p, p.min_ungapped, d_skey.p, d_counters.p + 1);
-            size_t tb = 0;
-            UC_HIP(rocprim::radix_sort_pairs(nullptr, tb, d_skey.p, d_skey2.p, d_cd.p, d_cd2.p, (size_t)n_cand, 0u, 64u, stream));
-            temp_reserve(tb);
-            UC_HIP(rocprim::radix_sort_pairs(d_temp.p, tb, d_skey.p, d_skey2.p, d_cd.p, d_cd2.p, (size_t)n_cand, 0u, 64u, stream));
-            unsigned long long kept = 0;
-            UC_HIP(hipMemcpyAsync(&kept, d_counters.p + 1, 8, hipMemcpyDeviceToHost, stream));
-            UC_HIP(hipStreamSynchronize(stream));
-            if (kept) {   // rank inside each query's run, keep the first max_seqs, append to the device hit lists
-                d_flag.reserve(kept); d_pos.reserve(kept);
-                hipLaunchKernelGGL(rank_flag_kernel, grid_for(kept), dim3(256), 0, stream, d_skey2.p, (uint64_t)kept, (uint32_t)p.max_seqs, d_flag.p);
-                auto rin = rocprim::make_transform_iterator(d_flag.p, WidenU32());
-                UC_HIP(rocprim::exclusive_scan(nullptr, tb, rin, d_pos.p, (uint64_t)0, (size_t)kept, rocprim::plus<uint64_t>(), stream));
-                temp_reserve(tb);
-                UC_HIP(rocprim::exclusive_scan(d_temp.p, tb, rin, d_pos.p, (uint64_t)0, (size_t)kept, rocprim::plus<uint64_t>(), stream));
-                uint64_t lp = 0; uint32_t lf = 0;
-                UC_HIP(hipMemcpyAsync(&lp, d_pos.p + (kept - 1), 8, hipMemcpyDeviceToHost, stream));
-                UC_HIP(hipMemcpyAsync(&lf, d_flag.p + (kept - 1), 4, hipMemcpyDeviceToHost, stream));
-                UC_HIP(hipStreamSynchronize(stream));
-                const uint64_t add = lp + lf;
-                d_hq.grow_preserve(n_hits + add, n_hits, stream); d_ht.grow_preserve(n_hits + add, n_hits, stream);
-                d_hs.grow_preserve(n_hits + add, n_hits, stream); d_hd.grow_preserve(n_hits + add, n_hits, stream);
-                hipLaunchKernelGGL(hit_scatter_kernel, grid_for(kept), dim3(256), 0, stream, d_skey2.p, d_cd2.p, (uint64_t)kept, d_flag.p, d_pos.p,
-                                   d_hq.p + n_hits, d_ht.p + n_hits, d_hs.p + n_hits, d_hd.p + n_hits);
-                n_hits += add;
-            }
-            UC_HIP(hipGetLastError());
-            gpu_ms += timed_ms_end();
-            t_sel += t_s.seconds();
-        }
-        qa = qb;
-    }
-    // per-query counts / offsets (the host only keeps these two small arrays)
-    if (n_hits && !mirrored) {
-        d_cnt.reserve(n);
-        hipLaunchKernelGGL(hit_count_kernel, grid_for(n), dim3(256), 0, stream, d_hq.p, n_hits, n, d_cnt.p);
-        UC_HIP(hipMemcpyAsync(hit_cnt.data(), d_cnt.p, (size_t)n * 4, hipMemcpyDeviceToHost, stream));
-        UC_HIP(hipStreamSynchronize(stream));
-    }
-    if (!mirrored) {
-        for (uint32_t q = 0; q < n; q++) hit_off[q + 1] = hit_off[q] + hit_cnt[q];
-        if (hit_off[n] != n_hits) fail(UC_ERR_GENERIC, "prefilter: hit list bookkeeping mismatch");
-    }
-    unsigned long long ovl = 0;
-    UC_HIP(hipMemcpy(&ovl, d_counters.p + 2, 8, hipMemcpyDeviceToHost));
-    const uint64_t ungapped_bytes = ovl + 16ull * n_cand_total;   // (overlap + 16) B per candidate, SURVEY.md 8(d)
-    stats.n_kmer_hits += n_hits_total;
-    stats.n_candidates += n_cand_total;
-    stats.algorithmic_bytes[UC_ST_KMER] += 8ull * (stats.n_sim_kmers - sims_before) + 6ull * n_hits_total + 8ull * n_cand_total;
-    stats.algorithmic_bytes[UC_ST_UNGAPPED] += ungapped_bytes;
-    stats.algorithmic_bytes[UC_ST_SELECT] += 16ull * n_cand_total;
-    stats.stage_seconds[UC_ST_KMER] += t_kmer;
-    stats.stage_seconds[UC_ST_UNGAPPED] += t_ung;
-    stats.stage_seconds[UC_ST_SELECT] += t_sel;
-    stats.prefilter_kernel_ms += gpu_ms;
-    return true;
+    release_scratch_for_gapped_stage(*this);
 }
 
 void Engine::export_hits_dev(uint32_t *dq, uint32_t *dt, int32_t *ds, int32_t *dd) const {
     if (!n_hits) return;
     UC_HIP(hipSetDevice(device));
-    UC_HIP(hipMemcpyAsync(dq, d_hq.p, n_hits * 4, hipMemcpyDeviceToDevice, stream));
-    UC_HIP(hipMemcpyAsync(dt, d_ht.p, n_hits * 4, hipMemcpyDeviceToDevice, stream));
-    UC_HIP(hipMemcpyAsync(ds, d_hs.p, n_hits * 4, hipMemcpyDeviceToDevice, stream));
-    UC_HIP(hipMemcpyAsync(dd, d_hd.p, n_hits * 4, hipMemcpyDeviceToDevice, stream));
-    UC_HIP(hipStreamSynchronize(stream));
+    copy_hits_dev(*this, dq, dt, ds, dd);
 }
 
 // Multi-GPU phase 2: the engine's (merged, truncated) lists regrouped by the rank that owns each pair.  The partition is a
@@ -1967,16 +2015,12 @@ void Engine::partition_hits_by_owner(uint32_t world, uint32_t *dq, uint32_t *dt,
     if (!pre) pre = ParkedScratch<PrefilterScratch>::take_or_new(device);
     DevBuf<uint32_t> &okey = pre->d_cq, &okey2 = pre->d_ct, &idx = pre->d_flag, &idx2 = pre->d_cnt;
     DevBuf<unsigned long long> cnt;
-    DevBuf<char> &tmp = pre->d_temp;
     okey.reserve(n_hits); okey2.reserve(n_hits); idx.reserve(n_hits); idx2.reserve(n_hits); cnt.reserve(world);
     UC_HIP(hipMemsetAsync(cnt.p, 0, (size_t)world * 8, stream));
     hipLaunchKernelGGL(owner_key_kernel, grid_for(n_hits), dim3(256), 0, stream, n_hits, d_hq.p, d_ht.p, ddb.len, world, okey.p, idx.p, cnt.p);
     unsigned bits = 1;
     while ((1u << bits) < world) bits++;
-    size_t tb = 0;
-    UC_HIP(rocprim::radix_sort_pairs(nullptr, tb, okey.p, okey2.p, idx.p, idx2.p, (size_t)n_hits, 0u, bits, stream));
-    tmp.reserve(tb + 256);
-    UC_HIP(rocprim::radix_sort_pairs(tmp.p, tb, okey.p, okey2.p, idx.p, idx2.p, (size_t)n_hits, 0u, bits, stream));
+    rocprim_call(pre->d_temp, [&](void *t, size_t &b) { return rocprim::radix_sort_pairs(t, b, okey.p, okey2.p, idx.p, idx2.p, (size_t)n_hits, 0u, bits, stream); });
     hipLaunchKernelGGL(owner_gather_kernel, grid_for(n_hits), dim3(256), 0, stream, n_hits, idx2.p, d_hq.p, d_ht.p, d_hs.p, d_hd.p, dq, dt, ds, dd);
     std::vector<unsigned long long> hc(world);
     UC_HIP(hipMemcpyAsync(hc.data(), cnt.p, (size_t)world * 8, hipMemcpyDeviceToHost, stream));
@@ -1992,7 +2036,7 @@ uint64_t Engine::import_hits_dev(uint64_t n_in, const uint32_t *dq, const uint32
 
 // The union of two record lists, merged per query under the frozen order (score desc, target asc), truncated to max_seqs and installed.  List 1 is
 // ALREADY in key order (a running top-M accumulator, i.e. the output of an earlier merge or a grouped pass); list 2 is sorted here unless the caller says
-// it is in key order as well.  r06: the chunk loop of prefilter_impl used to radix-sort accumulator + chunk after every pass - at nominal configs[3] the
+// it is in key order as well.  r06: the chunk loop (prefilter_chunks) used to radix-sort accumulator + chunk after every pass - at nominal configs[3] the
 // accumulator of up to max_seqs x queries records went through ~7 sort passes (~170 B of traffic per record) once per target chunk, 8.9 s of the call.
 // Now only the chunk's records are sorted and the two runs are merged (one read + one write of every record); the result is the stable sort's, record for record
 // (the passes' candidate sets are disjoint, so no two keys are equal; rocprim::merge takes list 1 first on ties, as the stable sort of the concatenation did).
@@ -2017,19 +2061,18 @@ uint64_t Engine::merge_hits_dev(uint64_t n1, const uint32_t *q1, const uint32_t 
     // ~50 B per record anew every time was most of the merge time at 10^9 records
     if (!pre) pre = ParkedScratch<PrefilterScratch>::take_or_new(device);
     DevBuf<uint64_t> &skey = pre->d_skey, &skey2 = pre->d_skey2, &pos = pre->d_pos;
-    DevBuf<int32_t> &cd2 = pre->d_cd2;
-    DevBuf<uint32_t> &flag = pre->d_flag, &cnt = pre->d_cnt;
+    DevBuf<int32_t> &cd2 = pre->d_cd2, &mval = pre->d_mval;
+    DevBuf<uint32_t> &flag = pre->d_flag;
     DevBuf<uint32_t> bad;
     DevBuf<char> &tmp = pre->d_temp;
     // the merge path (rocprim::merge partitions with 32-bit indices) - UC_MERGE_SORTED=0 keeps the plain sort of everything for A/B runs
-    static const bool merge_ok = !(getenv("UC_MERGE_SORTED") && atoi(getenv("UC_MERGE_SORTED")) == 0);
+    static const bool merge_ok = [] { const char *e = getenv("UC_MERGE_SORTED"); return !(e && atoi(e) == 0); }();
     const bool merging = n1 > 0 && n2 > 0 && merge_ok && n_in < (1ull << 32) - (1ull << 20);
     const bool presorted = n1 > 0 && n2 == 0 && merge_ok;              // nothing to add: only truncation / ownership / counts
     skey.reserve(n_in); flag.reserve(n_in); pos.reserve(n_in); bad.reserve(1);
     UC_HIP(hipMemsetAsync(bad.p, 0, 4, stream));
     if (n1) hipLaunchKernelGGL(merge_key_kernel, grid_for(n1), dim3(256), 0, stream, n1, q1, t1, s1, n, skey.p, bad.p);
     if (n2) hipLaunchKernelGGL(merge_key_kernel, grid_for(n2), dim3(256), 0, stream, n2, q2, t2, s2, n, skey.p + n1, bad.p);
-    size_t tb = 0;
     unsigned kb = 33;                              // [query | 255 - score : 8 | target : 24]: the query field ends at bit 32 + log2 n
     while (kb < 64 && (1ull << (kb - 32)) < n) kb++;
     const uint64_t *sk = nullptr;                  // the sorted keys and their diagonals
@@ -2040,53 +2083,36 @@ uint64_t Engine::merge_hits_dev(uint64_t n1, const uint32_t *q1, const uint32_t 
         const int32_t *v2 = d2;
         if (!sorted2) {
             skey2.reserve(n2); cd2.reserve(n2);
-            UC_HIP(rocprim::radix_sort_pairs(nullptr, tb, skey.p + n1, skey2.p, d2, cd2.p, (size_t)n2, 0u, kb, stream));
-            tmp.reserve(tb + 256);
-            UC_HIP(rocprim::radix_sort_pairs(tmp.p, tb, skey.p + n1, skey2.p, d2, cd2.p, (size_t)n2, 0u, kb, stream));
+            rocprim_call(tmp, [&](void *t, size_t &b) { return rocprim::radix_sort_pairs(t, b, skey.p + n1, skey2.p, d2, cd2.p, (size_t)n2, 0u, kb, stream); });
             k2 = skey2.p; v2 = cd2.p;
         }
         DevBuf<uint64_t> &mkey = pre->d_mkey;
-        DevBuf<int32_t> &mval = pre->d_mval;
         mkey.reserve(n_in); mval.reserve(n_in);
-        UC_HIP(rocprim::merge(nullptr, tb, skey.p, k2, mkey.p, d1, v2, mval.p, (size_t)n1, (size_t)n2, rocprim::less<uint64_t>(), stream));
-        tmp.reserve(tb + 256);
-        UC_HIP(rocprim::merge(tmp.p, tb, skey.p, k2, mkey.p, d1, v2, mval.p, (size_t)n1, (size_t)n2, rocprim::less<uint64_t>(), stream));
+        rocprim_call(tmp, [&](void *t, size_t &b) { return rocprim::merge(t, b, skey.p, k2, mkey.p, d1, v2, mval.p, (size_t)n1, (size_t)n2, rocprim::less<uint64_t>(), stream); });
         sk = mkey.p; sd = mval.p;
     } else {
         // one list (or the A/B switch): the diagonals of the two inputs have to be one array for the pair sort
         const int32_t *dd = n1 ? nullptr : d2;
         skey2.reserve(n_in); cd2.reserve(n_in);
         if (n1) {
-            DevBuf<int32_t> &mval = pre->d_mval;
             mval.reserve(n_in);
             UC_HIP(hipMemcpyAsync(mval.p, d1, n1 * 4, hipMemcpyDeviceToDevice, stream));
             if (n2) UC_HIP(hipMemcpyAsync(mval.p + n1, d2, n2 * 4, hipMemcpyDeviceToDevice, stream));
             dd = mval.p;
         }
-        UC_HIP(rocprim::radix_sort_pairs(nullptr, tb, skey.p, skey2.p, dd, cd2.p, (size_t)n_in, 0u, kb, stream));
-        tmp.reserve(tb + 256);
-        UC_HIP(rocprim::radix_sort_pairs(tmp.p, tb, skey.p, skey2.p, dd, cd2.p, (size_t)n_in, 0u, kb, stream));
+        rocprim_call(tmp, [&](void *t, size_t &b) { return rocprim::radix_sort_pairs(t, b, skey.p, skey2.p, dd, cd2.p, (size_t)n_in, 0u, kb, stream); });
         sk = skey2.p; sd = cd2.p;
     }
     hipLaunchKernelGGL(rank_flag_kernel, grid_for(n_in), dim3(256), 0, stream, sk, n_in, (uint32_t)p.max_seqs, flag.p);
     if (world > 1) hipLaunchKernelGGL(owner_flag_kernel, grid_for(n_in), dim3(256), 0, stream, sk, n_in, ddb.len, rank, world, flag.p);
-    auto rin = rocprim::make_transform_iterator(flag.p, WidenU32());
-    UC_HIP(rocprim::exclusive_scan(nullptr, tb, rin, pos.p, (uint64_t)0, (size_t)n_in, rocprim::plus<uint64_t>(), stream));
-    tmp.reserve(tb + 256);
-    UC_HIP(rocprim::exclusive_scan(tmp.p, tb, rin, pos.p, (uint64_t)0, (size_t)n_in, rocprim::plus<uint64_t>(), stream));
-    uint64_t lp = 0; uint32_t lf = 0, hbad = 0;
-    UC_HIP(hipMemcpyAsync(&lp, pos.p + (n_in - 1), 8, hipMemcpyDeviceToHost, stream));
-    UC_HIP(hipMemcpyAsync(&lf, flag.p + (n_in - 1), 4, hipMemcpyDeviceToHost, stream));
-    UC_HIP(hipMemcpyAsync(&hbad, bad.p, 4, hipMemcpyDeviceToHost, stream));
-    UC_HIP(hipStreamSynchronize(stream));
+    uint32_t hbad = 0;
+    const uint64_t keep = compact_u64(*this, tmp, flag.p, pos.p, n_in, bad.p, &hbad);
     if (hbad) fail(UC_ERR_ARGS, "hits_import_dev: %u records with a sequence id or score out of range", hbad);
-    const uint64_t keep = lp + lf;
     if (keep) {
         // (list 1 or 2 may BE the engine's own arrays: the scatter reads only keys and the sorted diagonals, never q / t / s / d of the inputs - but the
         // diagonals of a presorted or merged input are read from d1 / d2 themselves, so the output must not overwrite them in place)
         const bool alias = (sd == d1 && d1 == d_hd.p) || (sd == d2 && d2 == d_hd.p);
         if (alias) {
-            DevBuf<int32_t> &mval = pre->d_mval;
             mval.reserve(n_in);
             UC_HIP(hipMemcpyAsync(mval.p, sd, n_in * 4, hipMemcpyDeviceToDevice, stream));
             sd = mval.p;
@@ -2094,14 +2120,9 @@ uint64_t Engine::merge_hits_dev(uint64_t n1, const uint32_t *q1, const uint32_t 
         d_hq.reserve(keep); d_ht.reserve(keep); d_hs.reserve(keep); d_hd.reserve(keep);
         hipLaunchKernelGGL(hit_scatter_kernel, grid_for(n_in), dim3(256), 0, stream, sk, sd, n_in, flag.p, pos.p, d_hq.p, d_ht.p, d_hs.p, d_hd.p);
         n_hits = keep;
-        cnt.reserve(n);
-        hipLaunchKernelGGL(hit_count_kernel, grid_for(n), dim3(256), 0, stream, d_hq.p, n_hits, n, cnt.p);
-        UC_HIP(hipMemcpyAsync(hit_cnt.data(), cnt.p, (size_t)n * 4, hipMemcpyDeviceToHost, stream));
-        UC_HIP(hipStreamSynchronize(stream));
     }
+    finish_hit_lists("hits_import_dev");
     UC_HIP(hipGetLastError());
-    for (uint32_t q = 0; q < n; q++) hit_off[q + 1] = hit_off[q] + hit_cnt[q];
-    if (hit_off[n] != n_hits) fail(UC_ERR_GENERIC, "hits_import_dev: hit list bookkeeping mismatch");
     stats.prefilter_kernel_ms += timed_ms_end();
     stats.stage_seconds[UC_ST_SELECT] += tm.seconds();
     return keep;
