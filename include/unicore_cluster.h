@@ -254,6 +254,11 @@ int uc_write_cluster_db(const char *out_cluster_db, uint32_t n, const uint32_t *
 /* ungapped diagonal score (E3) for n candidates (q[i], t[i], diag[i]) of the engine's DB */
 int uc_engine_ungapped_batch(uc_engine *e, uint64_t n, const uint32_t *q, const uint32_t *t,
                              const int32_t *diag, int32_t *score_out);
+/* rule UC-1/X (--prefilter-mode 1) for queries [qbegin, qend) x targets [tbegin, tend) of the engine's DB: dense row-major
+ * [qend - qbegin][tend - tbegin] arrays, the best ungapped score over ALL diagonals (capped at 255) and the smallest diagonal that
+ * reaches it.  Computed tile by tile under tile_bytes (0 = the engine's default tile budget). */
+int uc_engine_ungapped_all(uc_engine *e, uint32_t qbegin, uint32_t qend, uint32_t tbegin, uint32_t tend, uint64_t tile_bytes,
+                           int32_t *score_out, int32_t *diag_out);
 /* gapped DP (E5) for n pairs.  mode 0: forward (score, qend, tend); mode 1: reversed query (score);
  * mode 2: start pass on reverse(q[0..qend_in]) x reverse(t[0..tend_in]) (score, qend', tend').
  * Pairs may be in any order (the engine groups them by query internally). */

@@ -62,7 +62,7 @@ SYMBOLS = (
     "uc_engine_hits_export_dev", "uc_engine_hits_import_dev", "uc_engine_setcover",
     "uc_hits_merge", "uc_engine_align", "uc_engine_alns_get", "uc_engine_edges_size", "uc_engine_edges_get",
     "uc_engine_stats", "uc_engine_reset_stats", "uc_setcover", "uc_write_cluster_db",
-    "uc_engine_ungapped_batch", "uc_engine_sw_batch", "uc_engine_sw_pass", "uc_engine_backtraces_size", "uc_engine_backtraces_get",
+    "uc_engine_ungapped_batch", "uc_engine_ungapped_all", "uc_engine_sw_batch", "uc_engine_sw_pass", "uc_engine_backtraces_size", "uc_engine_backtraces_get",
     "uc_backtrace_render", "uc_format_output_check", "uc_engine_tb_emit_pass", "uc_abi_version", "uc_stats_size", "uc_set_round_hook",
     "uc_t5_gemm_variant", "uc_t5_kernel_gemm", "uc_t5_kernel_rmsnorm", "uc_t5_kernel_attention", "uc_t5_kernel_cnn_head", "uc_t5_bias_table",
 )
@@ -136,6 +136,7 @@ def lib():
     L.uc_setcover.argtypes = [u32, vp, u64, vp]
     L.uc_write_cluster_db.argtypes = [C.c_char_p, u32, vp]
     L.uc_engine_ungapped_batch.argtypes = [vp, u64, vp, vp, vp, vp]
+    L.uc_engine_ungapped_all.argtypes = [vp, u32, u32, u32, u32, u64, vp, vp]
     L.uc_engine_sw_batch.argtypes = [vp, C.c_int, u64, vp, vp, vp, vp, vp, vp, vp]
     L.uc_engine_sw_pass.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, u64, vp, vp, vp, vp] + [vp] * 8
     L.uc_engine_backtraces_size.argtypes = [vp, u32, u32, C.POINTER(u64)]
@@ -547,6 +548,16 @@ class Engine:
         out = np.zeros(len(q), np.int32)
         _check(lib().uc_engine_ungapped_batch(self._h, len(q), q.ctypes.data, t.ctypes.data, diag.ctypes.data, out.ctypes.data))
         return out
+
+    def ungapped_all(self, qbegin=0, qend=None, tbegin=0, tend=None, tile_bytes=0):
+        """Rule UC-1/X (--prefilter-mode 1) on queries [qbegin, qend) x targets [tbegin, tend): dense int32 arrays (score, diag) of that shape,
+        the best ungapped score over all diagonals (capped at 255) and the smallest diagonal that reaches it.  tile_bytes: the tile budget (0 = default)."""
+        qend = self.n if qend is None else qend
+        tend = self.n if tend is None else tend
+        score = np.zeros((max(qend - qbegin, 0), max(tend - tbegin, 0)), np.int32)
+        diag = np.zeros_like(score)
+        _check(lib().uc_engine_ungapped_all(self._h, qbegin, qend, tbegin, tend, tile_bytes, score.ctypes.data, diag.ctypes.data))
+        return score, diag
 
     def sw(self, mode, q, t, qend=None, tend=None):
         q = np.ascontiguousarray(q, np.uint32); t = np.ascontiguousarray(t, np.uint32)

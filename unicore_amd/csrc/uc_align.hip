@@ -1738,7 +1738,11 @@ void Engine::sw_pass(int tab, int mode, int band, bool raw, const std::vector<Sw
         if (track) { oq.reserve(n); ot.reserve(n); rq.reserve(n); rt.reserve(n); }
         SwPlan P;
         build_plan(*this, P, tmp, nn, dq.p, dt.p, ends ? dqe.p : nullptr, ends ? dte.p : nullptr, tab, nullptr, nullptr, known ? dk.p : nullptr);
-        if (raw) launch_plan(*this, P, mode, os.p, oq.p, ot.p, work);
+        if (raw) {      // (event-timed like run_plan's launches: tools/ungapped_all_rate.py reads the pass's kernel time)
+            timed_ms_begin();
+            launch_plan(*this, P, mode, os.p, oq.p, ot.p, work);
+            stats.sw_kernel_ms += timed_ms_end();
+        }
         else run_plan(*this, P, mode, os.p, oq.p, ot.p, work, tmp);
         hipLaunchKernelGGL(scatter3_kernel, grid_for(nn), dim3(256), 0, stream, nn, P.idx.p, os.p, oq.p, ot.p, rs.p, rq.p, rt.p);
         classes();

@@ -465,6 +465,14 @@ int uc_engine_ungapped_batch(uc_engine *e, uint64_t n, const uint32_t *q, const 
     });
 }
 
+int uc_engine_ungapped_all(uc_engine *e, uint32_t qbegin, uint32_t qend, uint32_t tbegin, uint32_t tend, uint64_t tile_bytes, int32_t *score_out, int32_t *diag_out) {
+    return guard([&] {
+        require(e, "engine");
+        if (qend > qbegin && tend > tbegin) { require(score_out, "score_out"); require(diag_out, "diag_out"); }
+        e->e->ungapped_all(qbegin, qend, tbegin, tend, tile_bytes, score_out, diag_out);
+    });
+}
+
 int uc_engine_sw_batch(uc_engine *e, int mode, uint64_t n, const uint32_t *q, const uint32_t *t, const int32_t *qend_in,
                        const int32_t *tend_in, int32_t *score_out, int32_t *qend_out, int32_t *tend_out) {
     return guard([&] {

@@ -155,6 +155,29 @@ struct SwPassOut { int32_t *score, *qe, *te, *cls, *aln_len, *idents, *gaps, *mi
 // backtraces of a traceback pass run with emission (Engine::tb_emit_pass): slice i is runs[run_off[i] .. run_off[i + 1]), a run is length << 2 | op
 // (0 M, 1 I, 2 D), from the start of the alignment to its end; empty for a pair whose walk left the band.  plain[i]: the stored-int32-matrix pass served it
 struct BtPassOut { std::vector<uint64_t> run_off; std::vector<uint32_t> runs; std::vector<int32_t> plain; };
+// ---- rule UC-1/X (--prefilter-mode 1), uc_ungapped_all.hip: every query against every target, tile by tile ----
+// THE byte budget of the mode: what one (query batch x target chunk) tile may take per pair is a score byte and a 4-byte diagonal (the tile itself)
+// plus, in the worst case that EVERY pair passes --min-ungapped-score (the default 15 lets most pairs of non-trivial length through), its candidate
+// record (query, target, score, diagonal: 16 B) and the work arrays of the E4 selection (two sort keys, sorted diagonal, flag, position: 32 B).
+// A tile never exceeds this many bytes whatever the database size (UC_UNGAPPED_TILE_BYTES overrides: tests): 1 GiB = 20 M pairs, e.g. 2048 queries x
+// 9,900 targets; nothing of the mode grows with queries x targets of the whole database.
+constexpr uint64_t UNGAPPED_ALL_TILE_BYTES = 1ull << 30;
+constexpr uint64_t UNGAPPED_ALL_PAIR_BYTES = 5 + 16 + 32;
+struct UngappedAllWork {
+    DevBuf<uint8_t> score;                                // [queries of the batch][targets of the chunk]
+    DevBuf<int32_t> diag;
+    DevBuf<uint32_t> pairs, prof;                         // query pairs by length class; device-memory profiles of the long class
+    DevBuf<uint64_t> prof_off;
+};
+struct Engine;
+// queries per batch and targets per chunk of a tile under `budget_bytes`
+void ungapped_all_plan(uint64_t budget_bytes, uint32_t nq, uint32_t nt, uint32_t *qb, uint32_t *tc);
+// fills W.score / W.diag for queries [q0, q1) x targets [t0, t1) (one tile; enqueued on the engine's stream)
+void ungapped_all_tile(Engine &E, UngappedAllWork &W, uint32_t q0, uint32_t q1, uint32_t t0, uint32_t t1);
+// the tile's pairs with score >= min_score as candidate records (cq, ct, cs, cd: room for nq x nt each); returns their number
+uint64_t ungapped_all_candidates(Engine &E, const UngappedAllWork &W, uint32_t q0, uint32_t nq, uint32_t t0, uint32_t nt, int min_score,
+                                 uint32_t *cq, uint32_t *ct, int32_t *cs, int32_t *cd, unsigned long long *cursor);
+
 struct PrefilterScratch;                                  // uc_prefilter.hip
 void free_scratch(PrefilterScratch *p);
 struct AlignScratch;                                      // uc_align.hip
@@ -304,6 +327,8 @@ struct Engine {
     std::vector<uint32_t> linclust_pairs_impl(uint64_t *install);
     // kernel-level
     void ungapped_batch(uint64_t n, const uint32_t *q, const uint32_t *t, const int32_t *diag, int32_t *out);
+    // rule UC-1/X: dense [q1 - q0][t1 - t0] scores and diagonals, computed tile by tile under tile_bytes (0 = UNGAPPED_ALL_TILE_BYTES)   (uc_ungapped_all.hip)
+    void ungapped_all(uint32_t q0, uint32_t q1, uint32_t t0, uint32_t t1, uint64_t tile_bytes, int32_t *score_out, int32_t *diag_out);
     void sw_batch(int mode, const std::vector<PairIn> &pairs, int32_t *score, int32_t *qe, int32_t *te);
     void sw_pass(int tab, int mode, int band, bool raw, const std::vector<SwPassPair> &pairs, const SwPassOut &out, BtPassOut *bt = nullptr);
     // one traceback pass WITH emission on the listed boxes, by route: 0 = packed MODE 7 + walk with band `band`, 1 = the same with the whole box stored,

@@ -118,7 +118,8 @@ int option_arity(const std::string &f) {
         "--gap-open", "--gap-extend", "--spaced-kmer-pattern", "--rev-correction", "--linclust", "--kmer-per-seq", "--sym-dedup",
         "--sw-kernel", "--evalue-lambda", "--evalue-k", "--mat3di", "--mat-aa", "--cluster-mode", "--cluster-steps",
         "--alignment-type", "--alignment-mode", "--threads", "-v", "--remove-tmp-files", "--db-load-mode", "--compressed",
-        "--gpus", "--target-shards", "--mat-bit-factor-3di", "--mat-bit-factor-aa", "--comp-bias-corr", "--comp-bias-corr-scale", "--min-score-table", "--length-gate", "--format-output"};
+        "--gpus", "--target-shards", "--mat-bit-factor-3di", "--mat-bit-factor-aa", "--comp-bias-corr", "--comp-bias-corr-scale", "--min-score-table", "--length-gate", "--format-output",
+        "--prefilter-mode"};
     for (const char *v : valued) if (f == v) return 1;
     if (f == "--single-step-clustering" || f == "-a") return 2;
     return -1;
@@ -144,6 +145,11 @@ void parse_cluster_options(const std::string &opts, Params &p) {
         else if (f == "-e") { p.evalue = to_double(f, value()); if (!(p.evalue > 0)) fail(UC_ERR_ARGS, "-e must be > 0"); }
         else if (f == "-s") { p.sensitivity = (float)to_double(f, value()); }
         else if (f == "--max-seqs") { p.max_seqs = to_int(f, value()); if (p.max_seqs < 1 || p.max_seqs > 65535) fail(UC_ERR_ARGS, "--max-seqs must be in [1,65535]"); }
+        else if (f == "--prefilter-mode") {
+            p.prefilter_mode = to_int(f, value());
+            if (p.prefilter_mode == 2) fail(UC_ERR_ARGS, "--prefilter-mode 2 (no prefilter) unsupported (0 = k-mer, 1 = exhaustive ungapped)");
+            if (p.prefilter_mode != 0 && p.prefilter_mode != 1) fail(UC_ERR_ARGS, "--prefilter-mode %d unsupported (0 = k-mer, 1 = exhaustive ungapped)", p.prefilter_mode);
+        }
         else if (f == "--k-score") { p.kmer_thr = to_int(f, value()); }
         else if (f == "--min-ungapped-score") { p.min_ungapped = to_int(f, value()); }
         else if (f == "--min-diag-hits") { p.min_diag_hits = to_int(f, value()); if (p.min_diag_hits < 1) fail(UC_ERR_ARGS, "--min-diag-hits must be >= 1"); }

@@ -32,6 +32,7 @@ struct Params {
     int min_diag_hits = 2;
     int min_ungapped = 15;
     int max_seqs = 300;
+    int prefilter_mode = 0;     // 0: k-mer prefilter (E1/E2).  1 (rule UC-1/X, optional): every query against every target, all diagonals (no k-mer stage)
     // gapped alignment
     int gap_open = 10, gap_ext = 1;
     int rev_correction = 1;

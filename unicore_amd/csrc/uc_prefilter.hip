@@ -1330,12 +1330,14 @@ struct PrefilterScratch {
     DevBuf<uint64_t> d_drv, d_drv2, d_cumh, d_cumr, d_qh, d_qrn;
     DevBuf<RankRec> d_rec;
     DevBuf<uint32_t> d_kbits;       // presence bitmap of the chunk's k-mers
+    UngappedAllWork ua;             // rule UC-1/X: the score / diagonal tile, the query pairs and the long-class profiles (kept like everything here)
     // every buffer (for the size bookkeeping below)
     template <class F> void each(F f) {
         f(d_counters); f(d_temp); f(d_koff); f(k_in); f(k_out); f(d_ent32); f(v_in32); f(d_okey); f(d_okey2); f(d_oidx); f(d_order);
         f(d_ent); f(v_in); f(d_cnt); f(d_flag); f(d_cq); f(d_ct); f(d_rpidx2); f(d_qsurv); f(d_keys); f(d_keys2); f(d_pos); f(d_skey);
         f(d_skey2); f(d_rval2); f(d_qbase); f(d_soff); f(d_qr); f(d_cd); f(d_cd2); f(d_score); f(d_kflag); f(d_wflag); f(d_qk); f(d_kid); f(d_dk);
         f(d_nsimk); f(d_drk); f(d_drk2); f(d_roff); f(d_nr); f(d_src); f(d_ph); f(d_drv); f(d_drv2); f(d_cumh); f(d_cumr); f(d_qh); f(d_qrn); f(d_rec); f(d_kbits); f(d_mkey); f(d_mval); f(acc_q); f(acc_t); f(pass_q); f(pass_t); f(acc_s); f(acc_d); f(pass_s); f(pass_d);
+        f(ua.score); f(ua.diag); f(ua.pairs); f(ua.prof); f(ua.prof_off);
     }
     size_t bytes() {
         size_t b = 0;
@@ -1918,6 +1920,64 @@ static bool prefilter_chunks(Engine &E, const std::vector<std::pair<uint32_t, ui
     return true;
 }
 
+// ---- rule UC-1/X (--prefilter-mode 1): E3x on every (query, target) pair of the ranges instead of E1/E2 ------------------------------------
+// Tiles of (query batch x target chunk) under the byte budget UNGAPPED_ALL_TILE_BYTES (uc_ungapped_all.hip): the pairs of a tile that pass
+// --min-ungapped-score go through the E4 selection of the k-mer path (sort, rank, truncate to max_seqs per query) and the tile's lists are merged
+// into the running top-M accumulator of the chunked k-mer path (lossless: the tiles' pair sets are disjoint).
+static void prefilter_exhaustive(Engine &E, uint32_t tbegin, uint32_t tend, uint32_t qbegin, uint32_t qend) {
+    UC_HIP(hipSetDevice(E.device));
+    if (E.hdb.n > (1u << 24)) fail(UC_ERR_GENERIC, "prefilter: %u sequences exceed the 2^24 limit of the hit keys", E.hdb.n);
+    logf(3, "unicore-cluster: --prefilter-mode 1: all %u x %u pairs are scored on every diagonal; --k-score, --min-diag-hits and -s have no effect\n", qend - qbegin, tend - tbegin);
+    if (!E.pre) E.pre = ParkedScratch<PrefilterScratch>::take_or_new(E.device);
+    PrefilterScratch &S = *E.pre;
+    S.d_counters.reserve(8);
+    UC_HIP(hipMemsetAsync(S.d_counters.p, 0, 64, E.stream));
+    uint64_t budget = UNGAPPED_ALL_TILE_BYTES;
+    if (const char *ev = getenv("UC_UNGAPPED_TILE_BYTES")) budget = std::max<uint64_t>(1, strtoull(ev, nullptr, 10));
+    uint32_t QB = 1, TC = 1;
+    ungapped_all_plan(budget, qend - qbegin, tend - tbegin, &QB, &TC);
+    UngappedAllWork &W = S.ua;
+    PrefilterPass PP;
+    bool installed = false;       // the last tile's merge left accumulator + tile installed in the engine: no second pass over the accumulator at the end
+    const auto swap_acc = [&] { swap_hits(E, S.acc_q, S.acc_t, S.acc_s, S.acc_d); };
+    uint64_t acc_n = 0, cells = 0;
+    for (uint32_t qa = qbegin; qa < qend; qa += std::min(QB, qend - qa))
+        for (uint32_t ta = tbegin; ta < tend; ta += std::min(TC, tend - ta)) {
+            const uint32_t nq = std::min(QB, qend - qa), nt = std::min(TC, tend - ta);
+            const uint64_t np = (uint64_t)nq * nt;
+            Timer t_u;
+            E.timed_ms_begin();
+            ungapped_all_tile(E, W, qa, qa + nq, ta, ta + nt);
+            S.d_cq.reserve(np); S.d_ct.reserve(np); S.d_score.reserve(np); S.d_cd.reserve(np);
+            const uint64_t n_cand = ungapped_all_candidates(E, W, qa, nq, ta, nt, E.p.min_ungapped, S.d_cq.p, S.d_ct.p, S.d_score.p, S.d_cd.p, S.d_counters.p + 6);
+            PP.gpu_ms += E.timed_ms_end();
+            PP.t_ung += t_u.seconds();
+            PP.n_cand_total += np;
+            for (uint32_t q = qa; q < qa + nq; q++) cells += (uint64_t)E.h_len[q] * (uint64_t)(E.h_poff[ta + nt] - E.h_poff[ta]);   // (padded target residues: an upper bound)
+            if (!n_cand) continue;
+            if (installed) { swap_acc(); installed = false; }       // the installed lists are the accumulator again
+            E.n_hits = 0;
+            select_and_append(E, PP, n_cand);
+            if (!E.n_hits) continue;
+            if (!acc_n) { swap_acc(); acc_n = E.n_hits; E.n_hits = 0; continue; }
+            const uint64_t n_pass = E.n_hits;
+            swap_hits(E, S.pass_q, S.pass_t, S.pass_s, S.pass_d);
+            acc_n = E.merge_hits_dev(acc_n, S.acc_q.p, S.acc_t.p, S.acc_s.p, S.acc_d.p, n_pass, S.pass_q.p, S.pass_t.p, S.pass_s.p, S.pass_d.p, /*sorted2=*/true, 0, 1);
+            installed = true;
+        }
+    // installs the accumulated lists and rebuilds the per-query counts (an empty accumulator: empty lists) unless the last merge already did
+    if (!installed) E.merge_hits_dev(acc_n, S.acc_q.p, S.acc_t.p, S.acc_s.p, S.acc_d.p, 0, nullptr, nullptr, nullptr, nullptr, true, 0, 1);
+    uc_stats &st = E.stats;
+    st.n_candidates += PP.n_cand_total;
+    st.n_prefilter_hits += E.n_hits;
+    st.algorithmic_bytes[UC_ST_UNGAPPED] += cells / 64 + 5ull * PP.n_cand_total;      // a target residue is read once per wave (64 diagonals) + the tile bytes
+    st.algorithmic_bytes[UC_ST_SELECT] += 16ull * PP.n_cand_total;
+    st.stage_seconds[UC_ST_UNGAPPED] += PP.t_ung;
+    st.stage_seconds[UC_ST_SELECT] += PP.t_sel;
+    st.prefilter_kernel_ms += PP.gpu_ms;
+    release_scratch_for_gapped_stage(E);
+}
+
 // Large ranges are processed as several index chunks whose per-query top-M lists are
 // merged on the device (lossless, same argument as the multi-GPU shards): the double-hit filter keeps one query's
 // (target, diagonal) hashes in 2 x 2^19 LDS bits, which only works while a query has well under ~500 k k-mer hits,
@@ -1931,6 +1991,11 @@ static void prefilter_impl(Engine &E, uint32_t tbegin, uint32_t tend, uint32_t q
     if (tbegin > tend || tend > E.hdb.n) fail(UC_ERR_ARGS, "prefilter: bad target range");
     if (qend == UINT32_MAX) qend = E.hdb.n;
     if (qbegin > qend || qend > E.hdb.n) fail(UC_ERR_ARGS, "prefilter: bad query range");
+    if (E.p.prefilter_mode == 1) {      // rule UC-1/X: no k-mer stage, no chunk index, no mirror
+        if (mirror_all) fail(UC_ERR_GENERIC, "prefilter: --prefilter-mode 1 has no mirrored pass");
+        prefilter_exhaustive(E, tbegin, tend, qbegin, qend);
+        return;
+    }
     uint64_t chunk_res = E.prefilter_chunk_residues;
     if (const char *ev = getenv("UC_PREFILTER_CHUNK_RES")) chunk_res = std::max<uint64_t>(1, strtoull(ev, nullptr, 10));
     const char *sym = getenv("UC_PREFILTER_SYMMETRIC");
