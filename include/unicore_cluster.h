@@ -46,7 +46,7 @@ typedef struct uc_opts {
 /* ABI revision of this header: bumped whenever a struct below grows or an entry point changes meaning.  uc_stats is written in full by
  * uc_cluster / uc_search / uc_engine_stats and carries no size field of its own, so a caller built against an older header must check
  * uc_abi_version() == UC_ABI_VERSION (or uc_stats_size() == sizeof(uc_stats)) before passing one in. */
-#define UC_ABI_VERSION 7
+#define UC_ABI_VERSION 8
 uint32_t uc_abi_version(void);
 size_t uc_stats_size(void);
 
@@ -277,6 +277,16 @@ int uc_engine_sw_batch(uc_engine *e, int mode, uint64_t n, const uint32_t *q, co
 int uc_engine_sw_pass(uc_engine *e, int table, int mode, int band, int raw, uint64_t n, const uint32_t *q, const uint32_t *t,
                       const int32_t *box, const int32_t *known, int32_t *score_out, int32_t *qend_out, int32_t *tend_out,
                       int32_t *class_out, int32_t *aln_len_out, int32_t *idents_out, int32_t *gaps_out, int32_t *miss_out);
+/* (ABI 8) uc_engine_sw_pass with the second answer of the known-score modes 4 / 6 (anything else with a non-NULL qend2_out / tend2_out is
+ * UC_ERR_ARGS).  Among several optimal cells the pass reports the one in the first optimal column, then the first row (qend_out, tend_out); the
+ * second answer is the one in the first optimal ROW, then the first column - what the same pass reports for the pair (t, q) with the roles
+ * swapped, since the two DPs are transposes of each other (symmetric matrices).  The gapped stage uses it to serve both directions of a mutual
+ * hit from one DP.  -2 / -2 for a pair whose result did not come from the packed known-score kernel (queries beyond the systolic classes, and
+ * with raw = 0 the int32 re-runs).  Mode 6 reports it relative to the box like qend_out / tend_out. */
+int uc_engine_sw_pass2(uc_engine *e, int table, int mode, int band, int raw, uint64_t n, const uint32_t *q, const uint32_t *t,
+                       const int32_t *box, const int32_t *known, int32_t *score_out, int32_t *qend_out, int32_t *tend_out,
+                       int32_t *class_out, int32_t *aln_len_out, int32_t *idents_out, int32_t *gaps_out, int32_t *miss_out,
+                       int32_t *qend2_out, int32_t *tend2_out);
 
 /* ---- alignment backtraces (-a; ABI 7).  A backtrace is a slice of runs, each `length << 2 | op` with op 0 = M (diagonal step, match or
  * mismatch), 1 = I (query residue only), 2 = D (target residue only), from the start of the alignment to its end; adjacent runs differ in op.

@@ -62,11 +62,11 @@ SYMBOLS = (
     "uc_engine_hits_export_dev", "uc_engine_hits_import_dev", "uc_engine_setcover",
     "uc_hits_merge", "uc_engine_align", "uc_engine_alns_get", "uc_engine_edges_size", "uc_engine_edges_get",
     "uc_engine_stats", "uc_engine_reset_stats", "uc_setcover", "uc_write_cluster_db",
-    "uc_engine_ungapped_batch", "uc_engine_ungapped_all", "uc_engine_sw_batch", "uc_engine_sw_pass", "uc_engine_backtraces_size", "uc_engine_backtraces_get",
+    "uc_engine_ungapped_batch", "uc_engine_ungapped_all", "uc_engine_sw_batch", "uc_engine_sw_pass", "uc_engine_sw_pass2", "uc_engine_backtraces_size", "uc_engine_backtraces_get",
     "uc_backtrace_render", "uc_format_output_check", "uc_engine_tb_emit_pass", "uc_abi_version", "uc_stats_size", "uc_set_round_hook",
     "uc_t5_gemm_variant", "uc_t5_kernel_gemm", "uc_t5_kernel_rmsnorm", "uc_t5_kernel_attention", "uc_t5_kernel_cnn_head", "uc_t5_bias_table",
 )
-ABI_VERSION = 7      # == UC_ABI_VERSION of include/unicore_cluster.h this binding mirrors
+ABI_VERSION = 8      # == UC_ABI_VERSION of include/unicore_cluster.h this binding mirrors
 ROUND_HOOK = C.CFUNCTYPE(None, C.c_void_p, C.c_int32, C.c_uint32, C.POINTER(C.c_uint32), C.c_int32, C.c_void_p)
 
 _lib = None
@@ -139,6 +139,7 @@ def lib():
     L.uc_engine_ungapped_all.argtypes = [vp, u32, u32, u32, u32, u64, vp, vp]
     L.uc_engine_sw_batch.argtypes = [vp, C.c_int, u64, vp, vp, vp, vp, vp, vp, vp]
     L.uc_engine_sw_pass.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, u64, vp, vp, vp, vp] + [vp] * 8
+    L.uc_engine_sw_pass2.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, u64, vp, vp, vp, vp] + [vp] * 10
     L.uc_engine_backtraces_size.argtypes = [vp, u32, u32, C.POINTER(u64)]
     L.uc_engine_backtraces_get.argtypes = [vp, u32, u32, vp, vp]
     L.uc_backtrace_render.argtypes = [vp, u64, C.c_char_p, u64, C.POINTER(u64)]
@@ -602,16 +603,19 @@ class Engine:
         out["cigar"] = [render_backtrace(runs[int(off[i]):int(off[i + 1])]) if off[i + 1] > off[i] else "" for i in range(n)]
         return out
 
-    def sw_pass(self, table, mode, q, t, box=None, known=None, band=0, raw=False):
+    def sw_pass(self, table, mode, q, t, box=None, known=None, band=0, raw=False, second=False):
         """ONE gapped pass (class table, mode) on the pairs (q[i], t[i]), as Engine.align runs it (uc_engine_sw_pass):
         box [n, 4] = (qs, qe, ts, te), known [n] optimum scores.  Returns a dict of int32 arrays: score, qe, te, cls,
-        aln_len, idents, gaps, miss."""
+        aln_len, idents, gaps, miss.  second=True (modes 4 / 6, uc_engine_sw_pass2): also qe2, te2, the optimal cell in the
+        first optimal row, then the first column - the answer of the pair (t, q) with the roles swapped; -2 where absent."""
         q = np.ascontiguousarray(q, np.uint32); t = np.ascontiguousarray(t, np.uint32)
         n = len(q)
         bx = np.ascontiguousarray(box, np.int32).reshape(n, 4) if box is not None else None
         kn = np.ascontiguousarray(known, np.int32) if known is not None else None
-        out = {k: np.full(n, -1, np.int32) for k in ("score", "qe", "te", "cls", "aln_len", "idents", "gaps", "miss")}
-        _check(lib().uc_engine_sw_pass(self._h, table, mode, band, int(bool(raw)), n, q.ctypes.data, t.ctypes.data,
-                                       bx.ctypes.data if bx is not None else None, kn.ctypes.data if kn is not None else None,
-                                       *[out[k].ctypes.data for k in ("score", "qe", "te", "cls", "aln_len", "idents", "gaps", "miss")]))
+        names = ("score", "qe", "te", "cls", "aln_len", "idents", "gaps", "miss") + (("qe2", "te2") if second else ())
+        out = {k: np.full(n, -1, np.int32) for k in names}
+        fn = lib().uc_engine_sw_pass2 if second else lib().uc_engine_sw_pass
+        _check(fn(self._h, table, mode, band, int(bool(raw)), n, q.ctypes.data, t.ctypes.data,
+                  bx.ctypes.data if bx is not None else None, kn.ctypes.data if kn is not None else None,
+                  *[out[k].ctypes.data for k in names]))
         return out

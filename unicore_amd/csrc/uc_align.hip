@@ -111,6 +111,13 @@ static int pk_known_tab(uint32_t n_pairs, uint32_t n_queries) {
     return on && (double)n_pairs < 2.5 * (double)n_queries ? 3 : 1;
 }
 
+// Mutual hits take both tie-break answers from one known-score DP (uc_sw_pk_impl.hpp key2).  UC_DUAL_TIEBREAK=0: the earlier sharing rule, for A/B
+// runs - a mirror shares only where one row holds every optimal cell and is otherwise computed on its own.  The records are the same either way.
+static bool dual_tiebreak_on() {
+    static const bool on = !(getenv("UC_DUAL_TIEBREAK") && atoi(getenv("UC_DUAL_TIEBREAK")) == 0);
+    return on;
+}
+
 __device__ __forceinline__ int class_of(int lq, int tab) {
     int c = 0;
     while (c < c_tab[tab].n && c_tab[tab].cap[c] < lq) c++;
@@ -332,24 +339,31 @@ __global__ void __launch_bounds__(256) sm_gather_kernel(uint32_t n2, const uint3
     }
 }
 // results of a sub-plan (plan order k) -> natural order of the gate-passer list; uniq = the packed known-score kernel
-// found every optimal cell in one row (SW_TE_UNIQUE on the column output; results of the int32 kernel never carry it)
+// found every optimal cell in one row (SW_TE_UNIQUE on the column output; results of the int32 kernel never carry it).
+// qo2 / to2 (optional): the second answer of the packed known-score kernel (-2 where the result came from another kernel)
 __global__ void __launch_bounds__(256) sm_scatter_kernel(uint32_t na, const uint32_t *idx, const uint32_t *map, const int32_t *s,
                                                          const int32_t *qo, const int32_t *to, int32_t *s2,
-                                                         int32_t *q2o, int32_t *t2o, uint32_t *uniq) {
+                                                         int32_t *q2o, int32_t *t2o, uint32_t *uniq,
+                                                         const int32_t *qo2, const int32_t *to2, int32_t *q2o2, int32_t *t2o2) {
     for (uint32_t k = blockIdx.x * 256 + threadIdx.x; k < na; k += gridDim.x * 256) {
         const uint32_t i = map ? map[idx[k]] : idx[k];
         const int32_t te = to[k];
         const bool u = te >= 0 && (te & SW_TE_UNIQUE) != 0;
         s2[i] = s[k]; q2o[i] = qo[k]; t2o[i] = te >= 0 ? (te & ~SW_TE_UNIQUE) : te;
         if (uniq) uniq[i] = (u && qo[k] >= 0) ? 1u : 0u;
+        if (q2o2) { q2o2[i] = qo2[k]; t2o2[i] = to2[k]; }
     }
 }
+// a mirror takes its partner's second answer (first optimal row, then first column of the partner's DP = first optimal column, then first row
+// of its own, transposed one) with the roles swapped.  Where the partner has none (q2o2 null or -2: its result is not the packed known-score
+// kernel's) the one-row rule decides: share the first answer if a single row holds every optimal cell, else a run of its own (-2, round 2)
 __global__ void __launch_bounds__(256) sm_resolve_kernel(uint32_t n2, const uint32_t *partner, const uint32_t *uniq, int32_t *s2,
-                                                         int32_t *q2o, int32_t *t2o) {
+                                                         int32_t *q2o, int32_t *t2o, const int32_t *q2o2, const int32_t *t2o2) {
     for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n2; i += gridDim.x * 256) {
         const uint32_t pr = partner[i];
         if (pr == 0xFFFFFFFFu) continue;
-        if (uniq[pr]) { s2[i] = s2[pr]; q2o[i] = t2o[pr]; t2o[i] = q2o[pr]; }
+        if (q2o2 && q2o2[pr] >= 0 && t2o2[pr] >= 0) { s2[i] = s2[pr]; q2o[i] = t2o2[pr]; t2o[i] = q2o2[pr]; }
+        else if (uniq[pr]) { s2[i] = s2[pr]; q2o[i] = t2o[pr]; t2o[i] = q2o[pr]; }
         else q2o[i] = -2;
     }
 }
@@ -920,12 +934,25 @@ static void build_plan(Engine &E, SwPlan &P, DevBuf<char> &tmp, uint32_t n, cons
     P.cells = bytes[1];
 }
 
+// the second answer of a packed known-score pass (uc_sw_pk_impl.hpp key2): end under the order (first optimal row, then first column)
+struct SwSecond { int32_t *qe, *te; };
+__global__ void __launch_bounds__(256) fill2_kernel(uint32_t n, int32_t v, int32_t *a, int32_t *b) {
+    for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) { a[i] = v; b[i] = v; }
+}
+
 // one launch per populated class; outputs are in the plan's sorted order.  Returns the number of launches.
 // [t0, t1): only the tasks of that range of the plan's task list (the byte-budgeted batches of the traceback plan); skip_long: not the long-query launch
+// sec (MODE 4 / 6): where the packed known-score classes put their second answer, plan order; every other pair of the plan keeps -2 there
 static uint64_t launch_plan(Engine &E, SwPlan &P, int mode, int32_t *os, int32_t *oqe, int32_t *ote, DevBuf<int32_t> &work,
-                            const uint32_t *tb = nullptr, bool only_long = false, uint32_t t0 = 0, uint32_t t1 = 0xFFFFFFFFu, bool skip_long = false) {
+                            const uint32_t *tb = nullptr, bool only_long = false, uint32_t t0 = 0, uint32_t t1 = 0xFFFFFFFFu, bool skip_long = false,
+                            const SwSecond *sec = nullptr) {
     const ClassTable &tab = h_tab[P.tab];
     SwArgs a;
+    if (sec) {
+        if (mode != 4 && mode != 6) fail(UC_ERR_GENERIC, "second tie-break answer asked of a pass that has none");
+        hipLaunchKernelGGL(fill2_kernel, grid_for(P.n), dim3(256), 0, E.stream, P.n, -2, sec->qe, sec->te);
+        a.oqe2 = sec->qe; a.ote2 = sec->te;
+    }
     a.db = E.ddb; a.tasks = P.tasks.p; a.pt = P.st.p; a.pqe = P.sqe.p; a.pte = P.ste.p;
     a.pqs = P.has_starts ? P.sqs.p : nullptr; a.pts = P.has_starts ? P.sts.p : nullptr;
     a.oscore = os; a.oqe = oqe; a.ote = ote; a.open = E.p.gap_open; a.ext = E.p.gap_ext;
@@ -980,6 +1007,21 @@ __global__ void __launch_bounds__(256) pk_flag_kernel(uint32_t n_pk, const int32
 __global__ void __launch_bounds__(256) amb_flag_kernel(uint32_t n2, const int32_t *qe2, uint32_t *flag) {
     for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n2; i += gridDim.x * 256) flag[i] = qe2[i] == -2 ? 1u : 0u;
 }
+// Both tie-break answers from one DP: a flagged mirror (mirror[link[i]]) whose representative sits right before it in the gate-passer list and
+// is flagged too does not run - the representative's known-score re-run reports the mirror's end as its second answer (dual[i - 1] = 1).  A flagged
+// representative got its -2 from a packed class of the forward pass, with a score below the packed range: every table of the known-score
+// pass holds it in a packed class again (pk_cap: their common row limit), and its re-run cannot overflow.
+__global__ void __launch_bounds__(256) amb_dual_kernel(uint32_t n2, const int32_t *qe2, const uint32_t *q2, const uint32_t *link, const uint32_t *mirror,
+                                                       const uint32_t *len, uint32_t pk_cap, uint32_t *flag, uint32_t *dual) {
+    for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n2; i += gridDim.x * 256) {
+        const bool f = qe2[i] == -2;
+        const uint32_t j = link[i];
+        const bool shared = f && i > 0 && mirror[j] && !mirror[j - 1] && link[i - 1] == j - 1 && qe2[i - 1] == -2 && len[q2[i - 1]] <= pk_cap;
+        flag[i] = (f && !shared) ? 1u : 0u;
+        const bool serves = qe2[i] == -2 && !mirror[j] && i + 1 < n2 && link[i + 1] == j + 1 && mirror[j + 1] && qe2[i + 1] == -2 && len[q2[i]] <= pk_cap;
+        dual[i] = serves ? 1u : 0u;
+    }
+}
 __global__ void __launch_bounds__(256) amb_gather_kernel(uint32_t n2, const uint32_t *flag, const uint32_t *pos, const uint32_t *q2,
                                                          const uint32_t *t2, const uint32_t *link, const int32_t *s0, uint32_t *q3,
                                                          uint32_t *t3, uint32_t *link3, int32_t *s3) {
@@ -989,13 +1031,21 @@ __global__ void __launch_bounds__(256) amb_gather_kernel(uint32_t n2, const uint
         q3[w] = q2[i]; t3[w] = t2[i]; link3[w] = i; s3[w] = s0[link[i]];
     }
 }
+// dual (optional): entry j + 1 of the gate-passer list is the mirror that entry j's run serves - its end is the second answer, roles swapped
 __global__ void __launch_bounds__(256) amb_putback_kernel(uint32_t n3, const uint32_t *idx3, const uint32_t *link3, const uint32_t *link,
                                                           const int32_t *qe3, const int32_t *te3, int32_t *qe2, int32_t *te2,
-                                                          int32_t *qe0, int32_t *te0) {
+                                                          int32_t *qe0, int32_t *te0, const uint32_t *dual, const int32_t *qe3b,
+                                                          const int32_t *te3b, uint32_t *err) {
     for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n3; i += gridDim.x * 256) {
         const uint32_t j = link3[idx3[i]];
         qe2[j] = qe3[i]; te2[j] = te3[i];
         qe0[link[j]] = qe3[i]; te0[link[j]] = te3[i];
+        if (dual && dual[j]) {
+            const int32_t mq = te3b[i], mt = qe3b[i];
+            if (mq < 0 || mt < 0) atomicAdd(err, 1u);   // cannot happen (amb_dual_kernel); checked by the host at the stage's next synchronisation
+            qe2[j + 1] = mq; te2[j + 1] = mt;
+            qe0[link[j + 1]] = mq; te0[link[j + 1]] = mt;
+        }
     }
 }
 __global__ void __launch_bounds__(256) pk_gather_kernel(uint32_t n_pk, const uint32_t *flag, const uint32_t *pos, const uint32_t *sq,
@@ -1009,18 +1059,20 @@ __global__ void __launch_bounds__(256) pk_gather_kernel(uint32_t n_pk, const uin
     }
 }
 __global__ void __launch_bounds__(256) pk_putback_kernel(uint32_t n2, const uint32_t *idx2, const uint32_t *link, const int32_t *s,
-                                                         const int32_t *qe, const int32_t *te, int32_t *os, int32_t *oqe, int32_t *ote) {
+                                                         const int32_t *qe, const int32_t *te, int32_t *os, int32_t *oqe, int32_t *ote,
+                                                         int32_t *oqe2, int32_t *ote2) {
     for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n2; i += gridDim.x * 256) {
         const uint32_t o = link[idx2[i]];
         os[o] = s[i];
         if (oqe) { oqe[o] = qe[i]; ote[o] = te[i]; }
+        if (oqe2) { oqe2[o] = -2; ote2[o] = -2; }   // the int32 kernel reports one tie-break order only
     }
 }
 
 
 struct RerunBufs {
-    DevBuf<uint32_t> flag, pos, q2, t2, link;
-    DevBuf<int32_t> qe2, te2, s, qe, te, sin;
+    DevBuf<uint32_t> flag, pos, q2, t2, link, dual, err;
+    DevBuf<int32_t> qe2, te2, s, qe, te, sin, qeb, teb;
 };
 
 // Work buffers of the gapped stage and of the set-cover graph build.  ONE set per engine (parked per device between
@@ -1031,7 +1083,7 @@ struct AlignScratch {
     DevBuf<uint32_t> gflag, gpos, q1, t1, link1, q2, t2, link, eflag, epos, mism, d_e;
     DevBuf<uint64_t> ukey, ukey2;
     DevBuf<uint32_t> uidx_in, uidx, fq, ft, mirror, rep, rpos, qr, tr, jrep, rcopy;
-    DevBuf<int32_t> su, qeu, teu, s2s, q2os, t2os, qe2a, te2a, sknown;
+    DevBuf<int32_t> su, qeu, teu, s2s, q2os, t2os, qe2a, te2a, sknown, q2os2, t2os2, q2o2, t2o2;
     DevBuf<uint32_t> iota2, smkeep, smpos, partner, uniq, q2a, t2a, mapa;
     DevBuf<uint32_t> lg_q, lg_t, lg_map, lg_flag, lg_pos;   // rule UC-1/L: the compacted pair list of a batch and its records
     DevBuf<uc_aln> lg_alns;
@@ -1064,10 +1116,10 @@ static AlignScratch &scratch_of(Engine &E) {
 
 // ovf_only: re-run immediately only what saturated; ambiguous end rows (qe == -2) are left for the caller
 static void run_plan(Engine &E, SwPlan &P, int mode, int32_t *os, int32_t *oqe, int32_t *ote, DevBuf<int32_t> &work,
-                     DevBuf<char> &tmp, bool ovf_only = false) {
+                     DevBuf<char> &tmp, bool ovf_only = false, const SwSecond *sec = nullptr) {
     if (!P.n) return;
     E.timed_ms_begin();
-    uint64_t launches = launch_plan(E, P, mode, os, oqe, ote, work);
+    uint64_t launches = launch_plan(E, P, mode, os, oqe, ote, work, nullptr, false, 0, 0xFFFFFFFFu, false, sec);
     double ms = E.timed_ms_end();
     const uint32_t n_pk = packed_prefix(P).pairs;
     if (n_pk) {
@@ -1091,7 +1143,7 @@ static void run_plan(Engine &E, SwPlan &P, int mode, int32_t *os, int32_t *oqe, 
             E.stats.cells_run += P2.cells;
             E.stats.n_sw_runs += P2.n;
             hipLaunchKernelGGL(pk_putback_kernel, grid_for(n2), dim3(256), 0, s, n2, P2.idx.p, B.link.p, B.s.p,
-                               oqe ? B.qe.p : nullptr, oqe ? B.te.p : nullptr, os, oqe, ote);
+                               oqe ? B.qe.p : nullptr, oqe ? B.te.p : nullptr, os, oqe, ote, sec ? sec->qe : nullptr, sec ? sec->te : nullptr);
             UC_HIP(hipGetLastError());
         }
     }
@@ -1106,23 +1158,36 @@ static void run_plan(Engine &E, SwPlan &P, int mode, int32_t *os, int32_t *oqe, 
 // exact (qEnd, tEnd) for the gate-passing pairs whose end is still unknown (ambiguous end row of the packed kernel, or a
 // mirror that could not take its representative's end): a second forward pass that KNOWS the optimum score (packed
 // MODE 4; int32 kernel for --sw-kernel i32 and for queries beyond the systolic classes)
+// mirror (null: no mutual-hit sharing in this batch): with the packed kernel, the run of a flagged representative also serves its flagged mirror
+// (amb_dual_kernel) - one DP, both tie-break answers
 static void fix_ambiguous_ends(Engine &E, uint32_t n2, const uint32_t *q2, const uint32_t *t2, int32_t *qe2, int32_t *te2,
                                const uint32_t *link, const int32_t *s0, int32_t *qe0, int32_t *te0, DevBuf<int32_t> &work,
-                               DevBuf<char> &tmp, uint32_t n_queries) {
+                               DevBuf<char> &tmp, uint32_t n_queries, const uint32_t *mirror) {
     RerunBufs &B = scratch_of(E).amb_B;
     SwPlan &P3 = scratch_of(E).amb_P3;
     hipStream_t s = E.stream;
+    const bool pk = E.p.sw_pk != 0;
+    const bool dual = pk && mirror && dual_tiebreak_on();
     B.flag.reserve(n2); B.pos.reserve(n2);
-    hipLaunchKernelGGL(amb_flag_kernel, grid_for(n2), dim3(256), 0, s, n2, qe2, B.flag.p);
+    if (dual) {
+        B.dual.reserve(n2);
+        if (!B.err.p) { B.err.reserve(1); UC_HIP(hipMemsetAsync(B.err.p, 0, 4, s)); }
+        hipLaunchKernelGGL(amb_dual_kernel, grid_for(n2), dim3(256), 0, s, n2, qe2, q2, link, mirror, E.ddb.len,
+                           (uint32_t)std::min(h_tab[1].cap[h_tab[1].n - 1], h_tab[3].cap[h_tab[3].n - 1]), B.flag.p, B.dual.p);
+    } else {
+        hipLaunchKernelGGL(amb_flag_kernel, grid_for(n2), dim3(256), 0, s, n2, qe2, B.flag.p);
+    }
     const uint32_t n3 = compact(E, tmp, B.flag.p, B.pos.p, n2);
     E.stats.n_pk_reruns += n3;
     if (!n3) return;
     B.q2.reserve(n3); B.t2.reserve(n3); B.link.reserve(n3); B.s.reserve(n3); B.qe.reserve(n3); B.te.reserve(n3); B.sin.reserve(n3);
+    if (dual) { B.qeb.reserve(n3); B.teb.reserve(n3); }
     hipLaunchKernelGGL(amb_gather_kernel, grid_for(n2), dim3(256), 0, s, n2, B.flag.p, B.pos.p, q2, t2, link, s0, B.q2.p, B.t2.p, B.link.p, B.sin.p);
-    const bool pk = E.p.sw_pk != 0;
     build_plan(E, P3, tmp, n3, B.q2.p, B.t2.p, nullptr, nullptr, pk ? pk_known_tab(n3, n_queries) : 0, nullptr, nullptr, pk ? B.sin.p : nullptr);
-    run_plan(E, P3, pk ? 4 : 0, B.s.p, B.qe.p, B.te.p, work, tmp);
-    hipLaunchKernelGGL(amb_putback_kernel, grid_for(n3), dim3(256), 0, s, n3, P3.idx.p, B.link.p, link, B.qe.p, B.te.p, qe2, te2, qe0, te0);
+    const SwSecond sec{B.qeb.p, B.teb.p};
+    run_plan(E, P3, pk ? 4 : 0, B.s.p, B.qe.p, B.te.p, work, tmp, false, dual ? &sec : nullptr);
+    hipLaunchKernelGGL(amb_putback_kernel, grid_for(n3), dim3(256), 0, s, n3, P3.idx.p, B.link.p, link, B.qe.p, B.te.p, qe2, te2, qe0, te0,
+                       dual ? B.dual.p : nullptr, B.qeb.p, B.teb.p, B.err.p);
     UC_HIP(hipGetLastError());
 }
 
@@ -1292,13 +1357,15 @@ static void evalue_gate(Engine &E, AlignBatch &B) {
         hipLaunchKernelGGL(gate_scatter_kernel, grid_for(n), dim3(256), 0, s, n, A.gflag.p, A.gpos.p, B.Lsq, B.Lst, A.qe0.p, A.te0.p,
                            A.q2.p, A.t2.p, A.qe2.p, A.te2.p, A.link.p);
         if (E.p.sw_pk || B.dedup)
-            fix_ambiguous_ends(E, n2, A.q2.p, A.t2.p, A.qe2.p, A.te2.p, A.link.p, A.s0.p, A.qe0.p, A.te0.p, A.work, A.tmp, B.qb - B.qa);
+            fix_ambiguous_ends(E, n2, A.q2.p, A.t2.p, A.qe2.p, A.te2.p, A.link.p, A.s0.p, A.qe0.p, A.te0.p, A.work, A.tmp, B.qb - B.qa,
+                               B.dedup ? A.mirror.p : nullptr);
     }
     hipLaunchKernelGGL(aln_basic_kernel, grid_for(n), dim3(256), 0, s, n, B.Lidx, A.s0.p, s1p, A.qe0.p, A.te0.p, A.gflag.p, B.alns_b);
 }
 
 // one known-score start pass (packed MODE 6; the optimum of the start pass is the forward score) over the m gate passers flagged in smkeep
-static void known_start_round(Engine &E, const AlignBatch &B, SwPlan &P, uint32_t m, int tab, uint32_t *uniq) {
+// dual: round 1 - the second answer of every pair goes to q2o2 / t2o2 for the mirrors that share the DP
+static void known_start_round(Engine &E, const AlignBatch &B, SwPlan &P, uint32_t m, int tab, uint32_t *uniq, bool dual) {
     AlignScratch &A = scratch_of(E);
     hipStream_t s = E.stream;
     A.q2a.reserve(m); A.t2a.reserve(m); A.qe2a.reserve(m); A.te2a.reserve(m); A.mapa.reserve(m);
@@ -1307,9 +1374,12 @@ static void known_start_round(Engine &E, const AlignBatch &B, SwPlan &P, uint32_
     A.sknown.reserve(m);
     hipLaunchKernelGGL(sm_score_kernel, grid_for(m), dim3(256), 0, s, m, A.mapa.p, A.link.p, A.s0.p, A.sknown.p);
     build_plan(E, P, A.tmp, m, A.q2a.p, A.t2a.p, A.qe2a.p, A.te2a.p, tab, nullptr, nullptr, A.sknown.p);
-    run_plan(E, P, 6, A.s2s.p, A.q2os.p, A.t2os.p, A.work, A.tmp);
+    if (dual) { A.q2os2.reserve(m); A.t2os2.reserve(m); }
+    const SwSecond sec{A.q2os2.p, A.t2os2.p};
+    run_plan(E, P, 6, A.s2s.p, A.q2os.p, A.t2os.p, A.work, A.tmp, false, dual ? &sec : nullptr);
     hipLaunchKernelGGL(sm_scatter_kernel, grid_for(m), dim3(256), 0, s, m, P.idx.p, A.mapa.p, A.s2s.p, A.q2os.p, A.t2os.p,
-                       A.s2.p, A.q2o.p, A.t2o.p, uniq);
+                       A.s2.p, A.q2o.p, A.t2o.p, uniq, dual ? A.q2os2.p : nullptr, dual ? A.t2os2.p : nullptr,
+                       dual ? A.q2o2.p : nullptr, dual ? A.t2o2.p : nullptr);
 }
 
 // start pass of the shared-DP path on the packed kernel
@@ -1321,14 +1391,18 @@ static void start_pass_known(Engine &E, AlignBatch &B) {
     UC_HIP(hipMemsetAsync(A.uniq.p, 0, (size_t)n2 * 4, s));
     hipLaunchKernelGGL(sm_flag_kernel, grid_for(n2), dim3(256), 0, s, n2, A.link.p, A.mirror.p, A.gflag.p, A.gpos.p, A.qe2.p, A.te2.p,
                        A.qe0.p, A.te0.p, A.smkeep.p, A.partner.p);
-    // round 1: exact in one pass, and it reports whether a single row holds every optimal cell
-    known_start_round(E, B, A.P2, compact(E, A.tmp, A.smkeep.p, A.smpos.p, n2), B.tab, A.uniq.p);
-    hipLaunchKernelGGL(sm_resolve_kernel, grid_for(n2), dim3(256), 0, s, n2, A.partner.p, A.uniq.p, A.s2.p, A.q2o.p, A.t2o.p);
-    // round 2: the mirrors that could not take their partner's result
+    // round 1: exact in one pass; it reports both tie-break answers, and whether a single row holds every optimal cell
+    const bool dual = dual_tiebreak_on();
+    if (dual) { A.q2o2.reserve(n2); A.t2o2.reserve(n2); }
+    known_start_round(E, B, A.P2, compact(E, A.tmp, A.smkeep.p, A.smpos.p, n2), B.tab, A.uniq.p, dual);
+    hipLaunchKernelGGL(sm_resolve_kernel, grid_for(n2), dim3(256), 0, s, n2, A.partner.p, A.uniq.p, A.s2.p, A.q2o.p, A.t2o.p,
+                       dual ? A.q2o2.p : nullptr, dual ? A.t2o2.p : nullptr);
+    // round 2: the mirrors that could not take their partner's result - with both answers at hand only those whose partner's result came from
+    // another kernel than the packed known-score one (int32 re-runs, queries beyond the systolic classes)
     hipLaunchKernelGGL(amb_flag_kernel, grid_for(n2), dim3(256), 0, s, n2, A.q2o.p, A.smkeep.p);
     const uint32_t n2b = compact(E, A.tmp, A.smkeep.p, A.smpos.p, n2);
     if (!n2b) return;
-    known_start_round(E, B, A.P2b, n2b, pk_known_tab(n2b, B.qb - B.qa), nullptr);
+    known_start_round(E, B, A.P2b, n2b, pk_known_tab(n2b, B.qb - B.qa), nullptr, false);
     E.stats.n_pk_reruns += n2b;
 }
 
@@ -1348,11 +1422,15 @@ static void start_pass(Engine &E, AlignBatch &B) {
         build_plan(E, A.P2, A.tmp, n2, A.q2.p, A.t2.p, A.qe2.p, A.te2.p, B.tab);
         run_plan(E, A.P2, 2, A.s2s.p, A.q2os.p, A.t2os.p, A.work, A.tmp);
         hipLaunchKernelGGL(sm_scatter_kernel, grid_for(n2), dim3(256), 0, s, n2, A.P2.idx.p, (const uint32_t *)nullptr, A.s2s.p, A.q2os.p,
-                           A.t2os.p, A.s2.p, A.q2o.p, A.t2o.p, (uint32_t *)nullptr);
+                           A.t2os.p, A.s2.p, A.q2o.p, A.t2o.p, (uint32_t *)nullptr, (const int32_t *)nullptr, (const int32_t *)nullptr,
+                           (int32_t *)nullptr, (int32_t *)nullptr);
     }
     unsigned long long hc = 0;
+    uint32_t dual_err = 0;
     UC_HIP(hipMemcpyAsync(&hc, A.d_cells.p, 8, hipMemcpyDeviceToHost, s));
+    if (A.amb_B.err.p) UC_HIP(hipMemcpyAsync(&dual_err, A.amb_B.err.p, 4, hipMemcpyDeviceToHost, s));
     UC_HIP(hipStreamSynchronize(s));
+    if (dual_err) fail(UC_ERR_GENERIC, "gapped stage: %u shared end re-runs came back without a second answer", dual_err);
     E.stats.cells_start += hc;
     hipLaunchKernelGGL(finalize_kernel, grid_for(n2), dim3(256), 0, s, n2, A.iota2.p, A.link.p, B.Lidx, A.q2.p, A.t2.p, A.s2.p,
                        A.q2o.p, A.t2o.p, E.ddb.len, E.p.cov, E.p.cov_mode, B.alns_b, A.eflag.p, A.mism.p);
@@ -1736,18 +1814,26 @@ void Engine::sw_pass(int tab, int mode, int band, bool raw, const std::vector<Sw
         DevBuf<char> tmp;
         os.reserve(n); rs.reserve(n);
         if (track) { oq.reserve(n); ot.reserve(n); rq.reserve(n); rt.reserve(n); }
+        // the second tie-break answer of the known-score modes (-2 for a pair that the packed known-score kernel did not compute)
+        const bool second = o.qe2 || o.te2;
+        if (second && mode != 4 && mode != 6) fail(UC_ERR_ARGS, "sw_pass: only modes 4 and 6 have a second answer");
+        DevBuf<int32_t> oq2, ot2, rq2, rt2;
+        if (second) { oq2.reserve(n); ot2.reserve(n); rq2.reserve(n); rt2.reserve(n); }
+        const SwSecond sec{oq2.p, ot2.p};
         SwPlan P;
         build_plan(*this, P, tmp, nn, dq.p, dt.p, ends ? dqe.p : nullptr, ends ? dte.p : nullptr, tab, nullptr, nullptr, known ? dk.p : nullptr);
         if (raw) {      // (event-timed like run_plan's launches: tools/ungapped_all_rate.py reads the pass's kernel time)
             timed_ms_begin();
-            launch_plan(*this, P, mode, os.p, oq.p, ot.p, work);
+            launch_plan(*this, P, mode, os.p, oq.p, ot.p, work, nullptr, false, 0, 0xFFFFFFFFu, false, second ? &sec : nullptr);
             stats.sw_kernel_ms += timed_ms_end();
         }
-        else run_plan(*this, P, mode, os.p, oq.p, ot.p, work, tmp);
+        else run_plan(*this, P, mode, os.p, oq.p, ot.p, work, tmp, false, second ? &sec : nullptr);
         hipLaunchKernelGGL(scatter3_kernel, grid_for(nn), dim3(256), 0, stream, nn, P.idx.p, os.p, oq.p, ot.p, rs.p, rq.p, rt.p);
+        if (second) hipLaunchKernelGGL(scatter3_kernel, grid_for(nn), dim3(256), 0, stream, nn, P.idx.p, oq2.p, oq2.p, ot2.p, rq2.p, rq2.p, rt2.p);
         classes();
         down(o.score, rs.p);
         if (track) { down(o.qe, rq.p); down(o.te, rt.p); }
+        if (second) { down(o.qe2, rq2.p); down(o.te2, rt2.p); }
         UC_HIP(hipStreamSynchronize(stream));
         UC_HIP(hipGetLastError());
         return;

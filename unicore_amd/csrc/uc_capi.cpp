@@ -490,6 +490,14 @@ int uc_engine_sw_batch(uc_engine *e, int mode, uint64_t n, const uint32_t *q, co
 int uc_engine_sw_pass(uc_engine *e, int table, int mode, int band, int raw, uint64_t n, const uint32_t *q, const uint32_t *t,
                       const int32_t *box, const int32_t *known, int32_t *score_out, int32_t *qend_out, int32_t *tend_out,
                       int32_t *class_out, int32_t *aln_len_out, int32_t *idents_out, int32_t *gaps_out, int32_t *miss_out) {
+    return uc_engine_sw_pass2(e, table, mode, band, raw, n, q, t, box, known, score_out, qend_out, tend_out, class_out, aln_len_out, idents_out,
+                              gaps_out, miss_out, nullptr, nullptr);
+}
+
+int uc_engine_sw_pass2(uc_engine *e, int table, int mode, int band, int raw, uint64_t n, const uint32_t *q, const uint32_t *t,
+                       const int32_t *box, const int32_t *known, int32_t *score_out, int32_t *qend_out, int32_t *tend_out,
+                       int32_t *class_out, int32_t *aln_len_out, int32_t *idents_out, int32_t *gaps_out, int32_t *miss_out,
+                       int32_t *qend2_out, int32_t *tend2_out) {
     return guard([&] {
         require(e, "engine");
         if (!n) return;
@@ -503,7 +511,9 @@ int uc_engine_sw_pass(uc_engine *e, int table, int mode, int band, int raw, uint
             x.qs = box ? box[4 * i] : 0; x.qe = box ? box[4 * i + 1] : 0; x.ts = box ? box[4 * i + 2] : 0; x.te = box ? box[4 * i + 3] : 0;
             x.known = known ? known[i] : 0;
         }
-        e->e->sw_pass(table, mode, band, raw != 0, pairs, {score_out, qend_out, tend_out, class_out, aln_len_out, idents_out, gaps_out, miss_out});
+        if ((qend2_out || tend2_out) && mode != 4 && mode != 6) fail(UC_ERR_ARGS, "sw_pass: only modes 4 and 6 have a second answer");
+        e->e->sw_pass(table, mode, band, raw != 0, pairs,
+                      {score_out, qend_out, tend_out, class_out, aln_len_out, idents_out, gaps_out, miss_out, qend2_out, tend2_out});
     });
 }
 

@@ -57,6 +57,9 @@ struct SwArgs {
     // mode 3: what the traceback statistic adds per path step (diagonal step, identical AA on it, first residue of a gap,
     // further gap residues).  Default = (alignment length << 16 | identities); (0,0,1,0) counts the gaps instead.
     uint32_t tb_diag = 0x10000u, tb_ident = 1u, tb_open = 0x10000u, tb_ext = 0x10000u;
+    // packed modes 4/6 (optional, null = not written): the end under the other tie-break order - first optimal row, then first column - which is the
+    // answer of the transposed DP (the mirror of a mutual hit).  Last in the struct: the other kernels' argument offsets stay where they were.
+    int32_t *oqe2 = nullptr, *ote2 = nullptr;
 };
 
 constexpr int SW_MAX_ROWS = 2048;   // largest single-strip class (G=64, R=32)

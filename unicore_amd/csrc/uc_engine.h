@@ -151,7 +151,8 @@ struct PairIn { uint32_t q, t; int32_t qe, te; };
 struct SwPassPair { uint32_t q, t; int32_t qs, qe, ts, te, known; };
 // its outputs in list order (any may be null): score, qe, te (MODE 0 / 2 / 4 / 6; te keeps SW_TE_UNIQUE), class id of the table,
 // traceback statistics (MODE 3 / 7) and the band-miss mark of the MODE 7 walk
-struct SwPassOut { int32_t *score, *qe, *te, *cls, *aln_len, *idents, *gaps, *miss; };
+struct SwPassOut { int32_t *score, *qe, *te, *cls, *aln_len, *idents, *gaps, *miss;
+                   int32_t *qe2 = nullptr, *te2 = nullptr; };   // MODE 4 / 6: the end under the other tie-break order (first optimal row, then first column)
 // backtraces of a traceback pass run with emission (Engine::tb_emit_pass): slice i is runs[run_off[i] .. run_off[i + 1]), a run is length << 2 | op
 // (0 M, 1 I, 2 D), from the start of the alignment to its end; empty for a pair whose walk left the band.  plain[i]: the stored-int32-matrix pass served it
 struct BtPassOut { std::vector<uint64_t> run_off; std::vector<uint32_t> runs; std::vector<int32_t> plain; };

@@ -113,10 +113,13 @@ __global__ void __launch_bounds__(NW * 64) sw_pk_kernel(const SwArgs a) {
     uint32_t H[R], E[R], rowbest[(TRACK && !KNOWN) ? R : 1];   // E[r] holds the gap state ENTERING the next column (no separate H - open array)
     uint32_t mskA[MASK ? RW : 1], mskB[MASK ? RW : 1];
     uint32_t best = 0, Hlast = 0, prevHup = 0, fout = 0;
+    // KNOWN: colA / colB hold the lane's whole first-answer state in one register, so that the second key below costs no occupancy step:
+    // -1 = no optimal cell yet, else first optimal column << 6 | its first row (of this lane's R) << 1 | this lane saw the optimum in more than one of its rows
     int colA = -1, colB = -1;
-    [[maybe_unused]] int rowA = 0, rowB = 0;
-    [[maybe_unused]] bool multA = false, multB = false;   // KNOWN: this lane saw the optimum in more than one of its rows
     [[maybe_unused]] uint32_t knownA = 0, knownB = 0;
+    // KNOWN: the other tie-break order over this lane's optimal cells, (first optimal row, then first column) = row << 16 | col: the answer of the
+    // transposed DP, i.e. of the mirror (t,q) of a mutual hit.  Only touched inside the event branch.
+    [[maybe_unused]] int key2A = 0x7fffffff, key2B = 0x7fffffff;
     uint32_t gA = 0, gB = 0, toffA = 0, toffB = 0;
     [[maybe_unused]] unsigned long long tbA = 0, tbB = 0;
     [[maybe_unused]] int tsaA = 0, tsbA = 0, tsaB = 0, tsbB = 0;        // MODE 7: the steps in which this lane is inside the pair's stored band
@@ -249,7 +252,7 @@ __global__ void __launch_bounds__(NW * 64) sw_pk_kernel(const SwArgs a) {
         if constexpr (KNOWN) {
             knownA = (uint32_t)a.pscore[gA];
             knownB = vB ? (uint32_t)a.pscore[gB] : 0u;
-            rowA = 0; rowB = 0; multA = false; multB = false;
+            key2A = 0x7fffffff; key2B = 0x7fffffff;
         }
         best = 0; colA = -1; colB = -1; Hlast = 0; prevHup = 0; fout = 0;
         lst = 0;
@@ -350,15 +353,17 @@ __global__ void __launch_bounds__(NW * 64) sw_pk_kernel(const SwArgs a) {
                     int first = 0, cnt = 0;
 #pragma unroll
                     for (int r = R - 1; r >= 0; r--) { const bool hit = (H[r] & 0xffffu) == knownA; first = hit ? r : first; cnt += hit ? 1 : 0; }
-                    if (colA < 0) { colA = st - g; rowA = first; }
-                    multA |= cnt > 1 || first != rowA;
+                    if (colA < 0) colA = ((st - g) << 6) | (first << 1);
+                    if constexpr (MODE == 6) colA |= (cnt > 1 || first != ((colA >> 1) & 31)) ? 1 : 0;   // (only MODE 6 reports the one-row mark)
+                    key2A = min(key2A, ((g * R + first) << 16) | (st - g));   // columns ascend: a smaller row wins, an equal row keeps the earlier column
                 }
                 if (evB) {
                     int first = 0, cnt = 0;
 #pragma unroll
                     for (int r = R - 1; r >= 0; r--) { const bool hit = (H[r] >> 16) == knownB; first = hit ? r : first; cnt += hit ? 1 : 0; }
-                    if (colB < 0) { colB = st - g; rowB = first; }
-                    multB |= cnt > 1 || first != rowB;
+                    if (colB < 0) colB = ((st - g) << 6) | (first << 1);
+                    if constexpr (MODE == 6) colB |= (cnt > 1 || first != ((colB >> 1) & 31)) ? 1 : 0;
+                    key2B = min(key2B, ((g * R + first) << 16) | (st - g));
                 }
             }
         }
@@ -374,14 +379,16 @@ __global__ void __launch_bounds__(NW * 64) sw_pk_kernel(const SwArgs a) {
         if constexpr (KNOWN) {
 #pragma unroll
             for (int half = 0; half < 2; half++) {
-                const int col = half ? colB : colA, row = half ? rowB : rowA;
-                int key = col < 0 ? 0x7fffffff : ((col << 11) | (g * R + row));      // (first optimal column, then first row)
+                const int st1 = half ? colB : colA, col = st1 >> 6, row = (st1 >> 1) & 31;
+                int key = st1 < 0 ? 0x7fffffff : ((col << 11) | (g * R + row));      // (first optimal column, then first row)
                 // lanes that saw the optimum, + G if one of them saw it in two rows: exactly 1 <=> one row holds every optimal cell
-                int nrows = (col < 0 ? 0 : 1) + ((half ? multB : multA) ? G : 0);
+                int nrows = st1 < 0 ? 0 : 1 + ((st1 & 1) ? G : 0);
+                int key2 = half ? key2B : key2A;                                      // (first optimal row, then first column)
 #pragma unroll
                 for (int m = 1; m < G; m <<= 1) {
                     key = min(key, __shfl_xor(key, m, 64));
                     nrows += __shfl_xor(nrows, m, 64);
+                    key2 = min(key2, __shfl_xor(key2, m, 64));
                 }
                 const bool valid = half ? vB : true;
                 const uint32_t gp = half ? gB : gA;
@@ -392,6 +399,10 @@ __global__ void __launch_bounds__(NW * 64) sw_pk_kernel(const SwArgs a) {
                     a.oqe[gp] = found ? (key & 2047) - rowoff : -2;
                     // MODE 6 marks "one row only" in the column output (SW_TE_UNIQUE): the mirror of such a pair shares its result
                     a.ote[gp] = found ? ((key >> 11) | ((MODE == 6 && nrows == 1) ? SW_TE_UNIQUE : 0)) : -2;
+                    if (a.oqe2) {   // the second answer: what the mirror of the pair reports, with the roles swapped
+                        a.oqe2[gp] = found ? (key2 >> 16) - rowoff : -2;
+                        a.ote2[gp] = found ? (key2 & 0xffff) : -2;
+                    }
                 }
             }
             return;
