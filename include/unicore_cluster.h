@@ -46,7 +46,7 @@ typedef struct uc_opts {
 /* ABI revision of this header: bumped whenever a struct below grows or an entry point changes meaning.  uc_stats is written in full by
  * uc_cluster / uc_search / uc_engine_stats and carries no size field of its own, so a caller built against an older header must check
  * uc_abi_version() == UC_ABI_VERSION (or uc_stats_size() == sizeof(uc_stats)) before passing one in. */
-#define UC_ABI_VERSION 8
+#define UC_ABI_VERSION 9
 uint32_t uc_abi_version(void);
 size_t uc_stats_size(void);
 
@@ -247,6 +247,14 @@ int uc_setcover(uint32_t n, const uint32_t *edges, uint64_t n_edges, uint32_t *a
 /* the same result with the graph built on the engine's GPU (sort + unique of the edge list) and only the greedy
  * cover on the host: what uc_cluster and the bench step use */
 int uc_engine_setcover(uc_engine *e, const uint32_t *edges, uint64_t n_edges, uint32_t *assign);
+/* (ABI 9) E7 by clustering rule.  mode 0 = the greedy set cover (uc_setcover's result); mode 2 = greedy incremental (rule UC-1/G, what
+ * `--cluster-mode 2` runs): the same undirected graph on the pairs, self loops and duplicates dropped; the nodes are walked by len descending (ties:
+ * ascending id), an unassigned node becomes a representative and takes all its still-unassigned neighbours.  Any other mode is UC_ERR_ARGS.
+ * uc_cluster_graph is the host variant (no device needed); len[n] = residue counts, may be NULL for mode 0. */
+int uc_cluster_graph(uint32_t n, const uint32_t *edges, uint64_t n_edges, const uint32_t *len, int32_t mode, uint32_t *assign);
+/* the device variant: n and the lengths are those of the engine's database; graph, rounds and assignment on the engine's GPU.  mode 0 gives
+ * uc_engine_setcover's result. */
+int uc_engine_cluster_graph(uc_engine *e, int32_t mode, const uint32_t *edges, uint64_t n_edges, uint32_t *assign);
 /* E8/E9 outputs from an assignment: cluster DB (<prefix>, .index, .dbtype) */
 int uc_write_cluster_db(const char *out_cluster_db, uint32_t n, const uint32_t *assign);
 

@@ -65,8 +65,9 @@ SYMBOLS = (
     "uc_engine_ungapped_batch", "uc_engine_ungapped_all", "uc_engine_sw_batch", "uc_engine_sw_pass", "uc_engine_sw_pass2", "uc_engine_backtraces_size", "uc_engine_backtraces_get",
     "uc_backtrace_render", "uc_format_output_check", "uc_engine_tb_emit_pass", "uc_abi_version", "uc_stats_size", "uc_set_round_hook",
     "uc_t5_gemm_variant", "uc_t5_kernel_gemm", "uc_t5_kernel_rmsnorm", "uc_t5_kernel_attention", "uc_t5_kernel_cnn_head", "uc_t5_bias_table",
+    "uc_cluster_graph", "uc_engine_cluster_graph",
 )
-ABI_VERSION = 8      # == UC_ABI_VERSION of include/unicore_cluster.h this binding mirrors
+ABI_VERSION = 9      # == UC_ABI_VERSION of include/unicore_cluster.h this binding mirrors
 ROUND_HOOK = C.CFUNCTYPE(None, C.c_void_p, C.c_int32, C.c_uint32, C.POINTER(C.c_uint32), C.c_int32, C.c_void_p)
 
 _lib = None
@@ -134,6 +135,8 @@ def lib():
     L.uc_engine_reset_stats.argtypes = [vp]
     L.uc_engine_reset_stats.restype = None
     L.uc_setcover.argtypes = [u32, vp, u64, vp]
+    L.uc_cluster_graph.argtypes = [u32, vp, u64, vp, i32, vp]
+    L.uc_engine_cluster_graph.argtypes = [vp, i32, vp, u64, vp]
     L.uc_write_cluster_db.argtypes = [C.c_char_p, u32, vp]
     L.uc_engine_ungapped_batch.argtypes = [vp, u64, vp, vp, vp, vp]
     L.uc_engine_ungapped_all.argtypes = [vp, u32, u32, u32, u32, u64, vp, vp]
@@ -236,6 +239,18 @@ def setcover(n, edges):
     e = np.ascontiguousarray(edges, np.uint32).reshape(-1, 2)
     assign = np.zeros(n, np.uint32)
     _check(lib().uc_setcover(n, e.ctypes.data, len(e), assign.ctypes.data))
+    return assign
+
+
+def cluster_graph(n, edges, lens, mode):
+    """E7 on the host by rule (uc_cluster_graph): mode 0 = greedy set cover, 2 = greedy incremental (--cluster-mode 2: longest sequence first,
+    ties by ascending id; lens[n] = residue counts, may be None for mode 0).  Needs no device."""
+    e = np.ascontiguousarray(edges, np.uint32).reshape(-1, 2)
+    ln = np.ascontiguousarray(lens, np.uint32) if lens is not None else None
+    if ln is not None and len(ln) != n:
+        raise ValueError("lens has %d entries for %d nodes" % (len(ln), n))
+    assign = np.zeros(n, np.uint32)
+    _check(lib().uc_cluster_graph(n, e.ctypes.data, len(e), ln.ctypes.data if ln is not None else None, mode, assign.ctypes.data))
     return assign
 
 
@@ -505,6 +520,14 @@ class Engine:
         e = np.ascontiguousarray(edges, np.uint32).reshape(-1, 2)
         assign = np.zeros(self.n, np.uint32)
         _check(lib().uc_engine_setcover(self._h, e.ctypes.data, len(e), assign.ctypes.data))
+        return assign
+
+    def cluster_graph(self, edges, mode):
+        """E7 on this engine's GPU by rule (uc_engine_cluster_graph): mode 0 = greedy set cover (== setcover()), 2 = greedy incremental with the
+        lengths of the engine's database (same result as cluster_graph() of the module)"""
+        e = np.ascontiguousarray(edges, np.uint32).reshape(-1, 2)
+        assign = np.zeros(self.n, np.uint32)
+        _check(lib().uc_engine_cluster_graph(self._h, mode, e.ctypes.data, len(e), assign.ctypes.data))
         return assign
 
     def align(self, qbegin=0, qend=None):

@@ -1108,6 +1108,7 @@ struct AlignScratch {
     DevBuf<uint64_t> sc_m1;
     DevBuf<uint64_t> sc_key, sc_key2, sc_ukey, sc_doff;
     DevBuf<char> sc_tmp;
+    GreedyIncScratch gi;             // --cluster-mode 2 (uc_greedy_inc.hip): same graph buffers, its own round state
 };
 static AlignScratch &scratch_of(Engine &E) {
     if (!E.aln) E.aln = ParkedScratch<AlignScratch>::take_or_new(E.device);
@@ -2189,6 +2190,12 @@ __global__ void __launch_bounds__(256) sc_induced_kernel(uint32_t left, const ui
 __global__ void sc_next_round_kernel(uint32_t *ctr) { ctr[0] = ctr[3]; ctr[1] = 0; ctr[2] = 0; ctr[3] = 0; }
 
 void Engine::set_cover_own_edges(uint32_t n, uint32_t *assign) {
+    if (p.cluster_mode != 0) {      // --cluster-mode 2: the same three sources, the greedy incremental rule (uc_greedy_inc.hip)
+        if (edges_on_host) cluster_graph_device(p.cluster_mode, n, edges.data(), edges.size() / 2, assign);
+        else if (n_edges_dev >= (1ull << 31)) { const std::vector<uint32_t> &h = host_edges(); cluster_graph(n, h.data(), h.size() / 2, h_len.data(), p.cluster_mode, assign); }
+        else cluster_graph_dev_edges(n, d_edges.p, n_edges_dev, assign);
+        return;
+    }
     if (edges_on_host) { set_cover_device(n, edges.data(), edges.size() / 2, assign); return; }
     if (n_edges_dev >= (1ull << 31)) { const std::vector<uint32_t> &h = host_edges(); set_cover(n, h.data(), h.size() / 2, assign); return; }
     set_cover_graph(n, nullptr, d_edges.p, n_edges_dev, assign);
@@ -2199,46 +2206,82 @@ void Engine::set_cover_device(uint32_t n, const uint32_t *h_edges, uint64_t n_ed
     set_cover_graph(n, h_edges, nullptr, n_edges, assign);
 }
 
-// the graph (CSR, both directions, duplicates and self loops removed) on the device from a host or a device edge list, then the
-// greedy cover on the device as well (parallel rounds of local maxima: the host cover's assignment, uc_setcover.cpp, exactly)
+GreedyIncScratch &Engine::greedy_inc_scratch() { return scratch_of(*this).gi; }
+
+// the graph (CSR, both directions, duplicates and self loops removed) on the device from a host or a device edge list (n_edges > 0): the step
+// both clustering rules start from.  The arrays live in the engine's scratch and stay valid until the next graph build
+DevGraph Engine::build_cluster_graph(uint32_t n, const uint32_t *h_edges, const uint32_t *dev_edges, uint64_t n_edges) {
+    Timer t_graph;
+    AlignScratch &A = scratch_of(*this);
+    const uint64_t m = 2 * n_edges;
+    DevBuf<uint32_t> &d_e = A.sc_e, &flag = A.sc_flag, &pos = A.sc_pos, &d_adj = A.sc_dadj, &bad = A.sc_bad;
+    DevBuf<uint64_t> &key = A.sc_key, &key2 = A.sc_key2, &ukey = A.sc_ukey, &d_off = A.sc_doff;
+    DevBuf<char> &tmp = A.sc_tmp;
+    key.reserve(m); key2.reserve(m); flag.reserve(m); pos.reserve(m); bad.reserve(1); d_off.reserve((size_t)n + 1);
+    const uint32_t *e_in = dev_edges;
+    if (!e_in) {
+        d_e.reserve(m);
+        UC_HIP(hipMemcpyAsync(d_e.p, h_edges, m * 4, hipMemcpyHostToDevice, stream));
+        e_in = d_e.p;
+    }
+    UC_HIP(hipMemsetAsync(bad.p, 0, 4, stream));
+    hipLaunchKernelGGL(edge_key_kernel, grid_for(n_edges), dim3(256), 0, stream, n_edges, e_in, n, key.p, bad.p);
+    rocprim_call(tmp, [&](void *t, size_t &b) { return rocprim::radix_sort_keys(t, b, key.p, key2.p, (size_t)m, 0u, 64u, stream); });
+    hipLaunchKernelGGL(edge_uniq_kernel, grid_for(m), dim3(256), 0, stream, m, key2.p, flag.p);
+    const uint32_t mu = compact(*this, tmp, flag.p, pos.p, (uint32_t)m);
+    uint32_t hbad = 0;
+    UC_HIP(hipMemcpy(&hbad, bad.p, 4, hipMemcpyDeviceToHost));
+    if (hbad) fail(UC_ERR_ARGS, "set cover: %u edges with an endpoint out of range", hbad);
+    ukey.reserve(std::max<uint32_t>(mu, 1)); d_adj.reserve(std::max<uint32_t>(mu, 1));
+    hipLaunchKernelGGL(edge_adj_kernel, grid_for(m), dim3(256), 0, stream, m, key2.p, flag.p, pos.p, ukey.p, d_adj.p);
+    hipLaunchKernelGGL(edge_off_kernel, grid_for((uint64_t)n + 1), dim3(256), 0, stream, n, ukey.p, (uint64_t)mu, d_off.p);
+    UC_HIP(hipGetLastError());
+    if (getenv("UC_TIMING")) { UC_HIP(hipStreamSynchronize(stream)); fprintf(stderr, "set_cover_device: graph on the GPU %.2f ms\n", t_graph.seconds() * 1e3); }
+    return DevGraph{d_off.p, d_adj.p, mu};
+}
+
+// the subgraph the still-undecided nodes (mark[v] == SC_NONE) of the work list induce, for a host finish: their ids ascending (`back`) and the edges
+// among them in that numbering (`e2`, each once), gathered on the device (count pass, then an append pass; the order of the edge list does not matter)
+void Engine::induced_subgraph(const DevGraph &G, uint32_t left, const uint32_t *d_work, const uint32_t *d_mark, std::vector<uint32_t> &back, std::vector<uint32_t> &e2) {
+    DevBuf<unsigned long long> ecnt;
+    ecnt.reserve(1);
+    UC_HIP(hipMemsetAsync(ecnt.p, 0, 8, stream));
+    hipLaunchKernelGGL(sc_induced_kernel, grid_for(left), dim3(256), 0, stream, left, d_work, G.off, G.adj, d_mark, (uint32_t *)nullptr, ecnt.p);
+    unsigned long long ne2 = 0;
+    UC_HIP(hipMemcpyAsync(&ne2, ecnt.p, 8, hipMemcpyDeviceToHost, stream));
+    UC_HIP(hipStreamSynchronize(stream));
+    DevBuf<uint32_t> de2;
+    de2.reserve(2 * std::max<unsigned long long>(ne2, 1));
+    UC_HIP(hipMemsetAsync(ecnt.p, 0, 8, stream));
+    if (ne2) hipLaunchKernelGGL(sc_induced_kernel, grid_for(left), dim3(256), 0, stream, left, d_work, G.off, G.adj, d_mark, de2.p, ecnt.p);
+    back.resize(left); e2.resize(2 * (size_t)ne2);
+    UC_HIP(hipMemcpyAsync(back.data(), d_work, (size_t)left * 4, hipMemcpyDeviceToHost, stream));
+    if (ne2) UC_HIP(hipMemcpyAsync(e2.data(), de2.p, 2 * (size_t)ne2 * 4, hipMemcpyDeviceToHost, stream));
+    UC_HIP(hipStreamSynchronize(stream));
+    UC_HIP(hipGetLastError());
+    std::sort(back.begin(), back.end());                                   // ids keep their order: so do the ties
+    auto sub = [&](uint32_t v) { return (uint32_t)(std::lower_bound(back.begin(), back.end(), v) - back.begin()); };
+    for (uint32_t &x : e2) x = sub(x);
+}
+
+// the graph on the device (build_cluster_graph), then the greedy cover on the device as well (parallel rounds of local maxima: the host cover's
+// assignment, uc_setcover.cpp, exactly)
 void Engine::set_cover_graph(uint32_t n, const uint32_t *h_edges, const uint32_t *dev_edges, uint64_t n_edges, uint32_t *assign) {
     PressureScope ps(*this, 1);
     UC_HIP(hipSetDevice(device));
-    Timer t_graph;
     AlignScratch &A = scratch_of(*this);
     if (n_edges) {
-        const uint64_t m = 2 * n_edges;
-        DevBuf<uint32_t> &d_e = A.sc_e, &flag = A.sc_flag, &pos = A.sc_pos, &d_adj = A.sc_dadj, &bad = A.sc_bad;
-        DevBuf<uint64_t> &key = A.sc_key, &key2 = A.sc_key2, &ukey = A.sc_ukey, &d_off = A.sc_doff;
-        DevBuf<char> &tmp = A.sc_tmp;
-        key.reserve(m); key2.reserve(m); flag.reserve(m); pos.reserve(m); bad.reserve(1); d_off.reserve((size_t)n + 1);
-        const uint32_t *e_in = dev_edges;
-        if (!e_in) {
-            d_e.reserve(m);
-            UC_HIP(hipMemcpyAsync(d_e.p, h_edges, m * 4, hipMemcpyHostToDevice, stream));
-            e_in = d_e.p;
-        }
-        UC_HIP(hipMemsetAsync(bad.p, 0, 4, stream));
-        hipLaunchKernelGGL(edge_key_kernel, grid_for(n_edges), dim3(256), 0, stream, n_edges, e_in, n, key.p, bad.p);
-        rocprim_call(tmp, [&](void *t, size_t &b) { return rocprim::radix_sort_keys(t, b, key.p, key2.p, (size_t)m, 0u, 64u, stream); });
-        hipLaunchKernelGGL(edge_uniq_kernel, grid_for(m), dim3(256), 0, stream, m, key2.p, flag.p);
-        const uint32_t mu = compact(*this, tmp, flag.p, pos.p, (uint32_t)m);
-        uint32_t hbad = 0;
-        UC_HIP(hipMemcpy(&hbad, bad.p, 4, hipMemcpyDeviceToHost));
-        if (hbad) fail(UC_ERR_ARGS, "set cover: %u edges with an endpoint out of range", hbad);
-        ukey.reserve(std::max<uint32_t>(mu, 1)); d_adj.reserve(std::max<uint32_t>(mu, 1));
-        hipLaunchKernelGGL(edge_adj_kernel, grid_for(m), dim3(256), 0, stream, m, key2.p, flag.p, pos.p, ukey.p, d_adj.p);
-        hipLaunchKernelGGL(edge_off_kernel, grid_for((uint64_t)n + 1), dim3(256), 0, stream, n, ukey.p, (uint64_t)mu, d_off.p);
-        UC_HIP(hipGetLastError());
+        const DevGraph G = build_cluster_graph(n, h_edges, dev_edges, n_edges);
+        const uint64_t *d_off = G.off;
+        const uint32_t *d_adj = G.adj;
         const bool timing = getenv("UC_TIMING") != nullptr;
-        if (timing) { UC_HIP(hipStreamSynchronize(stream)); fprintf(stderr, "set_cover_device: graph on the GPU %.2f ms\n", t_graph.seconds() * 1e3); }
         // the greedy cover itself, on the device too (parallel rounds, see above): neither the adjacency (2 x edges x 4 bytes) nor the serial
         // host sweep — rank 0's Amdahl term of an N-GPU pass — is left; only the assignment comes back
         Timer t_greedy;
         DevBuf<uint32_t> &d_assign = A.sc_assign, &d_cnt = A.sc_cnt, &w0 = A.sc_work, &w1 = A.sc_work2, &picks = A.sc_picks, &newly = A.sc_newly, &ctr = A.sc_ctr;
         DevBuf<uint64_t> &m1 = A.sc_m1;
         d_assign.reserve(n); d_cnt.reserve(n); w0.reserve(n); w1.reserve(n); picks.reserve(n); newly.reserve(n); ctr.reserve(4); m1.reserve(n);
-        hipLaunchKernelGGL(sc_init_kernel, grid_for(n), dim3(256), 0, stream, n, d_off.p, d_assign.p, d_cnt.p, w0.p);
+        hipLaunchKernelGGL(sc_init_kernel, grid_for(n), dim3(256), 0, stream, n, d_off, d_assign.p, d_cnt.p, w0.p);
         const uint32_t h_ctr[4] = {n, 0, 0, 0};
         UC_HIP(hipMemcpyAsync(ctr.p, h_ctr, 16, hipMemcpyHostToDevice, stream));
         uint32_t left = n, rounds = 0;
@@ -2246,10 +2289,10 @@ void Engine::set_cover_graph(uint32_t n, const uint32_t *h_edges, const uint32_t
         uint32_t *cur = w0.p, *nxt = w1.p;
         while (left) {
             const dim3 gw((uint32_t)std::min<uint64_t>(((uint64_t)left + 3) / 4, 1u << 16));
-            hipLaunchKernelGGL(sc_m1_kernel, gw, dim3(256), 0, stream, (const uint32_t *)ctr.p, (const uint32_t *)cur, d_off.p, d_adj.p, d_assign.p, d_cnt.p, m1.p);
-            hipLaunchKernelGGL(sc_pick_kernel, gw, dim3(256), 0, stream, ctr.p, (const uint32_t *)cur, d_off.p, d_adj.p, d_assign.p, d_cnt.p, m1.p, picks.p);
-            hipLaunchKernelGGL(sc_apply_kernel, gw, dim3(256), 0, stream, ctr.p, (const uint32_t *)picks.p, d_off.p, d_adj.p, d_assign.p, newly.p);
-            hipLaunchKernelGGL(sc_dec_kernel, gw, dim3(256), 0, stream, (const uint32_t *)ctr.p, (const uint32_t *)newly.p, d_off.p, d_adj.p, d_assign.p, d_cnt.p);
+            hipLaunchKernelGGL(sc_m1_kernel, gw, dim3(256), 0, stream, (const uint32_t *)ctr.p, (const uint32_t *)cur, d_off, d_adj, d_assign.p, d_cnt.p, m1.p);
+            hipLaunchKernelGGL(sc_pick_kernel, gw, dim3(256), 0, stream, ctr.p, (const uint32_t *)cur, d_off, d_adj, d_assign.p, d_cnt.p, m1.p, picks.p);
+            hipLaunchKernelGGL(sc_apply_kernel, gw, dim3(256), 0, stream, ctr.p, (const uint32_t *)picks.p, d_off, d_adj, d_assign.p, newly.p);
+            hipLaunchKernelGGL(sc_dec_kernel, gw, dim3(256), 0, stream, (const uint32_t *)ctr.p, (const uint32_t *)newly.p, d_off, d_adj, d_assign.p, d_cnt.p);
             hipLaunchKernelGGL(sc_compact_kernel, grid_for(left), dim3(256), 0, stream, ctr.p, (const uint32_t *)cur, d_assign.p, nxt);
             uint32_t h[4];
             UC_HIP(hipMemcpyAsync(h, ctr.p, 16, hipMemcpyDeviceToHost, stream));
@@ -2268,28 +2311,10 @@ void Engine::set_cover_graph(uint32_t n, const uint32_t *h_edges, const uint32_t
         UC_HIP(hipStreamSynchronize(stream));
         UC_HIP(hipGetLastError());
         if (host_tail) {
-            // r06: only the subgraph the `left` unassigned nodes induce goes to the host - their ids and the edges among them, gathered on the
-            // device (count pass, then an append pass; the order of the edge list does not matter to the cover) - not the whole adjacency (4 B x 10^9 entries
-            // over PCIe plus an O(n) scan at nominal sizes, however few nodes were left)
-            DevBuf<unsigned long long> ecnt;
-            ecnt.reserve(1);
-            UC_HIP(hipMemsetAsync(ecnt.p, 0, 8, stream));
-            hipLaunchKernelGGL(sc_induced_kernel, grid_for(left), dim3(256), 0, stream, left, (const uint32_t *)cur, d_off.p, d_adj.p, d_assign.p, (uint32_t *)nullptr, ecnt.p);
-            unsigned long long ne2 = 0;
-            UC_HIP(hipMemcpyAsync(&ne2, ecnt.p, 8, hipMemcpyDeviceToHost, stream));
-            UC_HIP(hipStreamSynchronize(stream));
-            DevBuf<uint32_t> de2;
-            de2.reserve(2 * std::max<unsigned long long>(ne2, 1));
-            UC_HIP(hipMemsetAsync(ecnt.p, 0, 8, stream));
-            if (ne2) hipLaunchKernelGGL(sc_induced_kernel, grid_for(left), dim3(256), 0, stream, left, (const uint32_t *)cur, d_off.p, d_adj.p, d_assign.p, de2.p, ecnt.p);
-            std::vector<uint32_t> back(left), e2(2 * (size_t)ne2);
-            UC_HIP(hipMemcpyAsync(back.data(), cur, (size_t)left * 4, hipMemcpyDeviceToHost, stream));
-            if (ne2) UC_HIP(hipMemcpyAsync(e2.data(), de2.p, 2 * (size_t)ne2 * 4, hipMemcpyDeviceToHost, stream));
-            UC_HIP(hipStreamSynchronize(stream));
-            UC_HIP(hipGetLastError());
-            std::sort(back.begin(), back.end());                                   // ids keep their order: so do the ties
-            auto sub = [&](uint32_t v) { return (uint32_t)(std::lower_bound(back.begin(), back.end(), v) - back.begin()); };
-            for (uint32_t &x : e2) x = sub(x);
+            // r06: only the subgraph the `left` unassigned nodes induce goes to the host - their ids and the edges among them - not the whole
+            // adjacency (4 B x 10^9 entries over PCIe plus an O(n) scan at nominal sizes, however few nodes were left)
+            std::vector<uint32_t> back, e2;
+            induced_subgraph(G, left, cur, d_assign.p, back, e2);
             std::vector<uint32_t> a2(back.size());
             set_cover((uint32_t)back.size(), e2.data(), e2.size() / 2, a2.data());
             for (size_t i = 0; i < back.size(); i++) assign[back[i]] = back[a2[i]];

@@ -448,6 +448,29 @@ int uc_engine_setcover(uc_engine *e, const uint32_t *edges, uint64_t n_edges, ui
     });
 }
 
+int uc_cluster_graph(uint32_t n, const uint32_t *edges, uint64_t n_edges, const uint32_t *len, int32_t mode, uint32_t *assign) {
+    return guard([&] {
+        if (mode != 0 && mode != 2) fail(UC_ERR_ARGS, "uc_cluster_graph: mode %d unsupported (0 = greedy set cover, 2 = greedy incremental)", mode);
+        if (n) require(assign, "assign");
+        if (n_edges) require(edges, "edges");
+        if (n && mode == 2) require(len, "len");
+        cluster_graph(n, edges, n_edges, len, mode, assign);
+    });
+}
+
+int uc_engine_cluster_graph(uc_engine *e, int32_t mode, const uint32_t *edges, uint64_t n_edges, uint32_t *assign) {
+    return guard([&] {
+        require(e, "engine");
+        if (mode != 0 && mode != 2) fail(UC_ERR_ARGS, "uc_engine_cluster_graph: mode %d unsupported (0 = greedy set cover, 2 = greedy incremental)", mode);
+        const uint32_t n = e->e->hdb.n;
+        if (n) require(assign, "assign");
+        if (n_edges) require(edges, "edges");
+        Timer tc;
+        e->e->cluster_graph_device(mode, n, edges, n_edges, assign);
+        e->e->stats.stage_seconds[UC_ST_SETCOVER] += tc.seconds();
+    });
+}
+
 int uc_write_cluster_db(const char *out_cluster_db, uint32_t n, const uint32_t *assign) {
     return guard([&] {
         require(out_cluster_db, "out_cluster_db");
@@ -763,11 +786,12 @@ int uc_cluster(const char *db, const char *out_cluster_db, const char *tmp, cons
                 if (r == 0) {
                     Timer tc;
                     std::vector<uint32_t> sa(m);
-                    if (W > 1 && n_acc < (1ull << 31)) E.set_cover_graph(m, nullptr, dev_all, n_acc, sa.data());
-                    else if (W > 1) {   // beyond the 32-bit positions of the device graph build: the all-host cover
+                    // the rule is p.cluster_mode (0 = set cover, 2 = greedy incremental on the round's lengths) in all three branches
+                    if (W > 1 && n_acc < (1ull << 31)) E.cluster_graph_dev_edges(m, dev_all, n_acc, sa.data());
+                    else if (W > 1) {   // beyond the 32-bit positions of the device graph build: the all-host variant
                         std::vector<uint32_t> all(2 * n_acc);
                         UC_HIP(hipMemcpy(all.data(), dev_all, 2 * n_acc * 4, hipMemcpyDeviceToHost));
-                        set_cover(m, all.data(), n_acc, sa.data());
+                        cluster_graph(m, all.data(), n_acc, E.h_len.data(), E.p.cluster_mode, sa.data());
                     }
                     else E.set_cover_own_edges(m, sa.data());      // one rank: graph straight from the device-resident edge list
                     // mergeclusters: the representative of a sequence is the representative of its representative

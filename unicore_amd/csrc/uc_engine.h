@@ -179,6 +179,16 @@ void ungapped_all_tile(Engine &E, UngappedAllWork &W, uint32_t q0, uint32_t q1, 
 uint64_t ungapped_all_candidates(Engine &E, const UngappedAllWork &W, uint32_t q0, uint32_t nq, uint32_t t0, uint32_t nt, int min_score,
                                  uint32_t *cq, uint32_t *ct, int32_t *cs, int32_t *cd, unsigned long long *cursor);
 
+// ---- E7: the clustering graph on the device and the work buffers of the greedy incremental rule (--cluster-mode 2, uc_greedy_inc.hip) ----
+// CSR of the undirected graph on the accepted pairs: node v's neighbours are adj[off[v] .. off[v + 1]), ascending, unique, no self loops
+struct DevGraph { const uint64_t *off = nullptr; const uint32_t *adj = nullptr; uint64_t n_adj = 0; };
+// kept in the engine's AlignScratch beside the sc_* buffers of the set cover, so that a warm call allocates nothing
+struct GreedyIncScratch {
+    DevBuf<uint64_t> key, key2;                           // (length descending, id ascending) sort keys
+    DevBuf<uint32_t> order, rank, state, work, work2, ctr, assign, err, tail_id, tail_rep;
+    DevBuf<char> tmp;
+};
+
 struct PrefilterScratch;                                  // uc_prefilter.hip
 void free_scratch(PrefilterScratch *p);
 struct AlignScratch;                                      // uc_align.hip
@@ -322,6 +332,16 @@ struct Engine {
     void set_cover_device(uint32_t n, const uint32_t *h_edges, uint64_t n_edges, uint32_t *assign);
     void set_cover_own_edges(uint32_t n, uint32_t *assign);   // the engine's own (device-resident) edge list
     void set_cover_graph(uint32_t n, const uint32_t *h_edges, const uint32_t *dev_edges, uint64_t n_edges, uint32_t *assign);
+    // the graph build both clustering rules share (n_edges > 0; from a host or a device edge list), and the subgraph that the undecided nodes
+    // (mark[v] == 0xFFFFFFFF) of a work list induce, renumbered by ascending id, for a host finish          (uc_align.hip)
+    DevGraph build_cluster_graph(uint32_t n, const uint32_t *h_edges, const uint32_t *dev_edges, uint64_t n_edges);
+    void induced_subgraph(const DevGraph &G, uint32_t left, const uint32_t *d_work, const uint32_t *d_mark, std::vector<uint32_t> &back, std::vector<uint32_t> &e2);
+    GreedyIncScratch &greedy_inc_scratch();
+    // rule UC-1/G (--cluster-mode 2): greedy incremental clustering of the resident database's n sequences on the device     (uc_greedy_inc.hip)
+    void greedy_inc_graph(uint32_t n, const uint32_t *h_edges, const uint32_t *dev_edges, uint64_t n_edges, uint32_t *assign);
+    // E7 by rule (0 = set cover, 2 = greedy incremental) from a host edge list, and by p.cluster_mode from a device edge list (n_edges < 2^31)
+    void cluster_graph_device(int mode, uint32_t n, const uint32_t *h_edges, uint64_t n_edges, uint32_t *assign);
+    void cluster_graph_dev_edges(uint32_t n, const uint32_t *dev_edges, uint64_t n_edges, uint32_t *assign);
     // E8a: (centre, member) candidate pairs of the linear-time pre-step for the resident DB, sorted by (centre, member), unique (uc_linclust.hip)
     std::vector<uint32_t> linclust_pairs();
     uint64_t linclust_hits();                                        // ... installed as the hit lists (query = centre); returns the pair count
@@ -341,6 +361,8 @@ struct Engine {
 };
 
 void set_cover(uint32_t n, const uint32_t *edges, uint64_t n_edges, uint32_t *assign);
+// E7 on the host by rule: 0 = set_cover, 2 = greedy incremental (len[n]: residue counts; longest first, ties by ascending id)   (uc_setcover.cpp)
+void cluster_graph(uint32_t n, const uint32_t *edges, uint64_t n_edges, const uint32_t *len, int mode, uint32_t *assign);
 void merge_hits(uint32_t n, int max_seqs, int n_parts, const uint32_t *const *counts, const uc_hit *const *hits,
                 std::vector<uint32_t> &out_cnt, std::vector<uc_hit> &out_hits);
 const char *last_error_cstr();

@@ -585,11 +585,11 @@ uint64_t cluster_step(Engine &E, Comm &C, int target_shards, uint32_t *assign) {
     if (C.rank == 0) {
         if (!assign && n) fail(UC_ERR_ARGS, "cluster_step: rank 0 needs an assignment buffer");
         Timer tc;
-        if (n_all < (1ull << 31)) E.set_cover_graph(n, nullptr, dev_all, n_all, assign);     // the graph is built from the buffer the edges landed in
-        else {   // beyond the 32-bit positions of the device graph build: the all-host cover
+        if (n_all < (1ull << 31)) E.cluster_graph_dev_edges(n, dev_all, n_all, assign);     // the graph is built from the buffer the edges landed in; the rule is E.p.cluster_mode
+        else {   // beyond the 32-bit positions of the device graph build: the all-host variant
             std::vector<uint32_t> all(2 * n_all);
             UC_HIP(hipMemcpy(all.data(), dev_all, 2 * n_all * 4, hipMemcpyDeviceToHost));
-            set_cover(n, all.data(), n_all, assign);
+            cluster_graph(n, all.data(), n_all, E.h_len.data(), E.p.cluster_mode, assign);
         }
         E.stats.algorithmic_bytes[UC_ST_SETCOVER] += 8ull * n_all + 4ull * n;
         E.stats.stage_seconds[UC_ST_SETCOVER] += tc.seconds();

@@ -171,7 +171,11 @@ void parse_cluster_options(const std::string &opts, Params &p) {
         else if (f == "--comp-bias-corr-scale") { const double v = to_double(f, value()); if (v < 0 || v > 8) fail(UC_ERR_ARGS, "--comp-bias-corr-scale must be in [0,8]"); p.comp_bias_milli = (int)std::lround(v * 1000.0); }
         else if (f == "--min-score-table") { p.min_score_table_path = value(); }
         else if (f == "--length-gate") { p.len_gate = to_int(f, value()) != 0; }
-        else if (f == "--cluster-mode") { p.cluster_mode = to_int(f, value()); if (p.cluster_mode != 0) fail(UC_ERR_ARGS, "--cluster-mode %d unsupported (only 0 = greedy set cover)", p.cluster_mode); }
+        else if (f == "--cluster-mode") {
+            const int m = to_int(f, value());
+            if (m != 0 && m != 2 && m != 3) fail(UC_ERR_ARGS, "--cluster-mode %d unsupported (0 = greedy set cover, 2 = greedy incremental, 3 = the same rule: run as 2)", m);
+            p.cluster_mode = m == 3 ? 2 : m;      // rule UC-1/G; Foldseek's 3 is the low-memory form of 2
+        }
         else if (f == "--single-step-clustering") { p.single_step = opt_bool(); p.single_step_given = true; }
         else if (f == "-a") { p.want_bt = opt_bool(); /* implies want_tb where alignments are kept: uc_search, uc_engine_create */ }
         else if (f == "--format-output") { p.format_output = value(); /* read by convertalis only */ }

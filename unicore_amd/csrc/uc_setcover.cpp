@@ -1,4 +1,4 @@
-// uc_setcover.cpp — stage E7: greedy set cover on the host (the north star keeps it host-side).
+// uc_setcover.cpp — stage E7 on the host: greedy set cover (the north star keeps it host-side) and, behind cluster_graph, the greedy incremental rule.
 // Stands for MMseqs2 `clust --cluster-mode 0` inside `foldseek cluster` (cluster.rs:45-56).
 // Rule (spec UC-1): undirected graph on accepted pairs; repeatedly the unassigned node covering the most
 // unassigned nodes (its neighbours + itself; ties: smallest id) becomes a representative and takes all its
@@ -150,6 +150,45 @@ void set_cover(uint32_t n, const uint32_t *edges, uint64_t n_edges, uint32_t *as
     lap("sort");
     greedy_cover(n, off.data(), adj, deg.data(), assign);
     lap("greedy");
+}
+
+// Rule UC-1/G (--cluster-mode 2, greedy incremental, CD-HIT-like): the same undirected graph; the nodes are walked by length descending (ties: ascending
+// id), an unassigned node becomes a representative and takes all its still-unassigned neighbours.  Self loops and duplicate pairs change nothing, so the
+// adjacency is a plain counting sort.  The all-host variant: uc_cluster_graph, edge lists beyond the device build's 32-bit positions, and the finisher
+// of a chain-like tail of the device rounds (uc_greedy_inc.hip).
+static void greedy_incremental(uint32_t n, const uint32_t *edges, uint64_t n_edges, const uint32_t *len, uint32_t *assign) {
+    constexpr uint32_t NONE = UINT32_MAX;
+    if (n && !len) fail(UC_ERR_ARGS, "cluster graph: mode 2 needs the sequence lengths");
+    std::vector<uint64_t> off((size_t)n + 1, 0);
+    for (uint64_t e = 0; e < n_edges; e++) {
+        const uint32_t a = edges[2 * e], b = edges[2 * e + 1];
+        if (a >= n || b >= n) fail(UC_ERR_ARGS, "cluster graph: edge endpoint out of range");
+        if (a == b) continue;
+        off[(size_t)a + 1]++; off[(size_t)b + 1]++;
+    }
+    for (uint32_t i = 0; i < n; i++) off[(size_t)i + 1] += off[i];
+    std::vector<uint32_t> adj(std::max<uint64_t>(off[n], 1));
+    std::vector<uint64_t> cur(off.begin(), off.end() - 1);
+    for (uint64_t e = 0; e < n_edges; e++) {
+        const uint32_t a = edges[2 * e], b = edges[2 * e + 1];
+        if (a == b) continue;
+        adj[cur[a]++] = b; adj[cur[b]++] = a;
+    }
+    std::vector<uint32_t> order(n);
+    for (uint32_t i = 0; i < n; i++) { order[i] = i; assign[i] = NONE; }
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return len[a] > len[b]; });      // stable: ties keep ascending ids
+    for (uint32_t u : order) {
+        if (assign[u] != NONE) continue;
+        assign[u] = u;
+        for (uint64_t e = off[u]; e < off[(size_t)u + 1]; e++)
+            if (assign[adj[e]] == NONE) assign[adj[e]] = u;
+    }
+}
+
+void cluster_graph(uint32_t n, const uint32_t *edges, uint64_t n_edges, const uint32_t *len, int mode, uint32_t *assign) {
+    if (mode == 0) set_cover(n, edges, n_edges, assign);
+    else if (mode == 2) greedy_incremental(n, edges, n_edges, len, assign);
+    else fail(UC_ERR_ARGS, "cluster graph: mode %d unsupported (0 = greedy set cover, 2 = greedy incremental)", mode);
 }
 
 }  // namespace uc
