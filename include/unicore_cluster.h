@@ -255,6 +255,14 @@ int uc_cluster_graph(uint32_t n, const uint32_t *edges, uint64_t n_edges, const 
 /* the device variant: n and the lengths are those of the engine's database; graph, rounds and assignment on the engine's GPU.  mode 0 gives
  * uc_engine_setcover's result. */
 int uc_engine_cluster_graph(uc_engine *e, int32_t mode, const uint32_t *edges, uint64_t n_edges, uint32_t *assign);
+/* Rule UC-1/R (`--cluster-reassign`) on the engine's resident database and its options, as uc_cluster runs it behind the last round of
+ * the workflow.  assign_in[n] is an assignment with assign_in[assign_in[x]] == assign_in[x]; anything else (an entry out of range, a representative
+ * that is itself a member) is UC_ERR_ARGS.  Every member is verified against its representative with the gapped stage (query = representative), the
+ * rejected members are searched again against representatives + rejected members, and the engine's clustering rule (--cluster-mode) runs on the
+ * graph of everything that was accepted: assign_out[n].  rejected_out (nullable): n flags, 1 = the member failed the verification.
+ * counts = { members verified, rejected, accepted pairs of the re-search (self pairs not counted), final clusters }.  Adds an entry point only:
+ * the ABI revision and uc_stats are unchanged. */
+int uc_engine_reassign(uc_engine *e, const uint32_t *assign_in, uint32_t *assign_out, uint8_t *rejected_out, uint64_t counts[4]);
 /* E8/E9 outputs from an assignment: cluster DB (<prefix>, .index, .dbtype) */
 int uc_write_cluster_db(const char *out_cluster_db, uint32_t n, const uint32_t *assign);
 

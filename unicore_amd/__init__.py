@@ -65,7 +65,7 @@ SYMBOLS = (
     "uc_engine_ungapped_batch", "uc_engine_ungapped_all", "uc_engine_sw_batch", "uc_engine_sw_pass", "uc_engine_sw_pass2", "uc_engine_backtraces_size", "uc_engine_backtraces_get",
     "uc_backtrace_render", "uc_format_output_check", "uc_engine_tb_emit_pass", "uc_abi_version", "uc_stats_size", "uc_set_round_hook",
     "uc_t5_gemm_variant", "uc_t5_kernel_gemm", "uc_t5_kernel_rmsnorm", "uc_t5_kernel_attention", "uc_t5_kernel_cnn_head", "uc_t5_bias_table",
-    "uc_cluster_graph", "uc_engine_cluster_graph",
+    "uc_cluster_graph", "uc_engine_cluster_graph", "uc_engine_reassign",
 )
 ABI_VERSION = 9      # == UC_ABI_VERSION of include/unicore_cluster.h this binding mirrors
 ROUND_HOOK = C.CFUNCTYPE(None, C.c_void_p, C.c_int32, C.c_uint32, C.POINTER(C.c_uint32), C.c_int32, C.c_void_p)
@@ -137,6 +137,7 @@ def lib():
     L.uc_setcover.argtypes = [u32, vp, u64, vp]
     L.uc_cluster_graph.argtypes = [u32, vp, u64, vp, i32, vp]
     L.uc_engine_cluster_graph.argtypes = [vp, i32, vp, u64, vp]
+    L.uc_engine_reassign.argtypes = [vp, vp, vp, vp, vp]
     L.uc_write_cluster_db.argtypes = [C.c_char_p, u32, vp]
     L.uc_engine_ungapped_batch.argtypes = [vp, u64, vp, vp, vp, vp]
     L.uc_engine_ungapped_all.argtypes = [vp, u32, u32, u32, u32, u64, vp, vp]
@@ -529,6 +530,16 @@ class Engine:
         assign = np.zeros(self.n, np.uint32)
         _check(lib().uc_engine_cluster_graph(self._h, mode, e.ctypes.data, len(e), assign.ctypes.data))
         return assign
+
+    def reassign(self, assign):
+        """Rule UC-1/R (--cluster-reassign, uc_engine_reassign) on the assignment `assign` of the engine's database under the engine's options.
+        Returns (assign_out, rejected bool[n], counts dict: verified, rejected, research_accepted, clusters)."""
+        a = np.ascontiguousarray(assign, np.uint32)
+        if len(a) != self.n:
+            raise ValueError("assign has %d entries for %d sequences" % (len(a), self.n))
+        out, rej, cnt = np.zeros(self.n, np.uint32), np.zeros(max(self.n, 1), np.uint8), np.zeros(4, np.uint64)
+        _check(lib().uc_engine_reassign(self._h, a.ctypes.data, out.ctypes.data, rej.ctypes.data, cnt.ctypes.data))
+        return out, rej[: self.n].astype(bool), dict(zip(("verified", "rejected", "research_accepted", "clusters"), (int(x) for x in cnt)))
 
     def align(self, qbegin=0, qend=None):
         _check(lib().uc_engine_align(self._h, qbegin, self.n if qend is None else qend))

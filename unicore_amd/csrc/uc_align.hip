@@ -1109,6 +1109,7 @@ struct AlignScratch {
     DevBuf<uint64_t> sc_key, sc_key2, sc_ukey, sc_doff;
     DevBuf<char> sc_tmp;
     GreedyIncScratch gi;             // --cluster-mode 2 (uc_greedy_inc.hip): same graph buffers, its own round state
+    ReassignScratch ra;              // --cluster-reassign (uc_reassign.hip): member keys, flags, seeds, the stage's edge list
 };
 static AlignScratch &scratch_of(Engine &E) {
     if (!E.aln) E.aln = ParkedScratch<AlignScratch>::take_or_new(E.device);
@@ -2207,6 +2208,7 @@ void Engine::set_cover_device(uint32_t n, const uint32_t *h_edges, uint64_t n_ed
 }
 
 GreedyIncScratch &Engine::greedy_inc_scratch() { return scratch_of(*this).gi; }
+ReassignScratch &Engine::reassign_scratch() { return scratch_of(*this).ra; }
 
 // the graph (CSR, both directions, duplicates and self loops removed) on the device from a host or a device edge list (n_edges > 0): the step
 // both clustering rules start from.  The arrays live in the engine's scratch and stay valid until the next graph build

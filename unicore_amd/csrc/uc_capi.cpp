@@ -471,6 +471,14 @@ int uc_engine_cluster_graph(uc_engine *e, int32_t mode, const uint32_t *edges, u
     });
 }
 
+int uc_engine_reassign(uc_engine *e, const uint32_t *assign_in, uint32_t *assign_out, uint8_t *rejected_out, uint64_t counts[4]) {
+    return guard([&] {
+        require(e, "engine"); require(counts, "counts");
+        if (e->e->hdb.n) { require(assign_in, "assign_in"); require(assign_out, "assign_out"); }
+        e->e->reassign(assign_in, assign_out, rejected_out, counts);
+    });
+}
+
 int uc_write_cluster_db(const char *out_cluster_db, uint32_t n, const uint32_t *assign) {
     return guard([&] {
         require(out_cluster_db, "out_cluster_db");
@@ -807,6 +815,32 @@ int uc_cluster(const char *db, const char *out_cluster_db, const char *tmp, cons
                     E.stats.n_edges = n_acc;
                 }
                 phase("cover+merge", rr);
+            }
+            if (r == 0 && p.reassign) {
+                // rule UC-1/R on rank 0's engine alone (the others wait at the barrier below: the rejected sets are small).  The full database becomes
+                // the engine's again: one rank lays it out from the raw copy the rounds kept on the device (or still holds it after a plain step)
+                phase("(between)", p.cluster_steps + pre);
+                Timer tr;
+                const bool multi_round = p.cluster_steps + pre > 1;
+                E.p.kmer_thr = p.kmer_thr;                    // the final sensitivity, not a cascade round's
+                if (W == 1 && multi_round) {
+                    std::vector<uint32_t> all(n);
+                    for (uint32_t i = 0; i < n; i++) all[i] = i;
+                    E.upload_sub_db(all, full.off);
+                } else if (W > 1) {
+                    E.hdb = full;
+                    E.upload_db(/*keep_raw=*/true);
+                }
+                std::vector<uint32_t> out(n);
+                uint64_t rc[4] = {0, 0, 0, 0};
+                const uint64_t before = cur.size();
+                E.reassign(assign.data(), out.data(), nullptr, rc);
+                assign.swap(out);
+                cur.clear();
+                for (uint32_t x = 0; x < n; x++) if (assign[x] == x) cur.push_back(x);
+                logf(3, "unicore-cluster: reassign: %llu members verified, %llu rejected, %llu re-search pairs accepted, %llu -> %zu clusters (%.1f ms)\n",
+                     (unsigned long long)rc[0], (unsigned long long)rc[1], (unsigned long long)rc[2], (unsigned long long)before, cur.size(), 1e3 * tr.seconds());
+                phase("reassign", p.cluster_steps + pre);
             }
             C.barrier(E);
             if (W == 1 && p.cluster_steps + pre == 1) full = std::move(E.hdb);

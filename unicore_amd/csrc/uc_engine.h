@@ -189,6 +189,13 @@ struct GreedyIncScratch {
     DevBuf<char> tmp;
 };
 
+// the stage behind --cluster-reassign (rule UC-1/R, uc_reassign.hip): kept in the AlignScratch as well
+struct ReassignScratch {
+    DevBuf<uint64_t> key, key2;                           // (representative << 32 | member), unsorted / sorted
+    DevBuf<uint32_t> assign, cnt, rej, flag, pos, pos2, ids, ctr, edges;
+    DevBuf<char> tmp;
+};
+
 struct PrefilterScratch;                                  // uc_prefilter.hip
 void free_scratch(PrefilterScratch *p);
 struct AlignScratch;                                      // uc_align.hip
@@ -342,6 +349,11 @@ struct Engine {
     // E7 by rule (0 = set cover, 2 = greedy incremental) from a host edge list, and by p.cluster_mode from a device edge list (n_edges < 2^31)
     void cluster_graph_device(int mode, uint32_t n, const uint32_t *h_edges, uint64_t n_edges, uint32_t *assign);
     void cluster_graph_dev_edges(uint32_t n, const uint32_t *dev_edges, uint64_t n_edges, uint32_t *assign);
+    // rule UC-1/R (--cluster-reassign) on the assignment A = assign_in of the resident database's n sequences (A[A[x]] == A[x]): every member verified against
+    // its representative, the rejected ones searched again against representatives + rejected, the run's clustering rule on what was accepted.
+    // rejected_out (nullable): n flags; counts: members verified, rejected, accepted re-search pairs (self pairs dropped), final clusters      (uc_reassign.hip)
+    void reassign(const uint32_t *assign_in, uint32_t *assign_out, uint8_t *rejected_out, uint64_t counts[4]);
+    ReassignScratch &reassign_scratch();
     // E8a: (centre, member) candidate pairs of the linear-time pre-step for the resident DB, sorted by (centre, member), unique (uc_linclust.hip)
     std::vector<uint32_t> linclust_pairs();
     uint64_t linclust_hits();                                        // ... installed as the hit lists (query = centre); returns the pair count

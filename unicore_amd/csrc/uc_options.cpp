@@ -121,7 +121,7 @@ int option_arity(const std::string &f) {
         "--gpus", "--target-shards", "--mat-bit-factor-3di", "--mat-bit-factor-aa", "--comp-bias-corr", "--comp-bias-corr-scale", "--min-score-table", "--length-gate", "--format-output",
         "--prefilter-mode"};
     for (const char *v : valued) if (f == v) return 1;
-    if (f == "--single-step-clustering" || f == "-a") return 2;
+    if (f == "--single-step-clustering" || f == "-a" || f == "--cluster-reassign") return 2;
     return -1;
 }
 
@@ -177,6 +177,7 @@ void parse_cluster_options(const std::string &opts, Params &p) {
             p.cluster_mode = m == 3 ? 2 : m;      // rule UC-1/G; Foldseek's 3 is the low-memory form of 2
         }
         else if (f == "--single-step-clustering") { p.single_step = opt_bool(); p.single_step_given = true; }
+        else if (f == "--cluster-reassign") { p.reassign = opt_bool() ? 1 : 0; /* read by uc_cluster only */ }
         else if (f == "-a") { p.want_bt = opt_bool(); /* implies want_tb where alignments are kept: uc_search, uc_engine_create */ }
         else if (f == "--format-output") { p.format_output = value(); /* read by convertalis only */ }
         else if (f == "--cluster-steps") { p.cluster_steps = to_int(f, value()); p.cluster_steps_given = true; }
@@ -189,6 +190,8 @@ void parse_cluster_options(const std::string &opts, Params &p) {
         else if (f == "--remove-tmp-files" || f == "--db-load-mode" || f == "--compressed") { (void)value(); /* no effect on results */ }
         else fail(UC_ERR_ARGS, "unknown or unsupported cluster option '%s'", f.c_str());
     }
+    if (p.reassign && !p.min_score_table_path.empty())
+        fail(UC_ERR_ARGS, "--cluster-reassign cannot be combined with --min-score-table (the table is indexed by database sequence, the re-search runs on a sub-database)");
 }
 
 std::string default_data_dir() {

@@ -54,6 +54,7 @@ struct Params {
     int len_gate = 0;                       // --length-gate 1 (rule UC-1/L, optional): pairs whose lengths alone rule the coverage threshold out are not aligned
     // clustering
     int cluster_mode = 0;       // --cluster-mode: 0 = greedy set cover, 2 = greedy incremental (rule UC-1/G, optional; 3 is parsed into 2)
+    int reassign = 0;           // --cluster-reassign (rule UC-1/R, optional): members verified against their final representative, the rejected ones searched again
     int cluster_steps = 1;      // > 1: cascade (E8) — rounds on representatives with rising sensitivity, merged at the end
     int linclust = 0;           // 1: linear-time pre-step (E8a) before the clustering rounds
     int kmer_per_seq = 20;      // k-mers every sequence keeps in the pre-step
