@@ -241,6 +241,9 @@ int uc_engine_edges_get(const uc_engine *e, uint32_t *edges /* 2*n_edges: (query
 
 int uc_engine_stats(const uc_engine *e, uc_stats *out);
 void uc_engine_reset_stats(uc_engine *e);
+/* the prefilter's on-chip diagonal selection since the last reset: out[0] queries it took, out[1] queries of the double-hit path, out[2] surviving
+ * keys it took, out[3] surviving keys (= n_filtered_hits of that path); UC_TD_ONCHIP=0 leaves [0] and [2] at 0 */
+int uc_engine_td_onchip(const uc_engine *e, uint64_t *out /* 4 */);
 
 /* E7 (host, as the north star prescribes): greedy set cover over (a,b) pairs; assign[i] = representative */
 int uc_setcover(uint32_t n, const uint32_t *edges, uint64_t n_edges, uint32_t *assign);

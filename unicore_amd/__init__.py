@@ -65,7 +65,7 @@ SYMBOLS = (
     "uc_engine_ungapped_batch", "uc_engine_ungapped_all", "uc_engine_sw_batch", "uc_engine_sw_pass", "uc_engine_sw_pass2", "uc_engine_backtraces_size", "uc_engine_backtraces_get",
     "uc_backtrace_render", "uc_format_output_check", "uc_engine_tb_emit_pass", "uc_abi_version", "uc_stats_size", "uc_set_round_hook",
     "uc_t5_gemm_variant", "uc_t5_kernel_gemm", "uc_t5_kernel_rmsnorm", "uc_t5_kernel_attention", "uc_t5_kernel_cnn_head", "uc_t5_bias_table",
-    "uc_cluster_graph", "uc_engine_cluster_graph", "uc_engine_reassign",
+    "uc_cluster_graph", "uc_engine_cluster_graph", "uc_engine_reassign", "uc_engine_td_onchip",
 )
 ABI_VERSION = 9      # == UC_ABI_VERSION of include/unicore_cluster.h this binding mirrors
 ROUND_HOOK = C.CFUNCTYPE(None, C.c_void_p, C.c_int32, C.c_uint32, C.POINTER(C.c_uint32), C.c_int32, C.c_void_p)
@@ -134,6 +134,7 @@ def lib():
     L.uc_engine_stats.argtypes = [vp, C.POINTER(UcStats)]
     L.uc_engine_reset_stats.argtypes = [vp]
     L.uc_engine_reset_stats.restype = None
+    L.uc_engine_td_onchip.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.uc_setcover.argtypes = [u32, vp, u64, vp]
     L.uc_cluster_graph.argtypes = [u32, vp, u64, vp, i32, vp]
     L.uc_engine_cluster_graph.argtypes = [vp, i32, vp, u64, vp]
@@ -572,7 +573,12 @@ class Engine:
     def stats(self):
         st = UcStats()
         _check(lib().uc_engine_stats(self._h, C.byref(st)))
-        return st.as_dict()
+        d = st.as_dict()
+        # what the prefilter's on-chip diagonal selection took since the last reset (uc_engine_td_onchip: not part of uc_stats)
+        td = (C.c_uint64 * 4)()
+        _check(lib().uc_engine_td_onchip(self._h, td))
+        d["td_onchip_queries"], d["td_onchip_keys"] = int(td[0]), int(td[2])
+        return d
 
     def reset_stats(self):
         lib().uc_engine_reset_stats(self._h)

@@ -426,6 +426,11 @@ void uc_engine_reset_stats(uc_engine *e) {
     const uint64_t ns = s.n_seqs, nr = s.n_residues;
     memset(&s, 0, sizeof s);
     s.n_seqs = ns; s.n_residues = nr;
+    for (uint64_t &x : e->e->td_onchip) x = 0;
+}
+
+int uc_engine_td_onchip(const uc_engine *e, uint64_t *out) {
+    return guard([&] { require(e, "engine"); require(out, "out"); for (int i = 0; i < 4; i++) out[i] = e->e->td_onchip[i]; });
 }
 
 int uc_setcover(uint32_t n, const uint32_t *edges, uint64_t n_edges, uint32_t *assign) {

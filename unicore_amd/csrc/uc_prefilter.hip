@@ -1211,6 +1211,198 @@ __global__ void __launch_bounds__(256) diag_long_kernel(const uint64_t *keys, ui
     if (staged) drain();
 }
 
+// ---- E2 diagonal selection on chip (compact mode): one workgroup per query, right behind filter_kernel ----
+// filter_kernel leaves a query's surviving u32 keys [target - tbase | diagonal + dbias] at the head of the query's own region, so they are grouped by
+// query already; widening them to u64, prepending the query bits and radix-sorting the whole batch only restores that order.  A query with at most
+// TDS_CAP survivors is sorted here in LDS (rocprim::block_radix_sort over the significant bits, all-ones padding, items per thread chosen from n by a
+// workgroup-uniform branch), its runs and groups are evaluated under diag_select_kernel's rule by three max-scans over the sorted keys:
+//   A   index of the last run start at or before i            -> a run's length at its last key
+//   B1  [ group | length | dmask - diagonal ] at the run ends -> most hits, then the SMALLEST diagonal, at the group's last key
+//   B2  [ group | length | diagonal ]                         -> most hits, then the LARGEST diagonal (the pair the other way round)
+// (the group field leads, the keys are sorted, so a plain max-scan is the segmented one), and the chosen keys go back to the head of the region: plain
+// candidates first, the mirrored ones (still [target | largest diagonal]: cand_gather_kernel swaps and negates) behind them.  A candidate's group holds
+// >= min_hits >= 2 keys, so up to two records per group fit; every key is in registers before the first store (the sort's barriers).  No key-by-key walk:
+// a thread folds its own TDS_T-th of the sorted array whatever the runs look like.  Queries with no or more than `cap` survivors are left to the batch sort.
+// Measured at configs[1] (profiles/td_onchip): 99 % of the queries and 91 % of the surviving keys are taken here.
+constexpr int TDS_T = 256;             // threads per workgroup: several workgroups per CU
+constexpr int TDS_MAX_IPT = 32;
+constexpr uint32_t TDS_CAP = TDS_T * TDS_MAX_IPT;
+template <int IPT> using TdSort = rocprim::block_radix_sort<uint32_t, TDS_T, IPT>;
+constexpr size_t tds_max(size_t a, size_t b) { return a > b ? a : b; }
+// two launches share the work: the registers and the LDS of the 16- and 32-item sorts would leave the common short queries three workgroups per CU
+constexpr int TDS_SMALL_IPT = 8;       // td_select_kernel<false>: n <= 8 x TDS_T, td_select_kernel<true>: the rest up to TDS_CAP
+constexpr size_t TDS_SORT_BYTES_SMALL =
+    tds_max(tds_max(sizeof(TdSort<1>::storage_type), sizeof(TdSort<2>::storage_type)), tds_max(sizeof(TdSort<4>::storage_type), sizeof(TdSort<8>::storage_type)));
+constexpr size_t TDS_SORT_BYTES_BIG = tds_max(sizeof(TdSort<16>::storage_type), sizeof(TdSort<32>::storage_type));
+
+struct TdsMax { template <class T> __device__ T operator()(T a, T b) const { return a > b ? a : b; } };
+struct TdsSum { template <class T> __device__ T operator()(T a, T b) const { return a + b; } };
+// exclusive scan of one value per thread over the workgroup (identity 0); *total = the fold of all of them.  s_w: TDS_T / 64 slots, free again on return
+template <class T, class Op>
+__device__ __forceinline__ T tds_block_excl(T v, Op op, T *s_w, T *total) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    T inc = v;
+    for (int o = 1; o < 64; o <<= 1) {
+        const T u = (T)__shfl_up((unsigned long long)inc, o, 64);
+        if (lane >= o) inc = op(u, inc);
+    }
+    if (lane == 63) s_w[wv] = inc;
+    __syncthreads();
+    T ex = (T)__shfl_up((unsigned long long)inc, 1, 64), all = 0;
+    if (lane == 0) ex = 0;
+    for (int w = 0; w < TDS_T / 64; w++) {
+        const T u = s_w[w];
+        if (w < wv) ex = op(u, ex);
+        all = op(all, u);
+    }
+    __syncthreads();
+    if (total) *total = all;
+    return ex;
+}
+
+// the same for two values at once under max (one pair of barriers).  s_w: 2 x TDS_T / 64 slots
+__device__ __forceinline__ void tds_block_excl_max2(uint64_t a, uint64_t b, uint64_t *s_w, uint64_t &ea, uint64_t &eb) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint64_t ua = (uint64_t)__shfl_up((unsigned long long)a, o, 64), ub = (uint64_t)__shfl_up((unsigned long long)b, o, 64);
+        if (lane >= o) { a = ua > a ? ua : a; b = ub > b ? ub : b; }
+    }
+    if (lane == 63) { s_w[2 * wv] = a; s_w[2 * wv + 1] = b; }
+    __syncthreads();
+    ea = (uint64_t)__shfl_up((unsigned long long)a, 1, 64); eb = (uint64_t)__shfl_up((unsigned long long)b, 1, 64);
+    if (lane == 0) ea = eb = 0;
+    for (int w = 0; w < wv; w++) {
+        const uint64_t ua = s_w[2 * w], ub = s_w[2 * w + 1];
+        ea = ua > ea ? ua : ea; eb = ub > eb ? ub : eb;
+    }
+    __syncthreads();
+}
+
+template <int IPT>
+__device__ __forceinline__ uint32_t td_select_sorted(uint32_t *reg, uint32_t n, int min_hits, int dbits, unsigned end_bit, bool mirror, void *s_sort,
+                                                     uint32_t (*s_edge)[TDS_T], uint64_t *s_w) {
+    const int tid = threadIdx.x;
+    const uint32_t dmask = (1u << dbits) - 1u;
+    uint32_t keys[IPT];
+#pragma unroll
+    for (int j = 0; j < IPT; j++) {
+        const uint32_t i = (uint32_t)j * TDS_T + tid;
+        keys[j] = i < n ? reg[i] : 0xFFFFFFFFu;
+    }
+    TdSort<IPT>().sort(keys, *reinterpret_cast<typename TdSort<IPT>::storage_type *>(s_sort), 0u, end_bit);
+    // blocked: this thread holds the sorted keys i0 .. i0 + IPT - 1 (the padding sorts behind the n keys: only i < n is looked at)
+    const uint32_t i0 = (uint32_t)tid * IPT;
+    s_edge[0][tid] = keys[0]; s_edge[1][tid] = keys[IPT - 1];
+    __syncthreads();
+    const uint32_t kprev = tid ? s_edge[1][tid - 1] : 0u, knext = tid < TDS_T - 1 ? s_edge[0][tid + 1] : 0u;
+    __syncthreads();
+    uint32_t rs = 0;
+    uint64_t m1 = 0, m2 = 0;
+    // folds the sorted key i0 + j into (rs, m1, m2); true: it is the last key of its group
+    auto step = [&](int j) -> bool {
+        const uint32_t i = i0 + (uint32_t)j, k = keys[j];
+        const uint32_t kp = j ? keys[j ? j - 1 : 0] : kprev, kn = j < IPT - 1 ? keys[j < IPT - 1 ? j + 1 : j] : knext;
+        if (i >= n) return false;
+        if (i == 0 || kp != k) rs = i;
+        const bool last = i == n - 1;
+        if (last || kn != k) {
+            const uint64_t g = ((uint64_t)(k >> dbits) << 32) | ((uint64_t)(i + 1 - rs) << dbits);
+            const uint64_t a = g | (uint64_t)(dmask - (k & dmask)), b = g | (uint64_t)(k & dmask);
+            m1 = a > m1 ? a : m1; m2 = b > m2 ? b : m2;
+        }
+        return last || (kn >> dbits) != (k >> dbits);
+    };
+    // A
+#pragma unroll
+    for (int j = 0; j < IPT; j++) {
+        const uint32_t i = i0 + (uint32_t)j, kp = j ? keys[j ? j - 1 : 0] : kprev;
+        if (i < n && (i == 0 || kp != keys[j])) rs = i;
+    }
+    const uint32_t rs0 = (uint32_t)tds_block_excl<uint64_t>((uint64_t)rs, TdsMax(), s_w, nullptr);
+    // B1 / B2
+    rs = rs0;
+#pragma unroll
+    for (int j = 0; j < IPT; j++) (void)step(j);
+    uint64_t e1, e2;
+    tds_block_excl_max2(m1, m2, s_w, e1, e2);
+    // the candidates of this thread's group ends, counted, then written behind those of the threads below
+    uint32_t mine = 0;
+    rs = rs0; m1 = e1; m2 = e2;
+#pragma unroll
+    for (int j = 0; j < IPT; j++)
+        if (step(j)) mine += (int)((uint32_t)m1 >> dbits) >= min_hits ? 1u : 0u;
+    uint64_t tot64 = 0;
+    uint32_t w = (uint32_t)tds_block_excl<uint64_t>((uint64_t)mine, TdsSum(), s_w, &tot64);
+    const uint32_t ncand = (uint32_t)tot64;
+    if (mine) {
+        rs = rs0; m1 = e1; m2 = e2;
+#pragma unroll
+        for (int j = 0; j < IPT; j++)
+            if (step(j) && (int)((uint32_t)m1 >> dbits) >= min_hits) {
+                const uint32_t g = (keys[j] >> dbits) << dbits;
+                reg[w] = g | (dmask - ((uint32_t)m1 & dmask));
+                if (mirror) reg[ncand + w] = g | ((uint32_t)m2 & dmask);      // (2 ncand <= n: every candidate group holds >= min_hits >= 2 keys)
+                w++;
+            }
+    }
+    return ncand;
+}
+
+template <bool BIG>
+__global__ void __launch_bounds__(TDS_T) td_select_kernel(uint32_t *region, const uint64_t *qbase, uint32_t *qsurv, const uint32_t *order, uint32_t qbegin,
+                                                          uint32_t mirror_q0, int min_hits, int dbits, unsigned end_bit, uint32_t cap,
+                                                          uint32_t *qcand, uint32_t *qmir, uint32_t *qrec, unsigned long long *n_taken) {
+    __shared__ __attribute__((aligned(16))) char s_sort[BIG ? TDS_SORT_BYTES_BIG : TDS_SORT_BYTES_SMALL];
+    __shared__ uint32_t s_edge[2][TDS_T];
+    __shared__ uint64_t s_w[2 * TDS_T / 64];
+    constexpr uint32_t SMALL = (uint32_t)TDS_SMALL_IPT * TDS_T;
+    const uint32_t qi = order[blockIdx.x];
+    const uint32_t n = qsurv[qi];
+    if (n == 0 || n > cap) {                   // (workgroup-uniform, and so is every branch on n below)
+        if (!BIG && threadIdx.x == 0) { qcand[qi] = 0; qmir[qi] = 0; qrec[qi] = 0; }
+        return;
+    }
+    if (BIG != (n > SMALL)) return;            // the other launch's query (<true> runs behind <false>: qsurv of a query taken there is 0 by now)
+    uint32_t *reg = region + qbase[qi];
+    const bool mirror = mirror_q0 != UINT32_MAX && qbegin + qi >= mirror_q0;
+    uint32_t nc;
+    if (BIG) {
+        if (n <= 16u * TDS_T) nc = td_select_sorted<16>(reg, n, min_hits, dbits, end_bit, mirror, s_sort, s_edge, s_w);
+        else nc = td_select_sorted<32>(reg, n, min_hits, dbits, end_bit, mirror, s_sort, s_edge, s_w);
+    } else {
+        if (n <= 1u * TDS_T) nc = td_select_sorted<1>(reg, n, min_hits, dbits, end_bit, mirror, s_sort, s_edge, s_w);
+        else if (n <= 2u * TDS_T) nc = td_select_sorted<2>(reg, n, min_hits, dbits, end_bit, mirror, s_sort, s_edge, s_w);
+        else if (n <= 4u * TDS_T) nc = td_select_sorted<4>(reg, n, min_hits, dbits, end_bit, mirror, s_sort, s_edge, s_w);
+        else nc = td_select_sorted<8>(reg, n, min_hits, dbits, end_bit, mirror, s_sort, s_edge, s_w);
+    }
+    if (threadIdx.x == 0) {
+        qcand[qi] = nc; qmir[qi] = mirror ? nc : 0u; qrec[qi] = mirror ? 2u * nc : nc;
+        qsurv[qi] = 0;
+        atomicAdd(n_taken, (1ull << 40) | (unsigned long long)n);      // [ queries : 24 | keys : 40 ] of the batch that were taken here
+    }
+}
+
+// the region-resident records of td_select_kernel -> candidates at out0 + coff[query] (coff: exclusive scan of qcand + qmir), a wave per query
+__global__ void __launch_bounds__(256) cand_gather_kernel(const uint32_t *region, const uint64_t *qbase, const uint32_t *qcand, const uint32_t *qmir,
+                                                          const uint64_t *coff, uint32_t nq, KeyFmt fmt, uint32_t qbegin, uint64_t out0,
+                                                          uint32_t *cq, uint32_t *ct, int32_t *cd) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const uint32_t dmask = (1u << fmt.dbits) - 1u;
+    for (uint32_t qi = blockIdx.x * 4 + wv; qi < nq; qi += gridDim.x * 4) {
+        const uint32_t nc = qcand[qi], nr = nc + qmir[qi];
+        if (!nr) continue;
+        const uint64_t src = qbase[qi], dst = out0 + coff[qi];
+        const uint32_t q = qbegin + qi;
+        for (uint32_t k = lane; k < nr; k += 64) {
+            const uint32_t td = region[src + k];
+            const uint32_t t = (td >> fmt.dbits) + fmt.tbase;
+            const int32_t d = (int32_t)(td & dmask) - fmt.dbias;
+            const bool plain = k < nc;
+            cq[dst + k] = plain ? q : t; ct[dst + k] = plain ? t : q; cd[dst + k] = plain ? d : -d;
+        }
+    }
+}
+
 // E4 sort key: [ query : 32 | 255 - score : 8 | target : 24 ]; score < min -> all-ones (sorted last)
 __global__ void __launch_bounds__(256) select_key_kernel(uint64_t n, const uint32_t *cq, const uint32_t *ct, const int32_t *score,
                                                          int min_score, uint64_t *key, unsigned long long *n_kept) {
@@ -1319,6 +1511,8 @@ struct PrefilterScratch {
     DevBuf<uint32_t> d_koff, k_in, k_out, d_ent32, v_in32, d_okey, d_okey2, d_oidx, d_order;
     DevBuf<uint64_t> d_ent, v_in;
     DevBuf<uint32_t> d_cnt, d_flag, d_cq, d_ct, d_rpidx2, d_qsurv;
+    DevBuf<uint32_t> d_qcand, d_qmir, d_qrec;           // td_select_kernel: region-resident candidates per query (plain, mirrored, both)
+    DevBuf<uint64_t> d_coff;                            // ... and where cand_gather_kernel puts them
     DevBuf<uint64_t> d_keys, d_keys2, d_pos, d_skey, d_skey2, d_rval2, d_qbase, d_soff, d_qr;
     DevBuf<int32_t> d_cd, d_cd2, d_score, d_mval;      // d_mkey / d_mval: output of the sorted-run merge (merge_hits_dev)
     DevBuf<uint64_t> d_mkey;
@@ -1337,7 +1531,7 @@ struct PrefilterScratch {
         f(d_ent); f(v_in); f(d_cnt); f(d_flag); f(d_cq); f(d_ct); f(d_rpidx2); f(d_qsurv); f(d_keys); f(d_keys2); f(d_pos); f(d_skey);
         f(d_skey2); f(d_rval2); f(d_qbase); f(d_soff); f(d_qr); f(d_cd); f(d_cd2); f(d_score); f(d_kflag); f(d_wflag); f(d_qk); f(d_kid); f(d_dk);
         f(d_nsimk); f(d_drk); f(d_drk2); f(d_roff); f(d_nr); f(d_src); f(d_ph); f(d_drv); f(d_drv2); f(d_cumh); f(d_cumr); f(d_qh); f(d_qrn); f(d_rec); f(d_kbits); f(d_mkey); f(d_mval); f(acc_q); f(acc_t); f(pass_q); f(pass_t); f(acc_s); f(acc_d); f(pass_s); f(pass_d);
-        f(ua.score); f(ua.diag); f(ua.pairs); f(ua.prof); f(ua.prof_off);
+        f(d_qcand); f(d_qmir); f(d_qrec); f(d_coff); f(ua.score); f(ua.diag); f(ua.pairs); f(ua.prof); f(ua.prof_off);
     }
     size_t bytes() {
         size_t b = 0;
@@ -1435,6 +1629,8 @@ struct PrefilterPass {
     const void *ent_p = nullptr;               // the chunk's n_entries index entries sorted by k-mer (compact or wide, fmt.compact)
     uint32_t n_entries = 0;
     uint64_t HIT_CAP = 0, HIT_CAP_BIG = 0, DRUN_MAX = 0;
+    uint64_t td_queries = 0, td_keys = 0, filt_queries = 0, filt_keys = 0;   // what td_select_kernel took of the filter's queries and survivors (UC_TIMING)
+    uint32_t td_cap = 0;                       // td_select_kernel takes the queries with at most this many survivors (0: none, UC_TD_ONCHIP=0)
     uint64_t n_hits_total = 0, n_cand_total = 0, cand_cap = 0, run_cap = 1ull << 20;
     double t_kmer = 0, t_ung = 0, t_sel = 0, gpu_ms = 0;   // host seconds of E2 / E3 / E4 and the event time of everything
 };
@@ -1454,6 +1650,7 @@ struct QueryBatch {
     unsigned kbits = 0;                        // significant bits of its keys [query - qa | target | diagonal]
     const uint64_t *sorted = nullptr;          // the n_sort keys in that order
     uint64_t n_sort = 0;
+    uint64_t n_rec = 0;                        // candidates that td_select_kernel left in the query regions (cand_gather_kernel)
 };
 // consumes max_len, the sequence count and the chunk's target range; produces the layout of the (query, target, diagonal) keys
 static KeyFmt key_format(const Engine &E, uint32_t tbegin, uint32_t tend) {
@@ -1710,7 +1907,31 @@ static void expand_keys_filtered(Engine &E, PrefilterPass &PP, QueryBatch &B) {
     };
     if (fmt.compact) launch(filter_kernel<true>);
     else launch(filter_kernel<false>);
-    const uint64_t n_sort = compact_u64(E, S.d_temp, S.d_qsurv.p, S.d_soff.p, nq);
+    // queries of at most td_cap survivors are sorted and evaluated on chip (td_select_kernel); the batch sort below only sees the rest
+    unsigned long long taken = 0;
+    uint32_t last_rec = 0;
+    const bool onchip = fmt.compact && PP.td_cap > 0;
+    if (onchip) {
+        int rbits = 1;                             // bits of (target - tbase), as in key_format
+        while ((1ull << rbits) < (uint64_t)std::max<uint32_t>(PP.tend - PP.tbegin, 1)) rbits++;
+        S.d_qcand.reserve(nq); S.d_qmir.reserve(nq); S.d_qrec.reserve(nq); S.d_coff.reserve(nq);
+        UC_HIP(hipMemsetAsync(S.d_counters.p + 7, 0, 8, E.stream));
+        hipLaunchKernelGGL(td_select_kernel<false>, dim3(nq), dim3(TDS_T), 0, E.stream, (uint32_t *)S.d_keys.p, S.d_qbase.p, S.d_qsurv.p, S.d_order.p, qa, PP.mirror_q0,
+                           E.p.min_diag_hits, fmt.dbits, (unsigned)std::min(32, rbits + fmt.dbits), PP.td_cap, S.d_qcand.p, S.d_qmir.p, S.d_qrec.p, S.d_counters.p + 7);
+        if (PP.td_cap > (uint32_t)TDS_SMALL_IPT * TDS_T)
+            hipLaunchKernelGGL(td_select_kernel<true>, dim3(nq), dim3(TDS_T), 0, E.stream, (uint32_t *)S.d_keys.p, S.d_qbase.p, S.d_qsurv.p, S.d_order.p, qa, PP.mirror_q0,
+                               E.p.min_diag_hits, fmt.dbits, (unsigned)std::min(32, rbits + fmt.dbits), PP.td_cap, S.d_qcand.p, S.d_qmir.p, S.d_qrec.p, S.d_counters.p + 7);
+        auto rin = rocprim::make_transform_iterator(S.d_qrec.p, WidenU32());
+        rocprim_call(S.d_temp, [&](void *t, size_t &b) { return rocprim::exclusive_scan(t, b, rin, S.d_coff.p, (uint64_t)0, (size_t)nq, rocprim::plus<uint64_t>(), E.stream); });
+        // (fetched by the one synchronisation of the scan below)
+        UC_HIP(hipMemcpyAsync(&B.n_rec, S.d_coff.p + (nq - 1), 8, hipMemcpyDeviceToHost, E.stream));
+        UC_HIP(hipMemcpyAsync(&taken, S.d_counters.p + 7, 8, hipMemcpyDeviceToHost, E.stream));
+    }
+    const uint64_t n_sort = compact_u64(E, S.d_temp, S.d_qsurv.p, S.d_soff.p, nq, onchip ? S.d_qrec.p + (nq - 1) : nullptr, &last_rec);
+    B.n_rec += last_rec;
+    const uint64_t taken_keys = taken & ((1ull << 40) - 1);
+    PP.td_queries += taken >> 40; PP.td_keys += taken_keys; PP.filt_queries += nq; PP.filt_keys += n_sort + taken_keys;
+    E.td_onchip[0] += taken >> 40; E.td_onchip[1] += nq; E.td_onchip[2] += taken_keys; E.td_onchip[3] += n_sort + taken_keys;
     if (n_sort) {
         S.d_keys2.reserve(2 * n_sort);              // dense keys + the sort's output
         hipLaunchKernelGGL(fmt.compact ? compact_kernel<true> : compact_kernel<false>, dim3(std::min<uint32_t>(nq, 65535u)), dim3(256), 0, E.stream,
@@ -1718,7 +1939,7 @@ static void expand_keys_filtered(Engine &E, PrefilterPass &PP, QueryBatch &B) {
         rocprim_call(S.d_temp, [&](void *t, size_t &b) { return rocprim::radix_sort_keys(t, b, S.d_keys2.p, S.d_keys2.p + n_sort, (size_t)n_sort, 0u, B.kbits, E.stream); });
     }
     B.sorted = S.d_keys2.p + n_sort; B.n_sort = n_sort;
-    E.stats.n_filtered_hits += n_sort;
+    E.stats.n_filtered_hits += n_sort + taken_keys;
 }
 
 // pass 2 without the filter (min_diag_hits < 2, or a single query beyond 2^32 hits).  consumes the batch's runs; produces all its keys, sorted
@@ -1738,7 +1959,7 @@ static uint64_t select_diagonals(Engine &E, PrefilterPass &PP, const QueryBatch 
     PrefilterScratch &S = *E.pre;
     PP.cand_cap = std::max<uint64_t>(PP.cand_cap, std::max<uint64_t>(1u << 20, B.total_hits / 32));
     for (;;) {
-        S.d_cq.reserve(PP.cand_cap); S.d_ct.reserve(PP.cand_cap); S.d_cd.reserve(PP.cand_cap);
+        S.d_cq.reserve(PP.cand_cap + B.n_rec); S.d_ct.reserve(PP.cand_cap + B.n_rec); S.d_cd.reserve(PP.cand_cap + B.n_rec);      // (room for the region-resident records behind them)
         UC_HIP(hipMemsetAsync(S.d_counters.p + 6, 0, 8, E.stream));
         if (B.n_sort) {
             S.d_wflag.reserve((B.n_sort + 63) / 64 + 64);
@@ -1750,7 +1971,12 @@ static uint64_t select_diagonals(Engine &E, PrefilterPass &PP, const QueryBatch 
         unsigned long long nc = 0;
         UC_HIP(hipMemcpyAsync(&nc, S.d_counters.p + 6, 8, hipMemcpyDeviceToHost, E.stream));
         UC_HIP(hipStreamSynchronize(E.stream));
-        if (nc <= PP.cand_cap) return nc;
+        if (nc <= PP.cand_cap) {
+            if (B.n_rec)      // their number is known exactly: no cap, cursor or retry
+                hipLaunchKernelGGL(cand_gather_kernel, grid_for((uint64_t)(B.qb - B.qa) * 64), dim3(256), 0, E.stream, (const uint32_t *)S.d_keys.p, S.d_qbase.p,
+                                   S.d_qcand.p, S.d_qmir.p, S.d_coff.p, B.qb - B.qa, PP.fmt, B.qa, (uint64_t)nc, S.d_cq.p, S.d_ct.p, S.d_cd.p);
+            return nc + B.n_rec;
+        }
         PP.cand_cap = nc;     // rare: more candidates than provisioned, run the selection again
     }
 }
@@ -1775,7 +2001,9 @@ static void select_and_append(Engine &E, PrefilterPass &PP, uint64_t n_cand) {
     S.d_skey.reserve(n_cand); S.d_skey2.reserve(n_cand); S.d_cd2.reserve(n_cand);
     UC_HIP(hipMemsetAsync(S.d_counters.p + 1, 0, 8, E.stream));
     hipLaunchKernelGGL(select_key_kernel, grid_for(n_cand), dim3(256), 0, E.stream, n_cand, S.d_cq.p, S.d_ct.p, S.d_score.p, E.p.min_ungapped, S.d_skey.p, S.d_counters.p + 1);
-    rocprim_call(S.d_temp, [&](void *t, size_t &b) { return rocprim::radix_sort_pairs(t, b, S.d_skey.p, S.d_skey2.p, S.d_cd.p, S.d_cd2.p, (size_t)n_cand, 0u, 64u, E.stream); });
+    unsigned kb = 33;      // the query field ends below bit 32 + log2(n) + 1: the all-ones key of a dropped candidate still sorts behind every kept one
+    while (kb < 64 && (1ull << (kb - 32)) <= E.hdb.n) kb++;
+    rocprim_call(S.d_temp, [&](void *t, size_t &b) { return rocprim::radix_sort_pairs(t, b, S.d_skey.p, S.d_skey2.p, S.d_cd.p, S.d_cd2.p, (size_t)n_cand, 0u, kb, E.stream); });
     unsigned long long kept = 0;
     UC_HIP(hipMemcpyAsync(&kept, S.d_counters.p + 1, 8, hipMemcpyDeviceToHost, E.stream));
     UC_HIP(hipStreamSynchronize(E.stream));
@@ -1797,6 +2025,9 @@ static void select_and_append(Engine &E, PrefilterPass &PP, uint64_t n_cand) {
 // consumes the totals of the chunk; produces the per-query counts / offsets (unless the lists leave ungrouped) and the chunk's share of the statistics
 static void finish_chunk(Engine &E, const PrefilterPass &PP, uint64_t sims_before) {
     if (PP.mirror_q0 == UINT32_MAX) E.finish_hit_lists("prefilter");
+    if (getenv("UC_TIMING") && PP.filt_queries)
+        fprintf(stderr, "unicore-cluster[timing]: on-chip diagonal selection (cap %u): %llu of %llu queries, %llu of %llu surviving keys\n", PP.td_cap,
+                (unsigned long long)PP.td_queries, (unsigned long long)PP.filt_queries, (unsigned long long)PP.td_keys, (unsigned long long)PP.filt_keys);
     uc_stats &stats = E.stats;
     unsigned long long ovl = 0;
     UC_HIP(hipMemcpy(&ovl, E.pre->d_counters.p + 2, 8, hipMemcpyDeviceToHost));
@@ -1833,6 +2064,15 @@ static bool prefilter_one(Engine &E, uint32_t tbegin, uint32_t tend, uint32_t qb
     PP.HIT_CAP_BIG = hc ? PP.HIT_CAP : (15ull << 28);
     const char *dm = getenv("UC_DRUN_MAX");
     PP.DRUN_MAX = dm ? std::max<uint64_t>(1, strtoull(dm, nullptr, 10)) : (1ull << 31);   // 24 GiB + 24 GiB sort double buffer (env: tests)
+    // UC_TD_ONCHIP=0: every query through the batch sort (A/B runs); UC_TD_ONCHIP_CAP=<keys>: a lower cap, rounded down to a power of two >= 64 (tests)
+    const char *to = getenv("UC_TD_ONCHIP"), *tc = getenv("UC_TD_ONCHIP_CAP");
+    PP.td_cap = to && atoi(to) == 0 ? 0u : TDS_CAP;
+    if (PP.td_cap && tc) {
+        const uint64_t want = strtoull(tc, nullptr, 10);
+        uint32_t c = 64;
+        while (c < TDS_CAP && 2ull * c <= want) c *= 2;
+        PP.td_cap = c;
+    }
 
     E.hit_cnt.assign(n, 0);
     E.hit_off.assign((size_t)n + 1, 0);
@@ -1843,7 +2083,8 @@ static bool prefilter_one(Engine &E, uint32_t tbegin, uint32_t tend, uint32_t qb
 
     if (n > (1u << 24)) fail(UC_ERR_GENERIC, "prefilter: %u sequences exceed the 2^24 limit of the hit keys", n);
     // counters: [0] similar k-mers, [1] kept candidates, [2] ungapped overlap residues, [3] run cursor,
-    //           [4] k-mer hits of the batch, [5] key cursor, [6] candidate cursor
+    //           [4] k-mer hits of the batch, [5] key cursor, [6] candidate cursor, [7] queries and keys that td_select_kernel took of the batch
+    //           ([3]-[6] are zeroed by cut_batch, [7] by expand_keys_filtered)
     if (!E.pre) E.pre = ParkedScratch<PrefilterScratch>::take_or_new(E.device);
     E.pre->d_counters.reserve(8);
     UC_HIP(hipMemsetAsync(E.pre->d_counters.p, 0, 64, E.stream));
