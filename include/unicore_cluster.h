@@ -269,6 +269,39 @@ int uc_engine_reassign(uc_engine *e, const uint32_t *assign_in, uint32_t *assign
 /* E8/E9 outputs from an assignment: cluster DB (<prefix>, .index, .dbtype) */
 int uc_write_cluster_db(const char *out_cluster_db, uint32_t n, const uint32_t *assign);
 
+/* ---- `unicore profile` (rule UC-P; /root/reference/src/modules/profile.rs:13-147): core genes of a clustering -------------
+ * Map: <db>.map split on whitespace, field 0 a gene name, field 1 a species; a gene named on several lines belongs to every species listed
+ * (a set); S = distinct species (profile.rs:20-29).  Rows: the TSV (clust.tsv or an .m8) split on whitespace, fields 0 (group name) and 1
+ * (gene) are used; a group is a maximal run of consecutive rows with the same field 0 (profile.rs:55-77).  Per group, every row whose gene is
+ * in the map adds 1 to cnt[s] and the gene to genes[s] for every species s of the gene (profile.rs:79-84); multiple = species with cnt >= 1,
+ * single = species with cnt == 1 (profile.rs:121-122); the group is core iff single * 100 >= threshold * S in integers (profile.rs:134).
+ * A core group's file lists `gene \t species` for every species with |genes[s]| == 1 (profile.rs:138-143: single counts rows, the file counts
+ * distinct genes); full[s] = core groups with cnt[s] == 1 (profile.rs:60-71).
+ * uc_profile_count (host, no device needed) and uc_profile_count_dev (the HIP kernels of uc_profile.hip on `device`, -1 = the current one)
+ * take the same arrays and give the same outputs:
+ *   group[n_rows]   dense group index of a row: starts at 0, never decreases, never skips, ends at n_groups - 1
+ *   gene[n_rows]    gene id < n_genes, or UC_NO_GENE for a name that is not in the map
+ *   sp_off[n_genes + 1], sp[]   gene -> species CSR, the ids of a gene distinct and ascending, each < n_species;
+ *                   species ids are the rank of the species name in byte order
+ *   single, multiple [n_groups], core [n_groups] (0 / 1), full [n_species]
+ *   core_off [n_groups + 1], core_gene / core_species: the file lines of group g are core_off[g] .. core_off[g + 1], ascending species,
+ *                   empty for a group that is not core; capacity = the number of (row, species) pairs
+ * UC_ERR_ARGS: n_groups, n_genes or n_species >= 2^24, (row, species) pairs >= 2^32, a malformed group array, CSR or gene id. */
+#define UC_NO_GENE 0xffffffffu
+int uc_profile_count(uint64_t n_rows, const uint32_t *group, const uint32_t *gene, uint32_t n_groups, uint32_t n_genes, const uint64_t *sp_off,
+                     const uint32_t *sp, uint32_t n_species, uint32_t threshold, uint32_t *single, uint32_t *multiple, uint8_t *core,
+                     uint64_t *core_off, uint32_t *core_gene, uint32_t *core_species, uint32_t *full);
+int uc_profile_count_dev(int32_t device, uint64_t n_rows, const uint32_t *group, const uint32_t *gene, uint32_t n_groups, uint32_t n_genes,
+                         const uint64_t *sp_off, const uint32_t *sp, uint32_t n_species, uint32_t threshold, uint32_t *single, uint32_t *multiple,
+                         uint8_t *core, uint64_t *core_off, uint32_t *core_gene, uint32_t *core_species, uint32_t *full);
+/* == `unicore profile -t threshold <db_prefix> <tsv> <out_dir>` (profile.rs:149-172): reads <db_prefix>.map and the TSV (the database itself is
+ * not opened), counts on o->device (UC_PROFILE_HOST=1, read per call: the host counter, no device needed), writes one <name>.txt per core group
+ * (name = the group name's second `-`-separated field, else the whole name; a later group of the same name replaces the file), copiness.tsv
+ * (always) and profile.chk ("0", then "1").  Lines inside a gene file and the warnings go by ascending species name in bytes (the reference
+ * iterates hash maps).  o->verbosity is Unicore's own 0..4 scale here.  threshold > 100 is UC_ERR_ARGS, a map line with fewer than two fields
+ * or a TSV row with fewer than two is UC_ERR_IO. */
+int uc_profile(const char *db_prefix, const char *tsv, const char *out_dir, uint32_t threshold, const uc_opts *o);
+
 /* ---- kernel-level entry points (parity tests call the HIP kernels through these) -------------- */
 /* ungapped diagonal score (E3) for n candidates (q[i], t[i], diag[i]) of the engine's DB */
 int uc_engine_ungapped_batch(uc_engine *e, uint64_t n, const uint32_t *q, const uint32_t *t,

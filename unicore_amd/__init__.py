@@ -66,7 +66,9 @@ SYMBOLS = (
     "uc_backtrace_render", "uc_format_output_check", "uc_engine_tb_emit_pass", "uc_abi_version", "uc_stats_size", "uc_set_round_hook",
     "uc_t5_gemm_variant", "uc_t5_kernel_gemm", "uc_t5_kernel_rmsnorm", "uc_t5_kernel_attention", "uc_t5_kernel_cnn_head", "uc_t5_bias_table",
     "uc_cluster_graph", "uc_engine_cluster_graph", "uc_engine_reassign", "uc_engine_td_onchip",
+    "uc_profile_count", "uc_profile_count_dev", "uc_profile",
 )
+NO_GENE = 0xFFFFFFFF  # == UC_NO_GENE: a TSV row whose gene name is not in the map
 ABI_VERSION = 9      # == UC_ABI_VERSION of include/unicore_cluster.h this binding mirrors
 ROUND_HOOK = C.CFUNCTYPE(None, C.c_void_p, C.c_int32, C.c_uint32, C.POINTER(C.c_uint32), C.c_int32, C.c_void_p)
 
@@ -140,6 +142,9 @@ def lib():
     L.uc_engine_cluster_graph.argtypes = [vp, i32, vp, u64, vp]
     L.uc_engine_reassign.argtypes = [vp, vp, vp, vp, vp]
     L.uc_write_cluster_db.argtypes = [C.c_char_p, u32, vp]
+    L.uc_profile_count.argtypes = [u64, vp, vp, u32, u32, vp, vp, u32, u32] + [vp] * 7
+    L.uc_profile_count_dev.argtypes = [i32, u64, vp, vp, u32, u32, vp, vp, u32, u32] + [vp] * 7
+    L.uc_profile.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, u32, C.POINTER(UcOpts)]
     L.uc_engine_ungapped_batch.argtypes = [vp, u64, vp, vp, vp, vp]
     L.uc_engine_ungapped_all.argtypes = [vp, u32, u32, u32, u32, u64, vp, vp]
     L.uc_engine_sw_batch.argtypes = [vp, C.c_int, u64, vp, vp, vp, vp, vp, vp, vp]
@@ -254,6 +259,42 @@ def cluster_graph(n, edges, lens, mode):
     assign = np.zeros(n, np.uint32)
     _check(lib().uc_cluster_graph(n, e.ctypes.data, len(e), ln.ctypes.data if ln is not None else None, mode, assign.ctypes.data))
     return assign
+
+
+def profile_count(group, gene, n_groups, sp_off, sp, n_species, threshold=80, device=None):
+    """The counting core of `unicore profile` (rule UC-P; uc_profile_count / uc_profile_count_dev).  group[i] = dense group index of row i,
+    gene[i] = gene id or NO_GENE, sp_off / sp = the gene -> species CSR (ascending ids).  device=None: the host counter (needs no GPU);
+    an ordinal (-1 = the current device): the HIP kernels.  Returns a dict: single, multiple, core [n_groups], full [n_species],
+    core_off [n_groups + 1], core_gene / core_species (the file lines of every core group, ascending species)."""
+    gr, ge = np.ascontiguousarray(group, np.uint32), np.ascontiguousarray(gene, np.uint32)
+    so, spv = np.ascontiguousarray(sp_off, np.uint64), np.ascontiguousarray(sp, np.uint32)
+    if len(gr) != len(ge):
+        raise ValueError("group has %d entries, gene %d" % (len(gr), len(ge)))
+    if len(so) < 1:
+        raise ValueError("sp_off needs n_genes + 1 entries")
+    n_genes = len(so) - 1
+    cnt = np.diff(so.astype(np.int64))
+    ok = (ge != NO_GENE) & (ge < n_genes)
+    cap = int(cnt[ge[ok]].sum()) if n_genes and len(ge) and (cnt >= 0).all() else 0
+    ng, ns = max(int(n_groups), 0), max(int(n_species), 0)
+    small = ng < (1 << 24) and ns < (1 << 24)      # beyond the limit the call refuses before it looks at an array
+    single, multiple = (np.zeros(ng if small else 1, np.uint32) for _ in range(2))
+    core, full = np.zeros(ng if small else 1, np.uint8), np.zeros(ns if small else 1, np.uint32)
+    core_off = np.zeros((ng if small else 0) + 1, np.uint64)
+    cg, cs = np.zeros(max(cap, 1), np.uint32), np.zeros(max(cap, 1), np.uint32)
+    args = [len(gr), gr.ctypes.data, ge.ctypes.data, n_groups, n_genes, so.ctypes.data, spv.ctypes.data, n_species, threshold,
+            single.ctypes.data, multiple.ctypes.data, core.ctypes.data, core_off.ctypes.data, cg.ctypes.data, cs.ctypes.data, full.ctypes.data]
+    _check(lib().uc_profile_count(*args) if device is None else lib().uc_profile_count_dev(device, *args))
+    n = int(core_off[-1])
+    return {"single": single, "multiple": multiple, "core": core, "full": full, "core_off": core_off, "core_gene": cg[:n].copy(), "core_species": cs[:n].copy()}
+
+
+def profile(db, tsv, out_dir, threshold=80, verbosity=1, device=-1):
+    """== `unicore profile -t threshold <db> <tsv> <out_dir>` (uc_profile): reads <db>.map and the TSV, writes one .txt per core group,
+    copiness.tsv and profile.chk into out_dir.  verbosity is Unicore's 0..4 scale.  UC_PROFILE_HOST=1 in the environment selects the
+    host counter."""
+    o = make_opts("", 1, verbosity, device)
+    _check(lib().uc_profile(db.encode(), tsv.encode(), out_dir.encode(), threshold, C.byref(o)))
 
 
 def hits_merge(n_seqs, max_seqs, parts):

@@ -1,7 +1,7 @@
-// unicore_main.cpp — C++ host mirror of the reference's `unicore cluster` (and `unicore search`) module surface.
+// unicore_main.cpp — C++ host mirror of the reference's `unicore cluster`, `unicore search` and `unicore profile` module surfaces.
 // (The reference host is Rust; no Rust toolchain exists in this image — SURVEY.md 0.2/D3 — so the host
 // above the C ABI is C++ with the same names, argument meaning and error behaviour.)
-//   CLI surface      /root/reference/src/util/arg_parser.rs:225-246  (Commands::Cluster)
+//   CLI surface      /root/reference/src/util/arg_parser.rs:225-246  (Commands::Cluster), :271-293 (Commands::Profile)
 //   module body      /root/reference/src/modules/cluster.rs:9-84     (modules::cluster::run)
 //   checkpoint       /root/reference/src/util/checkpoint.rs:2-5
 //   error/exit codes /root/reference/src/envs/error_handler.rs:5-45
@@ -160,12 +160,81 @@ constexpr int CLAP_USAGE = 2;
     exit(CLAP_USAGE);
 }
 
+void usage_profile(FILE *to) {
+    fputs("Usage: unicore profile [OPTIONS] <INPUT_DB> <INPUT_TSV> <OUTPUT>\n\n"
+         "Arguments:\n"
+         "  <INPUT_DB>   Input database (createdb output)\n"
+         "  <INPUT_TSV>  Input tsv file (cluster or search output)\n"
+         "  <OUTPUT>     Output directory\n\n"
+         "Options:\n"
+         "  -t, --threshold <THRESHOLD>      Coverage threshold for core structures. [0 - 100] [default: 80]\n"
+         "  -p, --print-copiness             Generate tsv with copy number statistics\n"
+         "      --threads <THREADS>          Number of threads to use; 0 to use all [default: 0]\n"
+         "  -v, --verbosity <VERBOSITY>      Verbosity (0: quiet, 1: +errors, 2: +warnings, 3: +info, 4: +debug) [default: 3]\n"
+         "  -h, --help                       Print help\n", to);
+}
+
+[[noreturn]] void clap_error_profile(const std::string &what) {
+    fprintf(stderr, "error: %s\n\nUsage: unicore profile [OPTIONS] <INPUT_DB> <INPUT_TSV> <OUTPUT>\n\nFor more information, try '--help'.\n", what.c_str());
+    exit(CLAP_USAGE);
+}
+
+// Commands::Profile (arg_parser.rs:271-293) + modules::profile::run (profile.rs:149-172): the output directory, profile.chk, the messages and
+// the warnings are uc_profile's, which takes Unicore's own verbosity scale
+int profile_main(int argc, char **argv) {
+    if (argc == 2) { usage_profile(stderr); return CLAP_USAGE; }   // arg_required_else_help
+    std::vector<std::string> pos;
+    uint32_t threshold = 80;      // arg_parser.rs:282
+    int verbosity = 3;
+    for (int i = 2; i < argc; i++) {
+        std::string a = argv[i];
+        auto value = [&]() -> std::string {
+            if (i + 1 >= argc) clap_error_profile("a value is required for '" + a + "' but none was supplied");
+            return argv[++i];
+        };
+        auto parse_threshold = [&](const std::string &v) {   // threshold_in_range (arg_parser.rs:18-25)
+            if (v.empty() || v.find_first_not_of("0123456789") != std::string::npos)
+                clap_error_profile("invalid value '" + v + "' for '--threshold <THRESHOLD>': Not a number");
+            const long t = v.size() > 9 ? 101 : atol(v.c_str());
+            if (t > 100) clap_error_profile("invalid value '" + v + "' for '--threshold <THRESHOLD>': Threshold `" + v + "` is not in range 0 to 100");
+            threshold = (uint32_t)t;
+        };
+        if (a == "-t" || a == "--threshold") parse_threshold(value());
+        else if (a.rfind("--threshold=", 0) == 0) parse_threshold(a.substr(12));
+        else if (a == "-p" || a == "--print-copiness") {}   // always true (arg_parser.rs:285-286)
+        else if (a == "--threads") (void)value();            // the module has no threaded part (profile.rs never reads it)
+        else if (a == "-v" || a == "--verbosity") verbosity = atoi(value().c_str());
+        else if (a == "-h" || a == "--help") { usage_profile(stdout); return 0; }
+        else if (a.size() > 1 && a[0] == '-') clap_error_profile("unexpected argument '" + a + "' found");
+        else pos.push_back(a);
+    }
+    if (pos.size() < 3) clap_error_profile("the following required arguments were not provided");
+    if (pos.size() > 3) clap_error_profile("unexpected argument '" + pos[3] + "' found");
+    if (verbosity < 0 || verbosity > 4) clap_error_profile("invalid value for '--verbosity <VERBOSITY>'");
+    g_verbosity = verbosity;
+    uc_opts o;
+    memset(&o, 0, sizeof o);
+    o.struct_size = sizeof o;
+    o.threads = 1;
+    o.verbosity = verbosity;
+    o.device = -1;
+    const int rc = uc_profile(pos[0].c_str(), pos[1].c_str(), pos[2].c_str(), threshold, &o);
+    if (rc != 0) error(ERR_GENERAL, std::string("profile failed with code ") + std::to_string(rc) + "\n" + uc_last_error());
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char **argv) {
     if (argc < 2) { usage(stderr); return CLAP_USAGE; }
     if (!strcmp(argv[1], "-h") || !strcmp(argv[1], "--help")) { usage(stdout); return 0; }
     if (!strcmp(argv[1], "version") || !strcmp(argv[1], "--version")) { puts(uc_version()); return 0; }
+    if (!strcmp(argv[1], "profile")) {
+        const int rc = profile_main(argc, argv);
+        fflush(stdout);
+        fflush(stderr);
+        _exit(rc);
+    }
     const bool is_search = !strcmp(argv[1], "search");
     if (strcmp(argv[1], "cluster") != 0 && !is_search) error(0x30 /* ERR_MODULE_NOT_IMPLEMENTED */, argv[1]);
     if (argc == 2) { if (is_search) usage_search(stderr); else usage(stderr); return CLAP_USAGE; }   // arg_required_else_help
