@@ -302,6 +302,67 @@ int uc_profile_count_dev(int32_t device, uint64_t n_rows, const uint32_t *group,
  * or a TSV row with fewer than two is UC_ERR_IO. */
 int uc_profile(const char *db_prefix, const char *tsv, const char *out_dir, uint32_t threshold, const uc_opts *o);
 
+/* ---- `unicore tree --no-inference` (rule UC-T; /root/reference/src/modules/tree.rs:17-137,299-331): a centre-star MSA of every core gene on
+ * the engine's 3Di+AA gapped stage, filtered and concatenated.  Adds entry points only: the ABI revision and uc_stats are unchanged.
+ * A *group* is one gene file, its *rows* the file's lines in order; grp_off[n_groups + 1] counts rows, every group has 1 .. 65535 of them.  Each
+ * host function (no device needed) has a _dev sibling that runs the HIP kernels of uc_msa.hip on `device` (-1 = the current one) and gives the same
+ * outputs byte for byte.
+ * uc_msa_center (UC-T/C): scores holds, group after group, the packed upper triangle of the group's pair scores: m (m - 1) / 2 values, (i, j) with
+ *   i < j at i m - i (i + 1) / 2 + (j - i - 1).  sum(i) = the sum over j != i of S(min, max) in 64 bits; centre[g] = the row with the largest sum,
+ *   the earliest among equals (a group of one row: row 0).
+ * uc_msa_star (UC-T/L and the rows): centre[g] is group-local.  res_off[n_rows + 1] / res0 / res1: the residues of every row as bytes, for n_tracks = 1
+ *   or 2 tracks on the same offsets (track 0 is the amino acids: the column counts are taken from it).  Per row: aligned (0 = all gaps), qs / ts (start
+ *   of the alignment in the centre / in the row) and the backtrace runs[run_off[r] .. run_off[r + 1]) as `length << 2 | op` (0 M, 1 I = centre residue
+ *   only, 2 D = row residue only), centre as query; the centre's own entries are not read.  Slot s of a group (0 .. Lc, Lc = the centre's length) takes
+ *   ins[s] = the longest D run any row emits after consuming exactly s centre residues (qs included); col[c] = c + ins[0] + .. + ins[c]; width = Lc +
+ *   the sum of all ins; the insert block of slot s is the ins[s] columns before col[s] (the last ins[Lc] columns for s = Lc).  Cells start as '-';
+ *   the centre's residue c goes to col[c], an M step at centre position c writes the row's residue at col[c], a D run is written left-justified
+ *   into its slot's block, an I run writes nothing.  Outputs: width[n_groups]; col (Lc entries per group, back to back); cnt (per column: rows whose
+ *   track-0 cell is not '-'; width[g] entries per group) within cnt_capacity; cells0 / cells1 (group g: m_g x width[g] bytes, row-major, back to
+ *   back) within cells_capacity bytes each.  need_out (nullable, 2): the columns and the cell bytes the call needs, set as soon as the widths are
+ *   known - also when a capacity is too small (UC_ERR_ARGS).  The centre lengths plus the lengths of all D runs bound the columns.
+ *   UC_ERR_ARGS before the device is touched: a malformed grp_off / res_off / run_off, a centre outside its group, a word that is no run (op 3 or
+ *   length 0), adjacent runs of one operation, a backtrace that overruns the centre or the row, 2^31 or more columns.
+ * uc_msa_filter (UC-T/F, tree.rs:299-331): cells is one track as uc_msa_star lays it out.  Column c of group g is kept iff cnt * 100 >= threshold * m_g
+ *   in integers (m_g counts every row).  keep (one flag per column), fwidth[n_groups], fcells (group g: m_g x fwidth[g], back to back; never more
+ *   bytes than cells).  threshold > 100 is UC_ERR_ARGS. */
+int uc_msa_center(uint32_t n_groups, const uint64_t *grp_off, const int32_t *scores, uint32_t *centre);
+int uc_msa_center_dev(int32_t device, uint32_t n_groups, const uint64_t *grp_off, const int32_t *scores, uint32_t *centre);
+int uc_msa_star(uint32_t n_groups, const uint64_t *grp_off, const uint32_t *centre, uint32_t n_tracks, const uint64_t *res_off, const uint8_t *res0, const uint8_t *res1,
+                const int32_t *qs, const int32_t *ts, const uint64_t *run_off, const uint32_t *runs, const uint8_t *aligned, uint32_t *width, uint32_t *col, uint32_t *cnt,
+                uint64_t cnt_capacity, uint8_t *cells0, uint8_t *cells1, uint64_t cells_capacity, uint64_t *need_out);
+int uc_msa_star_dev(int32_t device, uint32_t n_groups, const uint64_t *grp_off, const uint32_t *centre, uint32_t n_tracks, const uint64_t *res_off, const uint8_t *res0,
+                    const uint8_t *res1, const int32_t *qs, const int32_t *ts, const uint64_t *run_off, const uint32_t *runs, const uint8_t *aligned, uint32_t *width,
+                    uint32_t *col, uint32_t *cnt, uint64_t cnt_capacity, uint8_t *cells0, uint8_t *cells1, uint64_t cells_capacity, uint64_t *need_out);
+int uc_msa_filter(uint32_t n_groups, const uint64_t *grp_off, const uint32_t *width, const uint8_t *cells, uint32_t threshold, uint8_t *keep, uint32_t *fwidth,
+                  uint8_t *fcells);
+int uc_msa_filter_dev(int32_t device, uint32_t n_groups, const uint64_t *grp_off, const uint32_t *width, const uint8_t *cells, uint32_t threshold, uint8_t *keep,
+                      uint32_t *fwidth, uint8_t *fcells);
+/* == `unicore tree --no-inference -d threshold -o aligner_options <db_prefix> <profile_dir> <out_dir>` (tree.rs:17-137).  Reads <db>, <db>_ss, <db>_h and the
+ * *.txt files of profile_dir (ascending file name; every line `gene species`, exactly two fields, the gene a name of <db>_h: anything else is UC_ERR_IO;
+ * more than 65535 lines in a file is UC_ERR_ARGS).  Per gene file: the forward gapped score of every pair of rows (scores only) gives the centre; the
+ * centre as query against every other row runs through the gapped stage as a `-a` search does, under
+ * "-e 1e30 -c 0 --cov-mode 0 --min-seq-id 0 --rev-correction 0 --max-seqs 65535" followed by aligner_options (nullable; Foldseek-style flags, unknown
+ * ones are UC_ERR_ARGS); a row the stage does not accept is all gaps.  Layout, rendering and filter run on o->device (UC_TREE_HOST=1, read per call:
+ * the host twins; the DP needs the device either way).  Writes under out_dir: fasta/<gene>/aa.fasta, 3di.fasta (the rows as stored), <gene>.fa,
+ * <gene>_3di.fa (the MSA, both tracks on the same columns), <gene>.fa.filtered; combined.fasta (names by first appearance over the kept genes, a gene
+ * without the name contributes gaps), combined.fasta.partitions (`JTT+F+I+G, <gene>=<first>-<last>` per kept gene) and tree.chk ("0": inference is
+ * what would set it to "1").  A gene that keeps no column is left out with a warning.  If out_dir/combined.fasta exists the call says so and returns
+ * UC_OK without touching anything.  o->verbosity is Unicore's own 0..4 scale.  UC_TREE_BUDGET_BYTES (default 512 MiB) bounds the pairs of one scoring
+ * batch and the cells of one layout call (whole groups; results do not depend on it); UC_TREE_DUMP=1 also writes fasta/<gene>/pair_scores.tsv. */
+#define UC_TREE_NPHASE 7
+typedef struct uc_tree_stats {
+    uint64_t n_groups, n_rows;           /* gene files, their lines */
+    uint64_t n_pairs_scored;             /* forward DPs of the all-pairs pass */
+    uint64_t n_rows_unaligned;
+    uint64_t n_columns, n_columns_kept;  /* before / after the filter, summed over the genes */
+    uint64_t n_groups_dropped;           /* genes without a row or without a kept column */
+    double seconds[UC_TREE_NPHASE];      /* host wall: [0] reading, [1] all-pairs scores, [2] centres, [3] centre alignments, [4] layout + render + filter,
+                                            [5] writing, [6] the whole call */
+} uc_tree_stats;
+int uc_tree(const char *db_prefix, const char *profile_dir, const char *out_dir, uint32_t threshold, const char *aligner_options, const uc_opts *o,
+            uc_tree_stats *stats_out);
+
 /* ---- kernel-level entry points (parity tests call the HIP kernels through these) -------------- */
 /* ungapped diagonal score (E3) for n candidates (q[i], t[i], diag[i]) of the engine's DB */
 int uc_engine_ungapped_batch(uc_engine *e, uint64_t n, const uint32_t *q, const uint32_t *t,

@@ -43,6 +43,14 @@ class UcStats(C.Structure):
         return d
 
 
+class UcTreeStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("n_groups", "n_rows", "n_pairs_scored", "n_rows_unaligned", "n_columns", "n_columns_kept", "n_groups_dropped")] + [
+        ("seconds", C.c_double * 7)]
+
+
+TREE_PHASES = ("read", "pair_scores", "centres", "centre_alignments", "layout_render_filter", "write", "total")
+
+
 class UcT5Stats(C.Structure):
     _fields_ = [("n_seqs", C.c_uint64), ("n_tokens", C.c_uint64), ("flops", C.c_double), ("gpu_ms", C.c_double),
                 ("n_replicas", C.c_uint32), ("reserved0", C.c_uint32), ("gpu_ms_sum", C.c_double),
@@ -67,6 +75,7 @@ SYMBOLS = (
     "uc_t5_gemm_variant", "uc_t5_kernel_gemm", "uc_t5_kernel_rmsnorm", "uc_t5_kernel_attention", "uc_t5_kernel_cnn_head", "uc_t5_bias_table",
     "uc_cluster_graph", "uc_engine_cluster_graph", "uc_engine_reassign", "uc_engine_td_onchip",
     "uc_profile_count", "uc_profile_count_dev", "uc_profile",
+    "uc_msa_center", "uc_msa_center_dev", "uc_msa_star", "uc_msa_star_dev", "uc_msa_filter", "uc_msa_filter_dev", "uc_tree",
 )
 NO_GENE = 0xFFFFFFFF  # == UC_NO_GENE: a TSV row whose gene name is not in the map
 ABI_VERSION = 9      # == UC_ABI_VERSION of include/unicore_cluster.h this binding mirrors
@@ -145,6 +154,13 @@ def lib():
     L.uc_profile_count.argtypes = [u64, vp, vp, u32, u32, vp, vp, u32, u32] + [vp] * 7
     L.uc_profile_count_dev.argtypes = [i32, u64, vp, vp, u32, u32, vp, vp, u32, u32] + [vp] * 7
     L.uc_profile.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, u32, C.POINTER(UcOpts)]
+    L.uc_msa_center.argtypes = [u32, vp, vp, vp]
+    L.uc_msa_center_dev.argtypes = [i32, u32, vp, vp, vp]
+    L.uc_msa_star.argtypes = [u32, vp, vp, u32] + [vp] * 8 + [vp, vp, vp, u64, vp, vp, u64, vp]
+    L.uc_msa_star_dev.argtypes = [i32] + L.uc_msa_star.argtypes
+    L.uc_msa_filter.argtypes = [u32, vp, vp, vp, u32, vp, vp, vp]
+    L.uc_msa_filter_dev.argtypes = [i32] + L.uc_msa_filter.argtypes
+    L.uc_tree.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, u32, C.c_char_p, C.POINTER(UcOpts), C.POINTER(UcTreeStats)]
     L.uc_engine_ungapped_batch.argtypes = [vp, u64, vp, vp, vp, vp]
     L.uc_engine_ungapped_all.argtypes = [vp, u32, u32, u32, u32, u64, vp, vp]
     L.uc_engine_sw_batch.argtypes = [vp, C.c_int, u64, vp, vp, vp, vp, vp, vp, vp]
@@ -295,6 +311,95 @@ def profile(db, tsv, out_dir, threshold=80, verbosity=1, device=-1):
     host counter."""
     o = make_opts("", 1, verbosity, device)
     _check(lib().uc_profile(db.encode(), tsv.encode(), out_dir.encode(), threshold, C.byref(o)))
+
+
+def _ptr(a):
+    return a.ctypes.data if a is not None and a.size else None
+
+
+def msa_center(grp_off, scores, device=None):
+    """UC-T/C (uc_msa_center / uc_msa_center_dev): grp_off [n_groups + 1] counts rows, scores holds every group's packed upper triangle of pair
+    scores (row-major over i < j), groups back to back.  Returns centre [n_groups]: per group the row with the largest 64-bit row sum, the
+    earliest among equals.  device=None: the host twin (needs no GPU); an ordinal (-1 = the current device): the HIP kernels."""
+    go, sc = np.ascontiguousarray(grp_off, np.uint64), np.ascontiguousarray(scores, np.int32)
+    ng = len(go) - 1
+    if ng < 0:
+        raise ValueError("grp_off needs n_groups + 1 entries")
+    m = np.diff(go.astype(np.int64))
+    if ng and (m >= 0).all() and len(sc) != int((m * (m - 1) // 2).sum()):
+        raise ValueError("scores has %d entries, the triangles hold %d" % (len(sc), int((m * (m - 1) // 2).sum())))
+    centre = np.zeros(max(ng, 1), np.uint32)
+    args = [ng, go.ctypes.data, _ptr(sc), centre.ctypes.data]
+    _check(lib().uc_msa_center(*args) if device is None else lib().uc_msa_center_dev(device, *args))
+    return centre[:ng]
+
+
+def msa_star(grp_off, centre, res_off, res, qs, ts, run_off, runs, aligned, device=None):
+    """UC-T/L and the rows (uc_msa_star / uc_msa_star_dev).  res: one or two byte arrays (tracks) on the offsets res_off [n_rows + 1]; per row qs, ts,
+    aligned and the backtrace runs[run_off[r]:run_off[r + 1]] (length << 2 | op; 0 M, 1 I, 2 D; centre as query).  Returns a dict: width [n_groups],
+    col (the centre positions' columns, groups back to back), cnt (rows with a residue per column of track 0), cells (list, one flat uint8 array
+    per track: group g holds m_g x width[g] bytes, row-major).  device as in msa_center."""
+    go, ce = np.ascontiguousarray(grp_off, np.uint64), np.ascontiguousarray(centre, np.uint32)
+    ro, uo = np.ascontiguousarray(res_off, np.uint64), np.ascontiguousarray(run_off, np.uint64)
+    tracks = [np.ascontiguousarray(t, np.uint8) for t in (res if isinstance(res, (list, tuple)) else [res])]
+    q, t, al = np.ascontiguousarray(qs, np.int32), np.ascontiguousarray(ts, np.int32), np.ascontiguousarray(aligned, np.uint8)
+    ru = np.ascontiguousarray(runs, np.uint32)
+    ng = len(go) - 1
+    n_rows = int(go[-1]) if ng > 0 else 0
+    if len(ce) != ng or any(len(x) != n_rows for x in (q, t, al)) or len(ro) != n_rows + 1 or len(uo) != n_rows + 1:
+        raise ValueError("array lengths do not match grp_off")
+    if n_rows and (int(uo[-1]) > len(ru) or any(int(ro[-1]) > len(x) for x in tracks) or len({len(x) for x in tracks}) != 1):
+        raise ValueError("res_off / run_off reach beyond the arrays they index")
+    # capacities from the bound the call itself uses: centre lengths + every D run, per group times its rows
+    ln = np.diff(ro.astype(np.int64))
+    dl = np.where((ru & 3) == 2, ru >> 2, 0).astype(np.int64)
+    dcum = np.concatenate([[0], np.cumsum(dl)])
+    cols = cells = ncol = 0
+    for g in range(ng):
+        b, e = int(go[g]), int(go[g + 1])
+        if not (0 <= b <= e <= n_rows) or int(ce[g]) >= max(e - b, 1) or not (0 <= int(uo[b]) <= int(uo[e]) <= len(ru)):
+            continue      # the call refuses these itself
+        lc = max(int(ln[b + int(ce[g])]), 0)
+        w = lc + int(dcum[int(uo[e])] - dcum[int(uo[b])])
+        cols += w; cells += (e - b) * w; ncol += lc
+    width, col, cnt = np.zeros(max(ng, 1), np.uint32), np.zeros(max(ncol, 1), np.uint32), np.zeros(max(cols, 1), np.uint32)
+    out = [np.zeros(max(cells, 1), np.uint8) for _ in tracks]
+    need = np.zeros(2, np.uint64)
+    args = [ng, go.ctypes.data, _ptr(ce), len(tracks), ro.ctypes.data, _ptr(tracks[0]), _ptr(tracks[1]) if len(tracks) > 1 else None, _ptr(q), _ptr(t),
+            uo.ctypes.data, _ptr(ru), _ptr(al), width.ctypes.data, col.ctypes.data, cnt.ctypes.data, cols, out[0].ctypes.data,
+            out[1].ctypes.data if len(tracks) > 1 else None, cells, need.ctypes.data]
+    _check(lib().uc_msa_star(*args) if device is None else lib().uc_msa_star_dev(device, *args))
+    return {"width": width[:ng], "col": col[:ncol], "cnt": cnt[: int(need[0])].copy(), "cells": [o[: int(need[1])].copy() for o in out]}
+
+
+def msa_filter(grp_off, width, cells, threshold, device=None):
+    """UC-T/F (uc_msa_filter / uc_msa_filter_dev): cells is one track as msa_star lays it out; column c of group g is kept iff cnt * 100 >=
+    threshold * m_g.  Returns a dict: keep (uint8 per column), fwidth [n_groups], fcells (flat: group g holds m_g x fwidth[g] bytes)."""
+    go, w, ce = np.ascontiguousarray(grp_off, np.uint64), np.ascontiguousarray(width, np.uint32), np.ascontiguousarray(cells, np.uint8)
+    ng = len(go) - 1
+    if len(w) != ng:
+        raise ValueError("width has %d entries for %d groups" % (len(w), ng))
+    m = np.diff(go.astype(np.int64))
+    ncols, ncells = int(w.astype(np.int64).sum()), int((m * w.astype(np.int64)).sum()) if ng else 0
+    if len(ce) != max(ncells, 0) and ng and (m > 0).all():
+        raise ValueError("cells has %d bytes, the groups hold %d" % (len(ce), ncells))
+    keep, fwidth, fcells = np.zeros(max(ncols, 1), np.uint8), np.zeros(max(ng, 1), np.uint32), np.zeros(max(ncells, 1), np.uint8)
+    args = [ng, go.ctypes.data, _ptr(w), _ptr(ce), threshold, keep.ctypes.data, fwidth.ctypes.data, fcells.ctypes.data]
+    _check(lib().uc_msa_filter(*args) if device is None else lib().uc_msa_filter_dev(device, *args))
+    nf = int((m * fwidth[:ng].astype(np.int64)).sum()) if ng else 0
+    return {"keep": keep[:ncols], "fwidth": fwidth[:ng], "fcells": fcells[:nf].copy()}
+
+
+def tree(db, profile_dir, out_dir, threshold=50, aligner_options="", verbosity=1, device=-1):
+    """== `unicore tree --no-inference -d threshold -o aligner_options <db> <profile_dir> <out_dir>` (uc_tree): a centre-star MSA of every gene
+    file of a `profile` output on the engine's gapped stage, filtered and concatenated into out_dir/combined.fasta (+ .partitions, fasta/<gene>/*,
+    tree.chk).  verbosity is Unicore's 0..4 scale.  UC_TREE_HOST=1 in the environment runs layout, rendering and filter through the host twins.
+    Returns the stats dict (counts and seconds per phase)."""
+    o, st = make_opts("", 1, verbosity, device), UcTreeStats()
+    _check(lib().uc_tree(db.encode(), profile_dir.encode(), out_dir.encode(), threshold, (aligner_options or "").encode(), C.byref(o), C.byref(st)))
+    d = {k: int(getattr(st, k)) for k, _ in UcTreeStats._fields_ if k != "seconds"}
+    d["seconds"] = dict(zip(TREE_PHASES, st.seconds))
+    return d
 
 
 def hits_merge(n_seqs, max_seqs, parts):

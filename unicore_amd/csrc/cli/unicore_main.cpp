@@ -1,7 +1,7 @@
-// unicore_main.cpp — C++ host mirror of the reference's `unicore cluster`, `unicore search` and `unicore profile` module surfaces.
+// unicore_main.cpp — C++ host mirror of the reference's `unicore cluster`, `unicore search`, `unicore profile` and `unicore tree --no-inference` module surfaces.
 // (The reference host is Rust; no Rust toolchain exists in this image — SURVEY.md 0.2/D3 — so the host
 // above the C ABI is C++ with the same names, argument meaning and error behaviour.)
-//   CLI surface      /root/reference/src/util/arg_parser.rs:225-246  (Commands::Cluster), :271-293 (Commands::Profile)
+//   CLI surface      /root/reference/src/util/arg_parser.rs:225-246  (Commands::Cluster), :271-293 (Commands::Profile), :296-330 (Commands::Tree)
 //   module body      /root/reference/src/modules/cluster.rs:9-84     (modules::cluster::run)
 //   checkpoint       /root/reference/src/util/checkpoint.rs:2-5
 //   error/exit codes /root/reference/src/envs/error_handler.rs:5-45
@@ -223,6 +223,89 @@ int profile_main(int argc, char **argv) {
     return 0;
 }
 
+void usage_tree(FILE *to) {
+    fputs("Usage: unicore tree [OPTIONS] --no-inference <DB> <INPUT> <OUTPUT>\n\n"
+         "Arguments:\n"
+         "  <DB>      Input database (createdb output)\n"
+         "  <INPUT>   Input directory containing core structures (profile output)\n"
+         "  <OUTPUT>  Output directory\n\n"
+         "Options:\n"
+         "  -a, --aligner <ALIGNER>                  Multiple sequence aligner [star]; foldmason, mafft-linsi and mafft are external programs and are refused [default: star]\n"
+         "  -t, --tree-builder <TREE_BUILDER>        Phylogenetic tree builder [iqtree, fasttree, raxml-ng]; parsed, not run [default: iqtree]\n"
+         "  -o, --aligner-options <ALIGNER_OPTIONS>  Foldseek-style options for the gapped stage behind the star aligner, e.g. -o \"--gap-open 12\"\n"
+         "  -n, --no-inference                       Stop the tree module after alignment (before tree inference); required: inference is not built in\n"
+         "  -p, --tree-options <TREE_OPTIONS>        Options for tree builder; parsed, not used\n"
+         "  -d, --threshold <THRESHOLD>              Gap threshold for multiple sequence alignment [0 - 100] [default: 50]\n"
+         "  -c, --threads <THREADS>                  Number of threads to use; 0 to use all [default: 0]\n"
+         "  -v, --verbosity <VERBOSITY>              Verbosity (0: quiet, 1: +errors, 2: +warnings, 3: +info, 4: +debug) [default: 3]\n"
+         "  -h, --help                               Print help\n", to);
+}
+
+[[noreturn]] void clap_error_tree(const std::string &what) {
+    fprintf(stderr, "error: %s\n\nUsage: unicore tree [OPTIONS] --no-inference <DB> <INPUT> <OUTPUT>\n\nFor more information, try '--help'.\n", what.c_str());
+    exit(CLAP_USAGE);
+}
+
+// Commands::Tree (arg_parser.rs:296-330) + modules::tree::run up to `if no_inference { return }` (tree.rs:17-134): files, tree.chk and messages are
+// uc_tree's, which takes Unicore's own verbosity scale.  The aligner is the built-in centre-star MSA; the reference's aligners and every tree builder
+// are external programs, which this host does not start.
+int tree_main(int argc, char **argv) {
+    std::vector<std::string> pos;
+    std::string aligner = "star", builder = "iqtree", aligner_options;
+    bool no_inference = false;
+    uint32_t threshold = 50;      // arg_parser.rs:322
+    int verbosity = 3;
+    for (int i = 2; i < argc; i++) {
+        std::string a = argv[i];
+        auto value = [&]() -> std::string {
+            if (i + 1 >= argc) clap_error_tree("a value is required for '" + a + "' but none was supplied");
+            return argv[++i];
+        };
+        auto parse_threshold = [&](const std::string &v) {   // threshold_in_range (arg_parser.rs:18-25)
+            if (v.empty() || v.find_first_not_of("0123456789") != std::string::npos)
+                clap_error_tree("invalid value '" + v + "' for '--threshold <THRESHOLD>': Not a number");
+            const long t = v.size() > 9 ? 101 : atol(v.c_str());
+            if (t > 100) clap_error_tree("invalid value '" + v + "' for '--threshold <THRESHOLD>': Threshold `" + v + "` is not in range 0 to 100");
+            threshold = (uint32_t)t;
+        };
+        if (a == "-a" || a == "--aligner") aligner = value();
+        else if (a.rfind("--aligner=", 0) == 0) aligner = a.substr(10);
+        else if (a == "-t" || a == "--tree-builder") builder = value();
+        else if (a.rfind("--tree-builder=", 0) == 0) builder = a.substr(15);
+        else if (a == "-o" || a == "--aligner-options") aligner_options = value();
+        else if (a.rfind("--aligner-options=", 0) == 0) aligner_options = a.substr(18);
+        else if (a == "-p" || a == "--tree-options") (void)value();
+        else if (a.rfind("--tree-options=", 0) == 0) {}
+        else if (a == "-n" || a == "--no-inference") no_inference = true;
+        else if (a == "-d" || a == "--threshold") parse_threshold(value());
+        else if (a.rfind("--threshold=", 0) == 0) parse_threshold(a.substr(12));
+        else if (a == "-c" || a == "--threads") (void)value();      // the module's host side has no threaded part
+        else if (a == "-v" || a == "--verbosity") verbosity = atoi(value().c_str());
+        else if (a == "-h" || a == "--help") { usage_tree(stdout); return 0; }
+        else if (a.size() > 1 && a[0] == '-') clap_error_tree("unexpected argument '" + a + "' found");
+        else pos.push_back(a);
+    }
+    if (pos.size() < 3) clap_error_tree("the following required arguments were not provided");
+    if (pos.size() > 3) clap_error_tree("unexpected argument '" + pos[3] + "' found");
+    if (verbosity < 0 || verbosity > 4) clap_error_tree("invalid value for '--verbosity <VERBOSITY>'");
+    g_verbosity = verbosity;
+    if (aligner == "foldmason" || aligner == "mafft" || aligner == "mafft-linsi")      // tree.rs:42-45: ERR_BINARY_NOT_FOUND in the reference
+        error(ERR_GENERAL, "aligner " + aligner + " is an external program, which this build does not start; the built-in aligner is 'star'");
+    if (aligner != "star") error(ERR_GENERAL, "Unrecognized aligner");                  // tree.rs:118
+    if (builder != "iqtree" && builder != "fasttree" && builder != "raxml-ng") error(ERR_GENERAL, "Unrecognized tree builder");   // tree.rs:146
+    if (!no_inference)
+        error(ERR_GENERAL, "tree inference would start the external program " + builder + ", which this build does not do; pass -n/--no-inference and run it on combined.fasta");
+    uc_opts o;
+    memset(&o, 0, sizeof o);
+    o.struct_size = sizeof o;
+    o.threads = 1;
+    o.verbosity = verbosity;
+    o.device = -1;
+    const int rc = uc_tree(pos[0].c_str(), pos[1].c_str(), pos[2].c_str(), threshold, aligner_options.c_str(), &o, nullptr);
+    if (rc != 0) error(ERR_GENERAL, std::string("tree failed with code ") + std::to_string(rc) + "\n" + uc_last_error());
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char **argv) {
@@ -231,6 +314,12 @@ int main(int argc, char **argv) {
     if (!strcmp(argv[1], "version") || !strcmp(argv[1], "--version")) { puts(uc_version()); return 0; }
     if (!strcmp(argv[1], "profile")) {
         const int rc = profile_main(argc, argv);
+        fflush(stdout);
+        fflush(stderr);
+        _exit(rc);
+    }
+    if (!strcmp(argv[1], "tree") && argc > 2) {      // bare `unicore tree` keeps its earlier answer below (ERR_MODULE_NOT_IMPLEMENTED)
+        const int rc = tree_main(argc, argv);
         fflush(stdout);
         fflush(stderr);
         _exit(rc);

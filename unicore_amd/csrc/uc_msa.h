@@ -1,0 +1,70 @@
+// uc_msa.h — the star MSA of `unicore tree --no-inference` (rule UC-T): argument blocks, the checks both sides share, the host
+// twins (uc_msa_host.cpp) and the device side (uc_msa.hip).  Host and device take the same arrays and give the same outputs.
+#pragma once
+#include <cstdint>
+#include <vector>
+
+#include "uc_common.h"
+
+namespace uc {
+
+constexpr uint32_t MSA_MAX_ROWS = 65535;      // rows of one group (the engine's --max-seqs limit: the centre's hit list holds the group)
+
+// ---- UC-T/C: the centre of every group from its packed upper triangle of pair scores
+struct MsaCenterArgs {
+    uint32_t n_groups;
+    const uint64_t *grp_off;      // n_groups + 1, rows
+    const int32_t *scores;        // group g: m (m - 1) / 2 scores, (i, j) with i < j at i m - i (i + 1) / 2 + (j - i - 1), groups back to back
+    uint32_t *centre;             // n_groups, group-local row
+};
+// tri_off [n_groups + 1]: where every group's triangle starts (UC_ERR_ARGS on a malformed grp_off, an empty group, a group beyond MSA_MAX_ROWS)
+void msa_center_validate(const MsaCenterArgs &a, std::vector<uint64_t> &tri_off);
+void msa_center_host(const MsaCenterArgs &a, const std::vector<uint64_t> &tri_off);
+void msa_center_device(int device, const MsaCenterArgs &a, const std::vector<uint64_t> &tri_off);
+
+// ---- UC-T/L + rows: layout and rendering
+struct MsaStarArgs {
+    uint32_t n_groups;
+    const uint64_t *grp_off;
+    const uint32_t *centre;
+    uint32_t n_tracks;            // 1 or 2; track 0 is the one the column counts are taken from (the amino acids)
+    const uint64_t *res_off;      // n_rows + 1 into res[*]
+    const uint8_t *res[2];
+    const int32_t *qs, *ts;       // per row: start of the box in the centre / in the row
+    const uint64_t *run_off;      // n_rows + 1 into runs
+    const uint32_t *runs;         // length << 2 | op (0 M, 1 I, 2 D)
+    const uint8_t *aligned;       // per row; the centre's own entry is not read
+    uint32_t *width;              // n_groups
+    uint32_t *col;                // sum of the centre lengths, groups back to back
+    uint32_t *cnt;                // sum of the widths
+    uint64_t cnt_capacity;
+    uint8_t *cells[2];            // group g: m_g x width[g] bytes, row-major, groups back to back
+    uint64_t cells_capacity;
+    uint64_t *need;               // nullable, 2: columns and cell bytes (per track) the call needs
+};
+struct MsaStarPlan {
+    uint64_t n_rows = 0;
+    std::vector<uint64_t> slot_off;      // n_groups + 1: a group has centre length + 1 insert slots
+    uint64_t max_columns = 0;            // bound on the sum of the widths: centre lengths + every D run
+};
+void msa_star_validate(const MsaStarArgs &a, MsaStarPlan &plan);
+void msa_star_host(const MsaStarArgs &a, const MsaStarPlan &plan);
+void msa_star_device(int device, const MsaStarArgs &a, const MsaStarPlan &plan);
+
+// ---- UC-T/F: the column filter
+struct MsaFilterArgs {
+    uint32_t n_groups;
+    const uint64_t *grp_off;
+    const uint32_t *width;
+    const uint8_t *cells;         // one track, laid out as MsaStarArgs::cells
+    uint32_t threshold;           // 0 .. 100
+    uint8_t *keep;                // sum of the widths
+    uint32_t *fwidth;             // n_groups
+    uint8_t *fcells;              // group g: m_g x fwidth[g]; the capacity of `cells` always suffices
+};
+struct MsaFilterPlan { std::vector<uint64_t> col_off, cell_off; };      // n_groups + 1 each
+void msa_filter_validate(const MsaFilterArgs &a, MsaFilterPlan &plan);
+void msa_filter_host(const MsaFilterArgs &a, const MsaFilterPlan &plan);
+void msa_filter_device(int device, const MsaFilterArgs &a, const MsaFilterPlan &plan);
+
+}  // namespace uc

@@ -16,6 +16,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "uc_files.h"
 #include "uc_profile.h"
 
 namespace uc {
@@ -96,23 +97,6 @@ void profile_count_host(const ProfileArgs &a, uint64_t) {
 
 namespace {
 
-template <typename F>
-int guard(F &&f) {
-    try {
-        f();
-        return UC_OK;
-    } catch (const Error &e) {
-        set_last_error(e.what());
-        return e.code;
-    } catch (const std::bad_alloc &) {
-        set_last_error("out of host memory");
-        return UC_ERR_GENERIC;
-    } catch (const std::exception &e) {
-        set_last_error(e.what());
-        return UC_ERR_GENERIC;
-    }
-}
-
 std::string slurp(const std::string &path) {
     std::ifstream f(path, std::ios::binary);
     if (!f) fail(UC_ERR_IO, "cannot open %s", path.c_str());
@@ -123,8 +107,6 @@ std::string slurp(const std::string &path) {
     if (n > 0 && !f.read(&s[0], n)) fail(UC_ERR_IO, "cannot read %s", path.c_str());
     return s;
 }
-
-inline bool is_space(char c) { return c == ' ' || (c >= '\t' && c <= '\r'); }
 
 // the first two whitespace-separated fields of every line (profile.rs:21,51); a line with fewer is an error
 template <typename F>
@@ -145,24 +127,6 @@ void two_fields(const std::string &text, const std::string &path, F &&row) {
         if (k < 2) fail(UC_ERR_IO, "%s: line %zu has fewer than two fields", path.c_str(), line);
         row(f[0], f[1]);
         p = e + 1;
-    }
-}
-
-void write_file(const std::string &path, const std::string &content) {
-    FILE *f = fopen(path.c_str(), "wb");
-    if (!f) fail(UC_ERR_IO, "cannot write %s", path.c_str());
-    const bool ok = fwrite(content.data(), 1, content.size(), f) == content.size();
-    if (fclose(f) != 0 || !ok) fail(UC_ERR_IO, "cannot write %s", path.c_str());
-}
-
-void make_dirs(const std::string &path) {      // profile.rs:158-160
-    std::string cur;
-    for (size_t i = 0; i <= path.size(); i++) {
-        if ((i == path.size() || path[i] == '/') && !cur.empty() && cur != "/") {
-            struct stat st;
-            if (stat(cur.c_str(), &st) != 0 && mkdir(cur.c_str(), 0777) != 0 && stat(cur.c_str(), &st) != 0) fail(UC_ERR_IO, "cannot create directory %s", cur.c_str());
-        }
-        if (i < path.size()) cur.push_back(path[i]);
     }
 }
 
