@@ -245,6 +245,13 @@ void uc_engine_reset_stats(uc_engine *e);
  * keys it took, out[3] surviving keys (= n_filtered_hits of that path); UC_TD_ONCHIP=0 leaves [0] and [2] at 0 */
 int uc_engine_td_onchip(const uc_engine *e, uint64_t *out /* 4 */);
 
+/* Kernel-level entry of the linear-time pre-step (E8a, uc_linclust.hip) on the engine's database; test support, uc_stats is untouched.
+ * m <= 0: the engine's --kmer-per-seq, otherwise m in [1,1000] replaces it for this call.  install = 0: *n_out = number of sorted unique
+ * (centre, member) pairs, copied to out_pairs[2 * i ..] when they fit into cap pairs (cap = 0: count only).  install = 1: the pairs become the
+ * engine's hit lists (query = centre, score 0, diag 0; read them with uc_engine_hits_get), *n_out = their number, out_pairs is not written.
+ * m > 1000, another install value or a missing pointer: UC_ERR_ARGS before the device is touched. */
+int uc_engine_linclust_pairs(uc_engine *e, int32_t m, int32_t install, uint32_t *out_pairs, uint64_t cap, uint64_t *n_out);
+
 /* E7 (host, as the north star prescribes): greedy set cover over (a,b) pairs; assign[i] = representative */
 int uc_setcover(uint32_t n, const uint32_t *edges, uint64_t n_edges, uint32_t *assign);
 /* the same result with the graph built on the engine's GPU (sort + unique of the edge list) and only the greedy

@@ -20,6 +20,7 @@ def test_library_loads_and_exports_every_declared_symbol():
     declared = set(re.findall(r"\b(uc_[a-z_0-9]+)\s*\(", hdr))
     assert declared == set(U.SYMBOLS), declared ^ set(U.SYMBOLS)
     assert {"uc_engine_sw_batch", "uc_engine_sw_pass"} <= declared      # kernel-level entries of the gapped stage (tests/test_sw_kernels.py)
+    assert "uc_engine_linclust_pairs" in declared                       # kernel-level entry of the linear-time pre-step (tests/test_linclust_kernels_gpu.py)
     for s in declared:
         assert hasattr(L, s), s
     assert "gfx950" in U.version()

@@ -73,7 +73,7 @@ SYMBOLS = (
     "uc_engine_ungapped_batch", "uc_engine_ungapped_all", "uc_engine_sw_batch", "uc_engine_sw_pass", "uc_engine_sw_pass2", "uc_engine_backtraces_size", "uc_engine_backtraces_get",
     "uc_backtrace_render", "uc_format_output_check", "uc_engine_tb_emit_pass", "uc_abi_version", "uc_stats_size", "uc_set_round_hook",
     "uc_t5_gemm_variant", "uc_t5_kernel_gemm", "uc_t5_kernel_rmsnorm", "uc_t5_kernel_attention", "uc_t5_kernel_cnn_head", "uc_t5_bias_table",
-    "uc_cluster_graph", "uc_engine_cluster_graph", "uc_engine_reassign", "uc_engine_td_onchip",
+    "uc_cluster_graph", "uc_engine_cluster_graph", "uc_engine_reassign", "uc_engine_td_onchip", "uc_engine_linclust_pairs",
     "uc_profile_count", "uc_profile_count_dev", "uc_profile",
     "uc_msa_center", "uc_msa_center_dev", "uc_msa_star", "uc_msa_star_dev", "uc_msa_filter", "uc_msa_filter_dev", "uc_tree",
 )
@@ -146,6 +146,7 @@ def lib():
     L.uc_engine_reset_stats.argtypes = [vp]
     L.uc_engine_reset_stats.restype = None
     L.uc_engine_td_onchip.argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.uc_engine_linclust_pairs.argtypes = [vp, i32, i32, vp, u64, C.POINTER(u64)]
     L.uc_setcover.argtypes = [u32, vp, u64, vp]
     L.uc_cluster_graph.argtypes = [u32, vp, u64, vp, i32, vp]
     L.uc_engine_cluster_graph.argtypes = [vp, i32, vp, u64, vp]
@@ -687,6 +688,25 @@ class Engine:
         out, rej, cnt = np.zeros(self.n, np.uint32), np.zeros(max(self.n, 1), np.uint8), np.zeros(4, np.uint64)
         _check(lib().uc_engine_reassign(self._h, a.ctypes.data, out.ctypes.data, rej.ctypes.data, cnt.ctypes.data))
         return out, rej[: self.n].astype(bool), dict(zip(("verified", "rejected", "research_accepted", "clusters"), (int(x) for x in cnt)))
+
+    def linclust_pairs(self, m=None, install=False):
+        """E8a on the engine's database (uc_engine_linclust_pairs): the sorted unique (centre, member) pairs as uint32 [np, 2]; m=None takes the
+        engine's --kmer-per-seq, otherwise m in [1, 1000].  install=True makes them the engine's hit lists (read them with hits()) and returns
+        their number."""
+        k = C.c_uint64()
+        mm = 0 if m is None else int(m)
+        if mm < 0 or (m is not None and mm == 0):
+            raise UcError(UC_ERR_ARGS, "linclust_pairs: m must be None or in [1, 1000]")
+        if install:
+            _check(lib().uc_engine_linclust_pairs(self._h, mm, 1, None, 0, C.byref(k)))
+            return int(k.value)
+        cap = 1 << 16
+        while True:
+            out = np.zeros((cap, 2), np.uint32)
+            _check(lib().uc_engine_linclust_pairs(self._h, mm, 0, out.ctypes.data, cap, C.byref(k)))
+            if k.value <= cap:
+                return out[: k.value].copy()
+            cap = int(k.value)
 
     def align(self, qbegin=0, qend=None):
         _check(lib().uc_engine_align(self._h, qbegin, self.n if qend is None else qend))

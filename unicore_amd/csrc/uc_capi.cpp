@@ -433,6 +433,20 @@ int uc_engine_td_onchip(const uc_engine *e, uint64_t *out) {
     return guard([&] { require(e, "engine"); require(out, "out"); for (int i = 0; i < 4; i++) out[i] = e->e->td_onchip[i]; });
 }
 
+int uc_engine_linclust_pairs(uc_engine *e, int32_t m, int32_t install, uint32_t *out_pairs, uint64_t cap, uint64_t *n_out) {
+    return guard([&] {
+        require(e, "engine"); require(n_out, "n_out");
+        if (m > 1000) fail(UC_ERR_ARGS, "uc_engine_linclust_pairs: m must be <= 0 (the engine's --kmer-per-seq) or in [1,1000]");
+        if (install != 0 && install != 1) fail(UC_ERR_ARGS, "uc_engine_linclust_pairs: install must be 0 or 1");
+        if (cap && !install) require(out_pairs, "out_pairs");
+        const int mo = m > 0 ? m : 0;
+        if (install) { *n_out = e->e->linclust_hits(mo); return; }
+        const std::vector<uint32_t> pr = e->e->linclust_pairs(mo);
+        *n_out = pr.size() / 2;
+        if (!pr.empty() && pr.size() / 2 <= cap) memcpy(out_pairs, pr.data(), pr.size() * 4);
+    });
+}
+
 int uc_setcover(uint32_t n, const uint32_t *edges, uint64_t n_edges, uint32_t *assign) {
     return guard([&] {
         if (n) require(assign, "assign");

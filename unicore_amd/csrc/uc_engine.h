@@ -356,9 +356,10 @@ struct Engine {
     void reassign(const uint32_t *assign_in, uint32_t *assign_out, uint8_t *rejected_out, uint64_t counts[4]);
     ReassignScratch &reassign_scratch();
     // E8a: (centre, member) candidate pairs of the linear-time pre-step for the resident DB, sorted by (centre, member), unique (uc_linclust.hip)
-    std::vector<uint32_t> linclust_pairs();
-    uint64_t linclust_hits();                                        // ... installed as the hit lists (query = centre); returns the pair count
-    std::vector<uint32_t> linclust_pairs_impl(uint64_t *install);
+    // m_override > 0 replaces p.kmer_per_seq for this call (kernel-level tests: one engine serves every m)
+    std::vector<uint32_t> linclust_pairs(int m_override = 0);
+    uint64_t linclust_hits(int m_override = 0);                      // ... installed as the hit lists (query = centre); returns the pair count
+    std::vector<uint32_t> linclust_pairs_impl(uint64_t *install, int m_override);
     // kernel-level
     void ungapped_batch(uint64_t n, const uint32_t *q, const uint32_t *t, const int32_t *diag, int32_t *out);
     // rule UC-1/X: dense [q1 - q0][t1 - t0] scores and diagonals, computed tile by tile under tile_bytes (0 = UNGAPPED_ALL_TILE_BYTES)   (uc_ungapped_all.hip)

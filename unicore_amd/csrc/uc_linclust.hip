@@ -119,12 +119,12 @@ inline dim3 lc_grid(uint64_t n) { return dim3((uint32_t)std::min<uint64_t>(std::
 
 // (centre, member) candidate pairs of the linear-time pre-step for the database resident on this engine's device, sorted by
 // (centre, member), unique
-std::vector<uint32_t> Engine::linclust_pairs_impl(uint64_t *install) {
+std::vector<uint32_t> Engine::linclust_pairs_impl(uint64_t *install, int m_override) {
     PressureScope ps(*this, 0);
     if (!have_db) fail(UC_ERR_ARGS, "no database loaded");
     UC_HIP(hipSetDevice(device));
     const uint32_t n = hdb.n;
-    const int m = p.kmer_per_seq;
+    const int m = m_override > 0 ? m_override : p.kmer_per_seq;
     std::vector<uint32_t> out;
     if (n == 0) return out;
     LcCfg cfg;
@@ -189,17 +189,17 @@ std::vector<uint32_t> Engine::linclust_pairs_impl(uint64_t *install) {
     return out;
 }
 
-std::vector<uint32_t> Engine::linclust_pairs() { return linclust_pairs_impl(nullptr); }
+std::vector<uint32_t> Engine::linclust_pairs(int m_override) { return linclust_pairs_impl(nullptr, m_override); }
 
 // the same pairs installed as this engine's hit lists (one rank: nothing goes through the host); returns their number
-uint64_t Engine::linclust_hits() {
+uint64_t Engine::linclust_hits(int m_override) {
     uint64_t np = 0;
     hit_cnt.assign(hdb.n, 0);
     hit_off.assign((size_t)hdb.n + 1, 0);
     n_hits = 0;
     alns_valid = false;
     clear_edges();
-    (void)linclust_pairs_impl(&np);
+    (void)linclust_pairs_impl(&np, m_override);
     return np;
 }
 
