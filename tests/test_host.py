@@ -353,3 +353,17 @@ def test_bench_dump_outputs_stays_in_budget_and_reads_cluster_dbs_back(tmp_path)
     out = str(tmp_path / "clu")
     assert U.lib().uc_write_cluster_db(out.encode(), len(assign), assign.ctypes.data) == 0
     assert np.array_equal(b.read_cluster_db(out), assign)
+
+
+def test_workflow_host_pieces_under_sanitizers(tmp_path):
+    """merge_round, sub_db, plan_devices and merge_stats of the cluster workflow are plain host code (uc_workflow_host.cpp links without the HIP
+    runtime): tests/workflow_host_check.cpp checks them in a program of its own, built with the address and undefined-behaviour sanitizers."""
+    csrc = os.path.join(ROOT, "unicore_amd", "csrc")
+    exe = str(tmp_path / "workflow_host_check")
+    cc = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-Wall", "-Wextra",
+                         "-I" + os.path.join(ROOT, "include"), "-I" + csrc, os.path.join(ROOT, "tests", "workflow_host_check.cpp"),
+                         os.path.join(csrc, "uc_workflow_host.cpp"), "-o", exe], capture_output=True, text=True)
+    assert cc.returncode == 0 and not cc.stderr, cc.stderr
+    run = subprocess.run([exe], capture_output=True, text=True)
+    assert run.returncode == 0 and not run.stderr, run.stdout + run.stderr
+    assert run.stdout.strip() == "workflow_host_check: ok"

@@ -1,5 +1,6 @@
 // uc_capi.cpp — extern "C" boundary (include/unicore_cluster.h).  No exception crosses it: every entry
-// point converts failures into the status classes of the header and records uc_last_error().
+// point converts failures into the status classes of the header and records uc_last_error().  What a uc_cluster
+// run does is not written here: the workflow lives in uc_workflow.cpp.
 #include <sys/stat.h>
 
 #include <algorithm>
@@ -7,20 +8,16 @@
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
-#include <future>
 #include <memory>
-#include <mutex>
-#include <thread>
 
 #include "uc_engine.h"
+#include "uc_files.h"
 #include "uc_multi.h"
 #include "uc_t5.h"
+#include "uc_workflow.h"
 
 using namespace uc;
 
-struct uc_engine {
-    std::unique_ptr<Engine> e;
-};
 struct uc_comm {
     Comm c;
 };
@@ -29,66 +26,6 @@ struct uc_t5 {
 };
 
 namespace {
-
-template <typename F>
-int guard(F &&f) {
-    try {
-        f();
-        return UC_OK;
-    } catch (const Error &e) {
-        set_last_error(e.what());
-        return e.code;
-    } catch (const std::bad_alloc &) {
-        set_last_error("out of host memory");
-        return UC_ERR_GENERIC;
-    } catch (const std::exception &e) {
-        set_last_error(e.what());
-        return UC_ERR_GENERIC;
-    }
-}
-
-Params params_from(const uc_opts *o, bool search = false) {
-    Params p;
-    if (search) { p.evalue = 10.0; p.max_seqs = 1000; p.want_tb = 1; }   // `foldseek search` defaults (EXT-UNVERIFIED)
-    if (o) {
-        if (o->struct_size != sizeof(uc_opts)) fail(UC_ERR_ARGS, "uc_opts.struct_size mismatch (%u != %zu)", o->struct_size, sizeof(uc_opts));
-        p.threads = o->threads > 0 ? o->threads : 1;
-        p.verbosity = o->verbosity;
-        p.num_gpus = o->num_gpus;
-        if (o->cluster_options) parse_cluster_options(o->cluster_options, p);
-    }
-    g_verbosity = p.verbosity;
-    finalize_params(p, o && o->data_dir ? o->data_dir : "");
-    return p;
-}
-
-void mkdir_p(const std::string &path) {
-    std::string cur;
-    for (size_t i = 0; i <= path.size(); i++) {
-        if (i == path.size() || path[i] == '/') {
-            if (!cur.empty() && cur != "/") {
-                struct stat st;
-                if (stat(cur.c_str(), &st) != 0 && mkdir(cur.c_str(), 0777) != 0) fail(UC_ERR_IO, "cannot create directory %s", cur.c_str());
-            }
-        }
-        if (i < path.size()) cur.push_back(path[i]);
-    }
-}
-
-// workflow observer (uc_set_round_hook): read once per round by rank 0's thread
-std::mutex g_hook_mu;
-uc_round_hook g_round_hook = nullptr;
-void *g_round_hook_user = nullptr;
-
-void call_round_hook(Engine &E, int round, const std::vector<uint32_t> &ids) {
-    uc_round_hook h; void *u;
-    { std::lock_guard<std::mutex> lk(g_hook_mu); h = g_round_hook; u = g_round_hook_user; }
-    if (!h) return;
-    uc_engine view;                       // a non-owning view of the round's engine for the duration of the call
-    view.e.reset(&E);
-    struct Release { uc_engine &v; ~Release() { (void)v.e.release(); } } rel{view};
-    h(u, round, E.hdb.n, ids.data(), E.p.kmer_thr, &view);
-}
 
 void require(const void *p, const char *what) {
     if (!p) fail(UC_ERR_ARGS, "%s must not be NULL", what);
@@ -167,10 +104,7 @@ const char *uc_version(void) {
 
 uint32_t uc_abi_version(void) { return UC_ABI_VERSION; }
 size_t uc_stats_size(void) { return sizeof(uc_stats); }
-void uc_set_round_hook(uc_round_hook hook, void *user) {
-    std::lock_guard<std::mutex> lk(g_hook_mu);
-    g_round_hook = hook; g_round_hook_user = user;
-}
+void uc_set_round_hook(uc_round_hook hook, void *user) { set_round_hook(hook, user); }
 
 int uc_option_arity(const char *flag) { return flag ? option_arity(flag) : -1; }
 
@@ -567,343 +501,12 @@ int uc_engine_sw_pass2(uc_engine *e, int table, int mode, int band, int raw, uin
     });
 }
 
-}  // extern "C"
-
-namespace {
-
-// counters add up over the ranks of a run; times are the slowest rank's (the ranks run side by side)
-void merge_stats(uc_stats &d, const uc_stats &s) {
-    d.n_index_entries += s.n_index_entries; d.n_sim_kmers += s.n_sim_kmers; d.n_kmer_hits += s.n_kmer_hits;
-    d.n_candidates += s.n_candidates; d.n_prefilter_hits += s.n_prefilter_hits; d.n_gapped_alignments += s.n_gapped_alignments;
-    d.n_start_alignments += s.n_start_alignments; d.n_pk_reruns += s.n_pk_reruns;
-    d.cells_fwd += s.cells_fwd; d.cells_rev += s.cells_rev; d.cells_start += s.cells_start; d.cells_tb += s.cells_tb;
-    d.sw_kernel_launches += s.sw_kernel_launches; d.sw_algorithmic_bytes += s.sw_algorithmic_bytes;
-    d.n_filtered_hits += s.n_filtered_hits; d.n_sw_runs += s.n_sw_runs; d.cells_run += s.cells_run; d.exchange_bytes += s.exchange_bytes;
-    for (int k = 0; k < UC_NSTAGE; k++) {
-        if (k != UC_ST_SETCOVER && k != UC_ST_OUTPUT && k != UC_ST_LOAD) d.algorithmic_bytes[k] += s.algorithmic_bytes[k];
-        d.stage_seconds[k] = std::max(d.stage_seconds[k], s.stage_seconds[k]);
-    }
-    d.sw_kernel_ms = std::max(d.sw_kernel_ms, s.sw_kernel_ms);
-    d.prefilter_kernel_ms = std::max(d.prefilter_kernel_ms, s.prefilter_kernel_ms);
-    d.exchange_seconds = std::max(d.exchange_seconds, s.exchange_seconds);
-    if (s.phase_seconds[3] > d.phase_seconds[3]) memcpy(d.exchange2_seconds, s.exchange2_seconds, sizeof d.exchange2_seconds);   // the split of the slowest rank's phase 3
-    for (int k = 0; k < UC_NPHASE; k++) d.phase_seconds[k] = std::max(d.phase_seconds[k], s.phase_seconds[k]);
-}
-
-// the sub-database of the current representatives (createsubdb)
-HostDb sub_db(const HostDb &full, const std::vector<uint32_t> &cur) {
-    HostDb sub;
-    sub.n = (uint32_t)cur.size();
-    sub.off.resize((size_t)sub.n + 1);
-    uint64_t tot = 0;
-    for (uint32_t i = 0; i < sub.n; i++) { sub.off[i] = tot; tot += full.len(cur[i]); }
-    sub.off[sub.n] = tot;
-    sub.s3.resize(tot); sub.sa.resize(tot); sub.keys.resize(sub.n);
-    for (uint32_t i = 0; i < sub.n; i++) {
-        memcpy(sub.s3.data() + sub.off[i], full.s3.data() + full.off[cur[i]], full.len(cur[i]));
-        memcpy(sub.sa.data() + sub.off[i], full.sa.data() + full.off[cur[i]], full.len(cur[i]));
-        sub.keys[i] = full.keys[cur[i]];
-    }
-    return sub;
-}
-
-}  // namespace
-
-extern "C" {
-
 // ---- the three calls of /root/reference/src/modules/cluster.rs:45-76 ----------------------------
 
 int uc_cluster(const char *db, const char *out_cluster_db, const char *tmp, const uc_opts *o, uc_stats *stats_out) {
     return guard([&] {
         require(db, "db"); require(out_cluster_db, "out_cluster_db");
-        const bool stamp = getenv("UC_TIMING") != nullptr;
-        auto mark = [&](const char *what) { if (stamp) fprintf(stderr, "unicore-cluster[timing]: t+%7.1f ms  %s\n", 1e3 * g_library_loaded.seconds(), what); };
-        mark("uc_cluster entered");
-        Params p = params_from(o);
-        mark("options + matrices");
-        if (tmp && *tmp) mkdir_p(tmp);   // callee owns <tmp>; nothing is spilled there yet
-        if (p.mat3di_synthetic)
-            logf(1, "Warning: clustering with the SYNTHETIC 3Di matrix %s (UC_ALLOW_SYNTHETIC=1): results are not Foldseek's\n", p.mat3di_path.c_str());
-
-        // The HIP runtime and the device context take 0.15-0.3 s to come up in a fresh process (tools/cold_stamps.sh): they are initialised on
-        // a helper thread WHILE this thread reads and encodes the database (a one-shot `foldseek cluster` process pays for both every time).
-        const int want_dev = o && o->device >= 0 ? o->device : 0;
-        std::future<int> warm = std::async(std::launch::async, [want_dev]() -> int {
-            int nd = 0;
-            if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) return 0;
-            if (hipSetDevice(want_dev < nd ? want_dev : 0) == hipSuccess) (void)hipFree(nullptr);      // forces the primary context into existence
-            return nd;
-        });
-        Timer tl;
-        logf(3, "unicore-cluster: reading %s\n", db);
-        HostDb full;
-        read_seq_db(db, full, false);
-        const double t_load = tl.seconds();
-        mark("database read + encoded");
-        // ---- devices (one engine + one host thread per GPU, hit lists all-gathered with RCCL)
-        const int ndev = warm.get();
-        if (ndev <= 0) fail(UC_ERR_DEVICE, "no HIP device available; this engine has no CPU fallback");
-        mark("HIP runtime + device context ready (initialised beside the database read)");
-        int W = p.num_gpus == 0 ? ndev : p.num_gpus;
-        std::vector<int> devices;
-        bool virtual_gpus = false;
-        if (W == 1) {
-            int d = o ? o->device : -1;
-            if (d < 0) UC_HIP(hipGetDevice(&d));
-            devices.push_back(d);
-        } else {
-            if (W > ndev) {
-                // several ranks per physical GPU: only to exercise the N > 1 path on a single-GPU box (tests); RCCL refuses
-                // two ranks on one device, so these ranks exchange with plain device copies
-                const char *v = getenv("UC_VIRTUAL_GPUS");
-                if (!v || strcmp(v, "1") != 0) fail(UC_ERR_DEVICE, "%d GPUs requested but only %d visible", W, ndev);
-                virtual_gpus = true;
-            }
-            for (int r = 0; r < W; r++) devices.push_back(r % ndev);
-        }
-        int gQ = 1, gT = 1;
-        grid_shape(W, p.target_shards, &gQ, &gT);
-
-
-        const uint32_t n = full.n;
-        if (n == 0) {   // an empty, well-formed database: an empty cluster DB, whatever the workflow
-            write_cluster_db(out_cluster_db, full.keys, nullptr, 0);
-            logf(3, "unicore-cluster: empty database -> %s\n", out_cluster_db);
-            if (stats_out) { *stats_out = uc_stats(); stats_out->n_gpus = (uint32_t)W; stats_out->target_shards = (uint32_t)gT; stats_out->stage_seconds[UC_ST_LOAD] = t_load; }
-            return;
-        }
-        const int pre = p.linclust ? 1 : 0;     // E8a: one linear-time pre-clustering round in front of the cascade rounds
-        // the kernels' code objects are uploaded on a helper thread beside engine construction, database upload and prefilter (uc_sw.hip:preload_modules);
-        // (The future's destructor joins the thread on every way out of this function.)
-        std::future<void> preload;
-        if (W == 1) {
-            const int d0 = devices[0];
-            const bool lc = pre != 0, st = stamp;
-            preload = std::async(std::launch::async, [d0, lc, st]() {
-                preload_modules(d0, lc);
-                if (st) fprintf(stderr, "unicore-cluster[timing]: t+%7.1f ms  (helper thread) code objects of the prefilter / alignment / SW modules loaded\n", 1e3 * g_library_loaded.seconds());
-            });
-        }
-        logf(3, "unicore-cluster: %u sequences, %llu residues, %d GPU(s)%s [%d query group(s) x %d target shard(s)], %s%d clustering step(s)\n", n,
-             (unsigned long long)full.residues(), W, virtual_gpus ? " (virtual: several ranks per device)" : "", gQ, gT,
-             pre ? "linear-time pre-step + " : "", p.cluster_steps);
-
-        // ---- state shared by the rank threads (host memory; rank 0 owns the workflow, the others follow its rounds)
-        std::vector<uint32_t> assign(n), cur(n), posmap(n);
-        for (uint32_t i = 0; i < n; i++) { assign[i] = i; cur[i] = i; }
-        HostDb round_db;                       // sub-database of the round (rounds > 0)
-        std::vector<uint32_t> pre_pairs;       // candidate pairs of the pre-step
-        int round_kmer_thr = p.kmer_thr;
-        LocalGroup grp(W);
-        if (virtual_gpus && getenv("UC_VIRTUAL_SERIAL")) grp.serialize = true;   // emulation: one rank's compute phase at a time on the shared GPU
-        std::vector<std::unique_ptr<Comm>> comms;
-        for (int r = 0; r < W; r++) {
-            comms.emplace_back(new Comm);
-            comms.back()->rank = r; comms.back()->world = W; comms.back()->grp = W > 1 ? &grp : nullptr;
-        }
-        std::vector<uc_stats> rank_stats((size_t)W);
-        uint64_t n_clusters = 0;
-        uint32_t nccl_ranks = 0;
-
-        auto rank_main = [&](int r) {
-            Engine E(p, devices[(size_t)r]);
-            if (r == 0) mark("engine constructed (streams, events, matrices on the device)");
-            Comm &C = *comms[(size_t)r];
-            // test hook: UC_FAIL_RANK="<rank>:<stage>" makes that rank throw (stage 0 = right after its engine exists, 1 = between
-            // its prefilter and the exchange) — the failure paths below must turn that into an error code, never into a hang
-            int fail_rank = -1, fail_stage = -1;
-            if (const char *fr = getenv("UC_FAIL_RANK")) sscanf(fr, "%d:%d", &fail_rank, &fail_stage);
-            if (fail_rank == r && fail_stage == 0) fail(UC_ERR_DEVICE, "injected failure of rank %d (UC_FAIL_RANK)", r);
-            if (W > 1) {
-                // every engine exists (a constructor that threw has failed the group: this barrier then throws on the others)
-                // BEFORE any rank enters RCCL; rank 0 then creates all communicators in one call — a collective init per rank
-                // would leave the survivors of a failed peer blocked inside ncclCommInitRank for good
-                grp.barrier();
-                if (r == 0 && !virtual_gpus) {
-                    std::vector<Comm *> cs;
-                    for (auto &c : comms) cs.push_back(c.get());
-                    comm_init_all(cs, devices);
-                    int cnt = 0, rk = 0, dv = 0;
-                    comm_info(C, &cnt, &rk, &dv);
-                    nccl_ranks = (uint32_t)cnt;
-                    logf(3, "unicore-cluster: RCCL communicator over %d ranks (ncclCommCount)\n", cnt);
-                }
-                grp.barrier();
-            }
-            const bool timing = getenv("UC_TIMING") != nullptr;
-            Timer tph;
-            auto phase = [&](const char *what, int rr) {
-                if (timing && r == 0) fprintf(stderr, "unicore-cluster[timing]: t+%7.1f ms  round %d %-14s %.1f ms\n", 1e3 * g_library_loaded.seconds(), rr, what, 1e3 * tph.seconds());
-                tph = Timer();
-            };
-            for (int rr = 0; rr < p.cluster_steps + pre; rr++) {
-                const int rd = rr - pre;             // cascade round index (-1 = the pre-step)
-                phase("(between)", rr);
-                if (W == 1 && rr == 1) full = std::move(E.hdb);      // a single rank borrows the databases instead of copying them
-                const bool dev_sub = W == 1 && rr > 0;                // ... and lays the representatives' sub-database out on the device
-                if (r == 0) {
-                    if (rr > 0 && !dev_sub) round_db = sub_db(full, cur);
-                    round_kmer_thr = p.kmer_thr;
-                    if (rd >= 0 && p.cluster_steps > 1 && !p.kmer_thr_explicit)   // sensitivity rises linearly from 1 to the target (spec UC-1 E8)
-                        round_kmer_thr = kmer_thr_for(p, 1.0 + (p.sensitivity - 1.0) * rd / (p.cluster_steps - 1));
-                }
-                C.barrier(E);
-                phase("sub_db", rr);
-                if (!dev_sub) {
-                    if (W == 1) E.hdb = std::move(rr == 0 ? full : round_db);
-                    else E.hdb = rr == 0 ? full : round_db;
-                }
-                phase("hdb copy", rr);
-                E.p.kmer_thr = round_kmer_thr;
-                if (dev_sub) E.upload_sub_db(cur, full.off);
-                else E.upload_db(/*keep_raw=*/W == 1 && p.cluster_steps + pre > 1);
-                phase("upload", rr);
-                const uint32_t m = E.hdb.n;
-                if (rd < 0 && W == 1) {   // E8a on one rank: the candidate pairs become the hit lists without leaving the device
-                    const uint64_t np = E.linclust_hits();
-                    phase("linclust_pairs", rr);
-                    E.stats.n_prefilter_hits += np;
-                    logf(3, "unicore-cluster: pre-step: %u sequences, %llu candidate pairs (%d k-mers per sequence)\n", m, (unsigned long long)np, p.kmer_per_seq);
-                } else if (rd < 0) {   // E8a: candidate pairs (centre, member) from shared minimum-hash k-mers, the centre is the query
-                    if (r == 0) pre_pairs = E.linclust_pairs();
-                    phase("linclust_pairs", rr);
-                    C.barrier(E);
-                    // a rank aligns the pairs of the centres it owns (centre mod world): whole queries stay together
-                    std::vector<uint32_t> cnt(m, 0);
-                    std::vector<uc_hit> hl;
-                    hl.reserve(pre_pairs.size() / 2 / (size_t)W + 16);
-                    for (size_t k = 0; k < pre_pairs.size() / 2; k++) {
-                        const uint32_t c = pre_pairs[2 * k];
-                        if ((int)(c % (uint32_t)W) != r) continue;
-                        cnt[c]++;
-                        uc_hit h; h.target = pre_pairs[2 * k + 1]; h.score = 0; h.diag = 0;
-                        hl.push_back(h);
-                    }
-                    E.set_hits(cnt.data(), hl.data(), /*check_max_seqs=*/false);
-                    E.stats.n_prefilter_hits += hl.size();
-                    if (r == 0)
-                        logf(3, "unicore-cluster: pre-step: %u sequences, %zu candidate pairs (%d k-mers per sequence)\n", m, pre_pairs.size() / 2, p.kmer_per_seq);
-                } else {
-                    {
-                        Turn turn(C, &E);
-                        Timer tp;
-                        prefilter_cell(E, W, p.target_shards, r);
-                        E.stats.phase_seconds[0] += tp.seconds();
-                    }
-                    if (fail_rank == r && fail_stage == 1) fail(UC_ERR_DEVICE, "injected failure of rank %d (UC_FAIL_RANK)", r);
-                    if (W > 1) exchange_hits(E, C);
-                    if (r == 0)
-                        logf(3, "unicore-cluster: step %d: %u sequences, prefilter kept %llu pairs%s (k-score %d, max-seqs %d)\n", rd + 1, m,
-                             (unsigned long long)E.n_hits, W > 1 ? " on rank 0" : "", E.p.kmer_thr, p.max_seqs);
-                }
-                phase("hits", rr);
-                {
-                    Turn turn(C, &E);
-                    Timer ta;
-                    E.align(0, m);
-                    E.stats.phase_seconds[5] += ta.seconds();
-                }
-                phase("align", rr);
-                if (r == 0) call_round_hook(E, rd, cur);
-                Timer te;
-                uint64_t n_acc = 0;                  // accepted pairs of the round (all ranks)
-                const uint32_t *dev_all = nullptr;   // rank 0: every rank's edges in one device buffer (gathered device to device)
-                if (W > 1) { n_acc = C.gather_edges_dev(E, &dev_all); E.stats.exchange_seconds += te.seconds(); }
-                else n_acc = E.edges_on_host ? E.edges.size() / 2 : E.n_edges_dev;
-                if (r == 0) {
-                    Timer tc;
-                    std::vector<uint32_t> sa(m);
-                    // the rule is p.cluster_mode (0 = set cover, 2 = greedy incremental on the round's lengths) in all three branches
-                    if (W > 1 && n_acc < (1ull << 31)) E.cluster_graph_dev_edges(m, dev_all, n_acc, sa.data());
-                    else if (W > 1) {   // beyond the 32-bit positions of the device graph build: the all-host variant
-                        std::vector<uint32_t> all(2 * n_acc);
-                        UC_HIP(hipMemcpy(all.data(), dev_all, 2 * n_acc * 4, hipMemcpyDeviceToHost));
-                        cluster_graph(m, all.data(), n_acc, E.h_len.data(), E.p.cluster_mode, sa.data());
-                    }
-                    else E.set_cover_own_edges(m, sa.data());      // one rank: graph straight from the device-resident edge list
-                    // mergeclusters: the representative of a sequence is the representative of its representative
-                    for (uint32_t i = 0; i < cur.size(); i++) posmap[cur[i]] = i;
-                    for (uint32_t x = 0; x < n; x++) assign[x] = cur[sa[posmap[assign[x]]]];
-                    std::vector<uint32_t> next;
-                    for (uint32_t i = 0; i < cur.size(); i++) if (sa[i] == i) next.push_back(cur[i]);
-                    E.stats.algorithmic_bytes[UC_ST_SETCOVER] += 8ull * n_acc + 4ull * m;
-                    E.stats.stage_seconds[UC_ST_SETCOVER] += tc.seconds();
-                    if (W > 1) E.stats.phase_seconds[7] += tc.seconds();
-                    logf(3, "unicore-cluster: step %d: %llu accepted pairs, %zu representatives\n", rd + 1, (unsigned long long)n_acc, next.size());
-                    cur.swap(next);
-                    E.stats.n_edges = n_acc;
-                }
-                phase("cover+merge", rr);
-            }
-            if (r == 0 && p.reassign) {
-                // rule UC-1/R on rank 0's engine alone (the others wait at the barrier below: the rejected sets are small).  The full database becomes
-                // the engine's again: one rank lays it out from the raw copy the rounds kept on the device (or still holds it after a plain step)
-                phase("(between)", p.cluster_steps + pre);
-                Timer tr;
-                const bool multi_round = p.cluster_steps + pre > 1;
-                E.p.kmer_thr = p.kmer_thr;                    // the final sensitivity, not a cascade round's
-                if (W == 1 && multi_round) {
-                    std::vector<uint32_t> all(n);
-                    for (uint32_t i = 0; i < n; i++) all[i] = i;
-                    E.upload_sub_db(all, full.off);
-                } else if (W > 1) {
-                    E.hdb = full;
-                    E.upload_db(/*keep_raw=*/true);
-                }
-                std::vector<uint32_t> out(n);
-                uint64_t rc[4] = {0, 0, 0, 0};
-                const uint64_t before = cur.size();
-                E.reassign(assign.data(), out.data(), nullptr, rc);
-                assign.swap(out);
-                cur.clear();
-                for (uint32_t x = 0; x < n; x++) if (assign[x] == x) cur.push_back(x);
-                logf(3, "unicore-cluster: reassign: %llu members verified, %llu rejected, %llu re-search pairs accepted, %llu -> %zu clusters (%.1f ms)\n",
-                     (unsigned long long)rc[0], (unsigned long long)rc[1], (unsigned long long)rc[2], (unsigned long long)before, cur.size(), 1e3 * tr.seconds());
-                phase("reassign", p.cluster_steps + pre);
-            }
-            C.barrier(E);
-            if (W == 1 && p.cluster_steps + pre == 1) full = std::move(E.hdb);
-            if (r == 0) n_clusters = cur.size();
-            rank_stats[(size_t)r] = E.stats;
-        };
-
-        if (W == 1) rank_main(0);
-        else {
-            std::vector<std::string> err((size_t)W);
-            std::vector<int> code((size_t)W, 0);
-            std::vector<std::thread> th;
-            // a rank on its way out fails the group (peers leave their next barrier with an error) and aborts every RCCL
-            // communicator (peers blocked INSIDE a collective return from it)
-            auto bail = [&] { grp.fail_all(); std::vector<Comm *> cs; for (auto &c : comms) cs.push_back(c.get()); abort_all(cs); };
-            for (int r = 0; r < W; r++)
-                th.emplace_back([&, r] {
-                    try { rank_main(r); }
-                    catch (const Error &e) { code[(size_t)r] = e.code; err[(size_t)r] = e.what(); bail(); }
-                    catch (const std::exception &e) { code[(size_t)r] = UC_ERR_GENERIC; err[(size_t)r] = e.what(); bail(); }
-                });
-            for (auto &t : th) t.join();
-            // report the rank that failed first-hand, not the ones that were released from a barrier because of it
-            int bad = -1;
-            for (int r = 0; r < W; r++)
-                if (code[(size_t)r] && (bad < 0 || err[(size_t)bad].find("another GPU rank") != std::string::npos)) bad = r;
-            if (bad >= 0) fail(code[(size_t)bad], "GPU rank %d: %s", bad, err[(size_t)bad].c_str());
-        }
-
-        uc_stats st = rank_stats[0];
-        for (int r = 1; r < W; r++) merge_stats(st, rank_stats[(size_t)r]);
-        st.stage_seconds[UC_ST_LOAD] += t_load;
-        st.n_clusters = n_clusters;
-        st.n_seqs = n;
-        st.n_residues = full.residues();
-        st.n_gpus = (uint32_t)W;
-        st.target_shards = (uint32_t)gT;
-        st.nccl_ranks = nccl_ranks;
-        Timer to;
-        write_cluster_db(out_cluster_db, full.keys, assign.data(), n);
-        st.stage_seconds[UC_ST_OUTPUT] += to.seconds();
-        mark("cluster DB written");
-        logf(3, "unicore-cluster: %llu clusters -> %s\n", (unsigned long long)n_clusters, out_cluster_db);
-        if (stats_out) *stats_out = st;
+        cluster_workflow(db, out_cluster_db, tmp, o, stats_out);      // uc_workflow.cpp
     });
 }
 
@@ -951,7 +554,7 @@ int uc_search(const char *query_db, const char *target_db, const char *out_aln_d
         require(query_db, "query_db"); require(target_db, "target_db"); require(out_aln_db, "out_aln_db");
         Params p = params_from(o, true);
         p.want_tb = 1;
-        if (tmp && *tmp) mkdir_p(tmp);
+        if (tmp && *tmp) make_dirs(tmp);
         Engine E(p, o ? o->device : -1);
         E.emit_bt = p.want_bt != 0;
         Timer tl;
@@ -1050,25 +653,13 @@ int uc_createdb(const char *const *fasta_paths, int n_fasta, const char *out_db,
         if (n_fasta < 1) fail(UC_ERR_ARGS, "createdb: no input files");
         std::vector<std::string> fp;
         for (int i = 0; i < n_fasta; i++) { require(fasta_paths[i], "fasta path"); fp.push_back(fasta_paths[i]); }
-        // devices: the convention of uc_cluster (uc_opts.num_gpus: 0 = all visible, 1 = `device`, N = devices 0..N-1; more than are visible only with
-        // UC_VIRTUAL_GPUS=1: several replicas per device, the single-GPU box's test of this path).  The encoder shards by sequence, "replicas only".
+        // devices: the convention of uc_cluster (plan_devices; more than are visible only with UC_VIRTUAL_GPUS=1: several replicas per device, the
+        // single-GPU box's test of this path).  The encoder shards by sequence, "replicas only".
         int ndev = 0;
         if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) fail(UC_ERR_DEVICE, "no HIP device available; the ProstT5 encoder has no CPU fallback");
         const int want = o ? o->num_gpus : 1;
         if (want < 0 || want > 64) fail(UC_ERR_ARGS, "createdb: num_gpus must be in [0,64] (0 = all visible)");
-        const int W = want == 0 ? ndev : want;
-        std::vector<int> devices;
-        if (W == 1) {
-            int d = o ? o->device : -1;
-            if (d < 0) UC_HIP(hipGetDevice(&d));
-            devices.push_back(d);
-        } else {
-            if (W > ndev) {
-                const char *v = getenv("UC_VIRTUAL_GPUS");
-                if (!v || strcmp(v, "1") != 0) fail(UC_ERR_DEVICE, "%d GPUs requested but only %d visible", W, ndev);
-            }
-            for (int r = 0; r < W; r++) devices.push_back(r % ndev);
-        }
+        const std::vector<int> devices = plan_visible_devices(want, o ? o->device : -1, ndev).devices;
         T5Stats st;
         std::vector<T5Stats> per;
         t5_createdb(fp, out_db, model, devices, o ? o->verbosity : 3, &st, &per);

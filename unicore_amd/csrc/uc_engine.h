@@ -9,6 +9,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <utility>
@@ -383,3 +384,8 @@ const char *last_error_cstr();
 
 void preload_modules(int device, bool linclust);      // uc_sw.hip: forces the code objects of the cluster path onto the device (cold start)
 }  // namespace uc
+
+// the engine handle of the C ABI (uc_capi.cpp; the workflow hands its round hook a non-owning one)
+struct uc_engine {
+    std::unique_ptr<uc::Engine> e;
+};

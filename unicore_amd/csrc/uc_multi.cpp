@@ -85,6 +85,14 @@ void abort_all(const std::vector<Comm *> &comms) {
     for (Comm *c : comms) if (c) c->abort();
 }
 
+// test hook: UC_FAIL_RANK="<rank>:<stage>" makes that rank throw: stage 0 = right after its engine exists, 1 = between its prefilter and the
+// exchange, 2 = inside the grouped point-to-point exchange, between ncclGroupStart and ncclGroupEnd
+bool inject_failure(int rank, int stage) {
+    int fr = -1, fs = -1;
+    if (const char *e = getenv("UC_FAIL_RANK")) sscanf(e, "%d:%d", &fr, &fs);
+    return fr == rank && fs == stage;
+}
+
 namespace {
 // ncclGroupStart ... ncclGroupEnd as a scope: an exception between the two (a failed ncclSend, an injected failure) must not leave the
 // calling thread's group open — the abort that follows would run INSIDE that group
@@ -94,13 +102,6 @@ struct GroupScope {
     void end() { open = false; UC_NCCL(ncclGroupEnd()); }
     ~GroupScope() { if (open) (void)ncclGroupEnd(); }
 };
-
-// test hook: UC_FAIL_RANK="<rank>:<stage>"; stage 2 = inside the grouped point-to-point exchange, between ncclGroupStart and ncclGroupEnd
-bool inject_failure(int rank, int stage) {
-    int fr = -1, fs = -1;
-    if (const char *e = getenv("UC_FAIL_RANK")) sscanf(e, "%d:%d", &fr, &fs);
-    return fr == rank && fs == stage;
-}
 
 // RCCL enqueue: the handle is read once; an abort() that lands between the read and the call makes the call fail (or return early) — both
 // surface as an error of this rank, which is what the caller wants to hear
@@ -550,51 +551,56 @@ uint64_t exchange_hits(Engine &E, Comm &C) {
     return kept;
 }
 
+void prefilter_turn(Engine &E, Comm &C, int target_shards) {
+    Turn turn(C, &E);
+    Timer tp;
+    prefilter_cell(E, C.world, target_shards, C.rank);
+    E.stats.phase_seconds[0] += tp.seconds();
+}
+
+void align_turn(Engine &E, Comm &C, uint32_t n) {
+    Turn turn(C, &E);
+    Timer ta;
+    E.align(0, n);
+    E.stats.phase_seconds[5] += ta.seconds();
+}
+
+uint64_t round_graph(Engine &E, Comm &C, uint32_t n, uint32_t *assign) {
+    const bool solo = C.world == 1 && !C.uses_rccl;      // one rank: the graph is built straight from the device-resident edge list
+    uint64_t n_all = E.edges_on_host ? E.edges.size() / 2 : E.n_edges_dev;
+    const uint32_t *dev_all = nullptr;                   // rank 0: every rank's edges in one device buffer (gathered device to device)
+    if (!solo) {
+        Timer te;
+        n_all = C.gather_edges_dev(E, &dev_all);
+        E.stats.exchange_seconds += C.world > 1 ? te.seconds() : 0.0;
+    }
+    if (C.rank != 0) return n_all;
+    if (!assign && n) fail(UC_ERR_ARGS, "rank 0 needs an assignment buffer for the graph of the round");
+    Timer tc;
+    // the rule is E.p.cluster_mode (0 = set cover, 2 = greedy incremental on the round's lengths) in all three branches
+    if (solo) E.set_cover_own_edges(n, assign);
+    else if (n_all < (1ull << 31)) E.cluster_graph_dev_edges(n, dev_all, n_all, assign);      // the graph is built from the buffer the edges landed in
+    else {   // beyond the 32-bit positions of the device graph build: the all-host variant
+        std::vector<uint32_t> all(2 * n_all);
+        UC_HIP(hipMemcpy(all.data(), dev_all, 2 * n_all * 4, hipMemcpyDeviceToHost));
+        cluster_graph(n, all.data(), n_all, E.h_len.data(), E.p.cluster_mode, assign);
+    }
+    E.stats.algorithmic_bytes[UC_ST_SETCOVER] += 8ull * n_all + 4ull * n;
+    E.stats.stage_seconds[UC_ST_SETCOVER] += tc.seconds();
+    if (!solo) E.stats.phase_seconds[7] += tc.seconds();
+    return n_all;
+}
+
 uint64_t cluster_step(Engine &E, Comm &C, int target_shards, uint32_t *assign) {
     if (!E.have_db) fail(UC_ERR_ARGS, "no database loaded");
     UC_HIP(hipSetDevice(E.device));
     const uint32_t n = E.hdb.n;
-    {
-        Turn turn(C, &E);
-        Timer tp;
-        prefilter_cell(E, C.world, target_shards, C.rank);
-        E.stats.phase_seconds[0] += tp.seconds();
-    }
+    prefilter_turn(E, C, target_shards);
     if (C.world > 1 || C.uses_rccl) (void)exchange_hits(E, C);
     const uint64_t aln_before = E.stats.n_gapped_alignments;
-    {
-        Turn turn(C, &E);
-        Timer ta;
-        E.align(0, n);
-        E.stats.phase_seconds[5] += ta.seconds();
-    }
+    align_turn(E, C, n);
     const uint64_t n_aln = E.stats.n_gapped_alignments - aln_before;   // pairs this rank aligned: its installed lists minus what an optional length gate (UC-1/L) ruled out
-    if (C.world == 1 && !C.uses_rccl) {   // one rank: the graph is built straight from the device-resident edge list
-        if (!assign && n) fail(UC_ERR_ARGS, "cluster_step: rank 0 needs an assignment buffer");
-        Timer tc;
-        const uint64_t ne = E.edges_on_host ? E.edges.size() / 2 : E.n_edges_dev;
-        E.set_cover_own_edges(n, assign);
-        E.stats.algorithmic_bytes[UC_ST_SETCOVER] += 8ull * ne + 4ull * n;
-        E.stats.stage_seconds[UC_ST_SETCOVER] += tc.seconds();
-        return n_aln;
-    }
-    Timer te;
-    const uint32_t *dev_all = nullptr;
-    const uint64_t n_all = C.gather_edges_dev(E, &dev_all);
-    E.stats.exchange_seconds += C.world > 1 ? te.seconds() : 0.0;
-    if (C.rank == 0) {
-        if (!assign && n) fail(UC_ERR_ARGS, "cluster_step: rank 0 needs an assignment buffer");
-        Timer tc;
-        if (n_all < (1ull << 31)) E.cluster_graph_dev_edges(n, dev_all, n_all, assign);     // the graph is built from the buffer the edges landed in; the rule is E.p.cluster_mode
-        else {   // beyond the 32-bit positions of the device graph build: the all-host variant
-            std::vector<uint32_t> all(2 * n_all);
-            UC_HIP(hipMemcpy(all.data(), dev_all, 2 * n_all * 4, hipMemcpyDeviceToHost));
-            cluster_graph(n, all.data(), n_all, E.h_len.data(), E.p.cluster_mode, assign);
-        }
-        E.stats.algorithmic_bytes[UC_ST_SETCOVER] += 8ull * n_all + 4ull * n;
-        E.stats.stage_seconds[UC_ST_SETCOVER] += tc.seconds();
-        E.stats.phase_seconds[7] += tc.seconds();
-    }
+    (void)round_graph(E, C, n, assign);
     return n_aln;
 }
 

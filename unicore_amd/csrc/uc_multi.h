@@ -1,5 +1,5 @@
 // uc_multi.h — the multi-GPU layout of the cluster path inside the library: one Engine per GPU, one host
-// thread per engine (uc_cluster, num_gpus > 1) or one process per engine (uc_comm_* of the C ABI, bench.py under
+// thread per engine (uc_cluster, num_gpus > 1: the workflow that drives them is uc_workflow.cpp) or one process per engine (uc_comm_* of the C ABI, bench.py under
 // torch.distributed.run), the per-shard hit lists all-gathered device to device with RCCL over xGMI.
 //
 //   rank r : index target shard r % T -> match query group r / T against it (E1-E4)       [Q x T = world]
@@ -113,9 +113,20 @@ void prefilter_cell(Engine &E, int world, int target_shards, int rank);
 
 // all-gather + merge + ownership filter of the engine's hit lists; returns the pairs this rank now owns
 uint64_t exchange_hits(Engine &E, Comm &C);
+// The three stages of a pass that cluster_step and the workflow's rounds (uc_workflow.cpp) share; whether the exchange runs between the first
+// two is the caller's decision.
+void prefilter_turn(Engine &E, Comm &C, int target_shards);      // prefilter_cell of this rank's cell under a Turn, charged to phase 0
+void align_turn(Engine &E, Comm &C, uint32_t n);                 // E5/E6 of [0, n) under a Turn, charged to phase 5
+// accepted edges of the pass -> assignment (n entries, written on rank 0 only; rank 0 without a buffer is UC_ERR_ARGS).  One rank without RCCL
+// builds the graph from its own device-resident edge list; otherwise the edges are gathered on rank 0 (exchange_seconds when world > 1), which
+// builds it on the device below 2^31 edges and on the host from there on.  Charges UC_ST_SETCOVER (bytes and seconds) and, on the gathered
+// path, phase 7.  Returns the accepted pairs of all ranks, on every rank.
+uint64_t round_graph(Engine &E, Comm &C, uint32_t n, uint32_t *assign);
 // one pass of the sharded path on this rank (prefilter of the rank's cell -> exchange -> E5/E6 -> edges to rank 0 -> set
 // cover on rank 0).  assign (n entries) is written on rank 0 only.  Returns the gapped alignments of this rank.
 uint64_t cluster_step(Engine &E, Comm &C, int target_shards, uint32_t *assign);
+// test hook UC_FAIL_RANK="<rank>:<stage>": true on the rank and at the stage the variable names (the caller throws)
+bool inject_failure(int rank, int stage);
 
 // RCCL plumbing for the C ABI
 void comm_unique_id(uint8_t id[128]);

@@ -287,4 +287,19 @@ int32_t min_score_for(const Params &p, int lq, uint64_t db_residues) {
     return s;
 }
 
+Params params_from(const uc_opts *o, bool search) {
+    Params p;
+    if (search) { p.evalue = 10.0; p.max_seqs = 1000; p.want_tb = 1; }   // `foldseek search` defaults (EXT-UNVERIFIED)
+    if (o) {
+        if (o->struct_size != sizeof(uc_opts)) fail(UC_ERR_ARGS, "uc_opts.struct_size mismatch (%u != %zu)", o->struct_size, sizeof(uc_opts));
+        p.threads = o->threads > 0 ? o->threads : 1;
+        p.verbosity = o->verbosity;
+        p.num_gpus = o->num_gpus;
+        if (o->cluster_options) parse_cluster_options(o->cluster_options, p);
+    }
+    g_verbosity = p.verbosity;
+    finalize_params(p, o && o->data_dir ? o->data_dir : "");
+    return p;
+}
+
 }  // namespace uc

@@ -7,6 +7,8 @@
 #include <string>
 #include <vector>
 
+#include "unicore_cluster.h"
+
 namespace uc {
 
 constexpr int A = 21;    // alphabet incl. X
@@ -80,6 +82,8 @@ void parse_cluster_options(const std::string &opts, Params &p);
 int option_arity(const std::string &flag);
 // resolve data files + derived values (pattern offsets, kmer_thr from sensitivity); loads matrices
 void finalize_params(Params &p, const std::string &data_dir);
+// the uc_opts of an entry point (may be null) -> finalized parameters; search: the defaults of `foldseek search`.  Sets g_verbosity.
+Params params_from(const uc_opts *o, bool search = false);
 std::string default_data_dir();
 // smallest integer score S with K * lq * db_residues * exp(-lambda*S) <= evalue
 // sensitivity -> k-mer threshold (the rule of finalize_params)
