@@ -92,6 +92,8 @@ def lib():
     L.uco_traceback.argtypes = [C.POINTER(Db), C.c_uint32, C.c_uint32, C.POINTER(Params), C.c_int, C.c_int, C.c_int, C.c_int,
                                 C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.uco_traceback.restype = None
+    L.uco_traceback_lean.argtypes = L.uco_traceback.argtypes + [C.POINTER(C.c_int32)]
+    L.uco_traceback_lean.restype = C.c_int
     L.uco_align_pair.argtypes = [C.POINTER(Db), C.c_uint32, C.c_uint32, C.POINTER(Params), C.c_int32, C.POINTER(Aln)]
     L.uco_setcover.argtypes = [C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p]
     L.uco_cluster.argtypes = [C.POINTER(Db), C.POINTER(Params), C.c_int, C.c_void_p, C.POINTER(Counts), C.c_void_p, C.c_void_p, C.c_void_p]
@@ -427,6 +429,16 @@ def traceback(odb, p, q, t, qs, qe, ts, te):
     ln, idn, gp = C.c_int32(), C.c_int32(), C.c_int32()
     lib().uco_traceback(C.byref(odb.db), int(q), int(t), C.byref(p), int(qs), int(qe), int(ts), int(te), C.byref(ln), C.byref(idn), C.byref(gp))
     return ln.value, idn.value, gp.value
+
+
+def traceback_lean(odb, p, q, t, qs, qe, ts, te):
+    """traceback() from one byte per cell, for boxes of any allowed size: (alignment length, identities, gap opens, tie mark)"""
+    ln, idn, gp, tie = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
+    rc = lib().uco_traceback_lean(C.byref(odb.db), int(q), int(t), C.byref(p), int(qs), int(qe), int(ts), int(te),
+                                  C.byref(ln), C.byref(idn), C.byref(gp), C.byref(tie))
+    if rc != 0:
+        raise MemoryError("uco_traceback_lean: box %d x %d" % (qe - qs + 1, te - ts + 1))
+    return ln.value, idn.value, gp.value, tie.value
 
 
 def min_score(odb, p, q):

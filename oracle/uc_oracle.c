@@ -530,6 +530,71 @@ void uco_traceback(const uco_db *db, uint32_t q, uint32_t t, const uco_params *p
     traceback(db, q, t, p, qs, qe, ts, te, aln_len, idents, gap_opens);
 }
 
+/* traceback() for boxes its three int32 matrices cannot hold (12 bytes per cell: 12.9 GB at 32,768 x 32,768).  The same recurrence and
+ * the same walk; H / E / F live in rolling rows, and of each cell only the comparisons the walk takes are kept, one byte per cell:
+ *   TBL_ZERO  H == 0                     TBL_DIAG  H == H(i-1,j-1) + s          TBL_F   H == F           TBL_E   H == E
+ *   TBL_FOPEN F == H(i-1,j) - open       TBL_EOPEN E == H(i,j-1) - open
+ * *tie: some cell where the walk turns into F also has H == E (the transposed pair's walk, which tries its F = this E first, would
+ * take the other gap there).  Returns 0, or -1 if the byte matrix cannot be allocated. */
+enum { TBL_ZERO = 1, TBL_DIAG = 2, TBL_F = 4, TBL_FOPEN = 8, TBL_EOPEN = 16, TBL_E = 32 };
+int uco_traceback_lean(const uco_db *db, uint32_t q, uint32_t t, const uco_params *p, int qs, int qe, int ts, int te,
+                       int32_t *aln_len, int32_t *idents, int32_t *gap_opens, int32_t *tie) {
+    const uint8_t *q3 = db->s3 + db->off[q] + qs, *qa = db->sa + db->off[q] + qs;
+    const uint8_t *t3 = db->s3 + db->off[t] + ts, *ta = db->sa + db->off[t] + ts;
+    const int lq = qe - qs + 1, lt = te - ts + 1;
+    const int open = p->gap_open, ext = p->gap_ext;
+    const int32_t NEG = -(1 << 28);
+    const size_t W = (size_t)lt;
+    uint8_t *D = (uint8_t *)malloc((size_t)lq * W);                     /* decisions of cell (i, j), 1-based, at (i-1) * W + j-1 */
+    int32_t *H = (int32_t *)calloc(W + 1, sizeof(int32_t));             /* row i-1 on entry to row i, [0] = the border column */
+    int32_t *F = (int32_t *)malloc((W + 1) * sizeof(int32_t));
+    if (!D || !H || !F) { free(D); free(H); free(F); return -1; }
+    for (size_t j = 0; j <= W; j++) F[j] = NEG;
+    for (int i = 1; i <= lq; i++) {
+        const int8_t *r3 = p->S3 + q3[i - 1] * UCO_A, *ra = p->SA + qa[i - 1] * UCO_A;
+        uint8_t *d = D + (size_t)(i - 1) * W;
+        int32_t hdiag = 0, hleft = 0, eleft = NEG;                      /* H(i-1,j-1), H(i,j-1), E(i,j-1) */
+        for (int j = 1; j <= lt; j++) {
+            const int s = r3[t3[j - 1]] + ra[ta[j - 1]];
+            const int32_t hup = H[j];
+            int32_t e = eleft - ext; if (hleft - open > e) e = hleft - open;
+            int32_t f = F[j] - ext; if (hup - open > f) f = hup - open;
+            int32_t h = hdiag + s;
+            if (e > h) h = e;
+            if (f > h) h = f;
+            if (h < 0) h = 0;
+            d[j - 1] = (uint8_t)((h == 0 ? TBL_ZERO : 0) | (h == hdiag + s ? TBL_DIAG : 0) | (h == f ? TBL_F : 0) | (h == e ? TBL_E : 0) |
+                                 (f == hup - open ? TBL_FOPEN : 0) | (e == hleft - open ? TBL_EOPEN : 0));
+            hdiag = hup; H[j] = h; F[j] = f; hleft = h; eleft = e;
+        }
+    }
+    int i = lq, j = lt, state = 0, len = 0, id = 0, gaps = 0, tied = 0;
+    while (i > 0 && j > 0) {
+        const uint8_t c = D[(size_t)(i - 1) * W + (size_t)(j - 1)];
+        if (state == 0) {
+            if (c & TBL_ZERO) break;
+            if (c & TBL_DIAG) { len++; id += (qa[i - 1] == ta[j - 1]); i--; j--; }
+            else if (c & TBL_F) { state = 1; gaps++; tied |= (c & TBL_E) != 0; }
+            else { state = 2; gaps++; }
+        } else if (state == 1) {
+            len++;
+            if (c & TBL_FOPEN) state = 0;
+            i--;
+        } else {
+            len++;
+            if (c & TBL_EOPEN) state = 0;
+            j--;
+        }
+    }
+    free(D); free(H); free(F);
+    *aln_len = len; *idents = id; *gap_opens = gaps; *tie = tied;
+    return 0;
+}
+
+/* boxes of more cells than this take uco_traceback_lean in uco_align_pair: 2^25 cells are 403 MB of traceback()'s matrices, the most
+ * the suite's boxes ever asked of it (4,300 x 5,003 = 21.5 M cells); above, one byte per cell reaches the 65,535 x 65,535 limit in 4.3 GB */
+#define UCO_TB_LEAN_CELLS ((uint64_t)1 << 25)
+
 /* Foldseek structurealign for one (query, target) pair (call site cluster.rs:45-49). */
 void uco_align_pair(const uco_db *db, uint32_t q, uint32_t t, const uco_params *p, int32_t min_score, uco_aln *o) {
     memset(o, 0, sizeof *o);
@@ -553,7 +618,13 @@ void uco_align_pair(const uco_db *db, uint32_t q, uint32_t t, const uco_params *
     float tcov = (float)(o->tend - o->tstart + 1) / (float)lt;
     int ok = p->cov_mode == 0 ? (qcov >= p->cov && tcov >= p->cov) : p->cov_mode == 1 ? (tcov >= p->cov) : (qcov >= p->cov);
     if (ok && (p->min_seq_id > 0.0f || p->want_tb)) {
-        traceback(db, q, t, p, o->qstart, o->qend, o->tstart, o->tend, &o->aln_len, &o->idents, &o->gap_opens);
+        int32_t tie;
+        const uint64_t cells = (uint64_t)(o->qend - o->qstart + 1) * (uint64_t)(o->tend - o->tstart + 1);
+        if (cells <= UCO_TB_LEAN_CELLS) traceback(db, q, t, p, o->qstart, o->qend, o->tstart, o->tend, &o->aln_len, &o->idents, &o->gap_opens);
+        else if (uco_traceback_lean(db, q, t, p, o->qstart, o->qend, o->tstart, o->tend, &o->aln_len, &o->idents, &o->gap_opens, &tie) != 0) {
+            fprintf(stderr, "uco_align_pair: no memory for the traceback of pair (%u, %u)\n", q, t);
+            abort();
+        }
         float sid = o->aln_len > 0 ? (float)o->idents / (float)o->aln_len : 0.0f;
         if (p->min_seq_id > 0.0f) ok = sid >= p->min_seq_id;
     }

@@ -228,6 +228,10 @@ uint64_t uco_sample_run(const uco_db *db, const uco_index *ix, const uco_params 
 /* traceback statistics of the box [qs..qe] x [ts..te] (spec E6) */
 void uco_traceback(const uco_db *db, uint32_t q, uint32_t t, const uco_params *p, int qs, int qe, int ts, int te,
                    int32_t *aln_len, int32_t *idents, int32_t *gap_opens);
+/* the same statistics from rolling rows and one byte of decisions per cell (boxes up to 65,535 x 65,535), plus the gap-direction tie
+   mark: 1 if some cell where the walk turns into F also has H == E.  uco_align_pair uses it for boxes above 2^25 cells.  0 / -1 (no memory) */
+int uco_traceback_lean(const uco_db *db, uint32_t q, uint32_t t, const uco_params *p, int qs, int qe, int ts, int te,
+                       int32_t *aln_len, int32_t *idents, int32_t *gap_opens, int32_t *tie);
 
 /* ---- vectorised CPU leg (uc_simd.c; bench.py cpu_baseline "kind": "simd") -------------------------------------------
    E5/E6 of one query against its hit list with inter-sequence AVX2 Smith-Waterman: results identical to uco_align_pair */

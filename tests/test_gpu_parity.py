@@ -126,7 +126,9 @@ def test_sw_long_query_fallback(O):
                                   # (3Di -48..38, AA -17..48) with the largest gap open: 86 + 31 = 117 (long sequences leave the packed score range and
                                   # take the int32 pass, the others the byte walk)
                                   "-c 0.5 --mat-bit-factor-3di 9.5 --mat-bit-factor-aa 8.7 --gap-open 31 --gap-extend 3 --min-seq-id 0.3",
-                                  "-c 0.5 --mat-bit-factor-aa 8.7 --gap-open 31 --gap-extend 31 --min-seq-id 0.2 --max-seqs 50"])
+                                  "-c 0.5 --mat-bit-factor-aa 8.7 --gap-open 31 --gap-extend 31 --min-seq-id 0.2 --max-seqs 50",
+                                  # free gap extension, the edge of the recurrence (E - ext saturating at ext = 0; a gap is still left as soon as it can be)
+                                  "-c 0.5 --gap-extend 0 --min-seq-id 0.3", "-c 0.8 --gap-open 4 --gap-extend 0"])
 def test_pipeline_stage_parity(O, small, opts):
     """prefilter hit lists, per-pair alignment records, edges and the set cover all equal the oracle's"""
     import unicore_amd as U
@@ -915,11 +917,11 @@ def test_linclust_workflow_tsv_bytes(O, tmp_path, opts, steps, m):
     assert len(pr) > 20 and (pr[:, 0] != pr[:, 1]).all()
 
 
-@pytest.mark.parametrize("seed", list(range(16)))
+@pytest.mark.parametrize("seed", list(range(20)))
 def test_random_option_sets_against_the_oracle(O, seed):
     """property test: random small databases x random option strings (gates, gap costs, sensitivity, truncation, execution
     variants): accepted pairs and the cluster assignment equal the oracle's.  Seeds >= 12 add sequences beyond 2048
-    residues with a mutated copy each (row-blocked kernel in every pass)."""
+    residues with a mutated copy each (row-blocked kernel in every pass).  Seeds >= 16 run under --gap-extend 0."""
     import unicore_amd as U
     rng = np.random.default_rng(1000 + seed)
     extra = tuple(int(x) for x in rng.integers(300, 1900, int(rng.integers(0, 3))))
@@ -945,6 +947,9 @@ def test_random_option_sets_against_the_oracle(O, seed):
     if rng.random() < 0.3: eng.append("--sym-dedup 0")
     if rng.random() < 0.3: eng.append("--sw-kernel i32")
     if rng.random() < 0.35: opts.append("--length-gate 1")     # optional rule UC-1/L (drawn last: the other draws of a seed are what they were)
+    if seed >= 16:     # free gap extension, with the traceback statistics (new seeds, drawn last: seeds 0..15 draw what they drew)
+        opts = [o for o in opts if not o.startswith(("--gap-open", "--min-seq-id"))]
+        opts += ["--gap-open %d --gap-extend 0" % rng.choice([4, 8, 10]), "--min-seq-id %.2f" % rng.choice([0.2, 0.4])]
     ostr = " ".join(opts)
     off, c3, ca = util.flat(s3, sa)
     e = U.Engine(ostr + " " + " ".join(eng), verbosity=1)

@@ -457,7 +457,11 @@ __global__ void __launch_bounds__(256) finalize_kernel(uint32_t n2, const uint32
 }
 
 // seq-id stage (only with --min-seq-id > 0): pairs that passed the coverage gate get their traceback statistics
-constexpr uint32_t TB_BAND_MISS = 0x7FFFFFFFu;     // "the walk left the stored band" (no traceback has length 0x7fff with 0xffff identities)
+// Every statistic of a traceback travels in a 32-bit word of its own, the count in bits 0..30 and the gap-direction tie mark of the walk that
+// counted it in bit 31: alignment length (at most lq + lt = 131,070 columns), identities (at most 65,535), gaps (at most the length).  One word
+// cannot hold two of them: 17 + 16 bits and the mark.
+constexpr uint32_t TB_COUNT = 0x7FFFFFFFu;
+constexpr uint32_t TB_BAND_MISS = 0x7FFFFFFFu;     // in the length word: "the walk left the stored band" (no traceback has 2^31 - 1 columns)
 __global__ void __launch_bounds__(256) tb_gather_kernel(uint32_t n2, const uint32_t *eflag, const uint32_t *epos, const uint32_t *idx2,
                                                         const uint32_t *link, const uint32_t *idx0, const uint32_t *sq2, const uint32_t *st2,
                                                         const uc_aln *alns, uint32_t *q3, uint32_t *t3, int32_t *qs3, int32_t *qe3,
@@ -472,7 +476,7 @@ __global__ void __launch_bounds__(256) tb_gather_kernel(uint32_t n2, const uint3
     }
 }
 __global__ void __launch_bounds__(256) tb_apply_kernel(uint32_t n3, const uint32_t *idx3, const uint32_t *src3, const int32_t *pack,
-                                                       const int32_t *gaps, const uint32_t *idx2, const uint32_t *link, const uint32_t *idx0,
+                                                       const int32_t *ident, const int32_t *gaps, const uint32_t *idx2, const uint32_t *link, const uint32_t *idx0,
                                                        float min_seq_id, uc_aln *alns, uint32_t *eflag, uint32_t *tie, uint32_t *miss) {
     for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n3; i += gridDim.x * 256) {
         const uint32_t i2 = src3[idx3[i]];
@@ -482,10 +486,10 @@ __global__ void __launch_bounds__(256) tb_apply_kernel(uint32_t n3, const uint32
             miss[i2] = pk == TB_BAND_MISS;
             if (pk == TB_BAND_MISS) continue;
         }
-        a.aln_len = (int32_t)((pk >> 16) & 0x7fffu);
-        a.idents = (int32_t)(pk & 0xffffu);
+        a.aln_len = (int32_t)(pk & TB_COUNT);
+        a.idents = (int32_t)((uint32_t)ident[i] & TB_COUNT);
         if (tie) tie[i2] = pk >> 31;
-        if (gaps) a.gap_opens = gaps[i] & 0x7fffffff;   // bit 31 is the gap-direction tie mark of the pass
+        if (gaps) a.gap_opens = (int32_t)((uint32_t)gaps[i] & TB_COUNT);
         if (min_seq_id > 0.0f) {
             const float sid = a.aln_len > 0 ? (float)a.idents / (float)a.aln_len : 0.0f;
             const bool ok = sid >= min_seq_id;
@@ -513,7 +517,7 @@ __global__ void __launch_bounds__(256) tb_size_kernel(uint32_t n_pk, const uint6
     }
 }
 // one thread per pair walks its matrix of H bytes (packed MODE 7) from the end cell (oracle: traceback(), diag > F > E, a gap is left
-// as soon as it can be): (alignment length << 16 | identities | tie << 31) and the number of gaps.
+// as soon as it can be): alignment length | tie << 31, identities and the number of gaps, a word each.
 // The end cell's H is the pair's score; a cell next to one whose H is known differs from it by less than 128 (vertical / horizontal
 // neighbours: -open .. M + open, diagonal: min score .. M, M = the largest substitution score; the host checks M + open <= 127 and
 // sends everything else through the int32 pass), so its byte gives its H exactly.  Every decision the traceback takes is a comparison
@@ -551,7 +555,7 @@ __global__ void __launch_bounds__(256) tb_walk_kernel(uint32_t p_begin, uint32_t
                                                       const int32_t *sqs, const int32_t *sqe, const int32_t *sts, const int32_t *ste,
                                                       const int32_t *score, int open, int ext, int band,
                                                       int tab, const uint8_t *tbm, const unsigned long long *tboff, int32_t *pack,
-                                                      int32_t *gaps_out, uint32_t *bt_cnt, const uint32_t *bt_off, uint32_t *bt_runs,
+                                                      int32_t *ident_out, int32_t *gaps_out, uint32_t *bt_cnt, const uint32_t *bt_off, uint32_t *bt_runs,
                                                       unsigned long long bt_base, unsigned long long *bt_pos, uint32_t *bt_plain, uint32_t *bt_err) {
     __shared__ int8_t s_S3[21 * 21], s_SA[21 * 21];
     for (int k = threadIdx.x; k < 21 * 21; k += 256) { s_S3[k] = db.S3[k]; s_SA[k] = db.SA[k]; }
@@ -669,7 +673,8 @@ __global__ void __launch_bounds__(256) tb_walk_kernel(uint32_t p_begin, uint32_t
             continue;                                                  // the statistics were written by the counting walk
         }
         if (EMIT == 1) bt_cnt[p] = miss ? 0u : sink.n;
-        pack[p] = miss ? (int32_t)TB_BAND_MISS : (int32_t)((len << 16) | id | (tie << 31));
+        pack[p] = miss ? (int32_t)TB_BAND_MISS : (int32_t)(len | (tie << 31));
+        ident_out[p] = (int32_t)id;
         if (gaps_out) gaps_out[p] = (int32_t)gaps;
     }
 }
@@ -1098,7 +1103,7 @@ struct AlignScratch {
     DevBuf<unsigned long long> tb_tbsize, tb_tboff, tb_toff;
     DevBuf<uint8_t> tb_tbm;
     bool tb_tbm_live = false;        // inside the batch loop of a MODE 7 call: the one time the matrices may not be given back (release_tb_matrices)
-    DevBuf<int32_t> tb_qs3, tb_qe3, tb_ts3, tb_te3, tb_pack3, tb_gaps3, tb_sc3;
+    DevBuf<int32_t> tb_qs3, tb_qe3, tb_ts3, tb_te3, tb_pack3, tb_id3, tb_gaps3, tb_sc3;
     SwPlan tb_P3;
     // backtraces (-a): runs per pair of the traceback plan, slice offsets inside a matrix batch, where each slice went, which kernel walked it
     DevBuf<uint32_t> bt_cnt3, bt_off3, bt_plain3, bt_err, lg_btn;
@@ -1449,7 +1454,8 @@ static bool tb_bytes_ok(const Params &p) {
     return p.gap_open >= p.gap_ext && p.gap_ext >= 0 && m3 + ma + p.gap_open <= 127 && n3 + na >= -127;
 }
 
-constexpr uint32_t TB_GAPS[4] = {0u, 0u, 1u, 0u};   // MODE 3 weights (diagonal, identity, open, extension) of the gap count
+// MODE 3 weights (diagonal, identity, open, extension), one pass per statistic: columns of the alignment, identities, gaps
+constexpr uint32_t TB_LEN[4] = {1u, 0u, 1u, 1u}, TB_IDENT[4] = {0u, 1u, 0u, 0u}, TB_GAPS[4] = {0u, 0u, 1u, 0u};
 
 // the walk over the matrices of pairs [p0, p1) of the plan tb_P3 that are resident now.  Without -a: the statistics walk.  With -a (E.emit_bt):
 // count (statistics + runs per pair), scan, make room in the engine's run buffer for exactly that many, write.
@@ -1462,7 +1468,7 @@ static void tb_walk(Engine &E, uint32_t p0, uint32_t p1, int band, const uint8_t
     const dim3 grid = grid_for(p1 - p0);
 #define UC_TB_WALK(EMIT, base)                                                                                                                   \
     hipLaunchKernelGGL((tb_walk_kernel<EMIT, PLAIN>), grid, dim3(256), 0, s, p0, p1, E.ddb, P3.key2.p, P3.st.p, P3.sqs.p, P3.sqe.p, P3.sts.p, P3.ste.p,  \
-                       P3.saux.p, E.p.gap_open, E.p.gap_ext, band, 1, tbm, tboff, A.tb_pack3.p, A.tb_gaps3.p, A.bt_cnt3.p, A.bt_off3.p,              \
+                       P3.saux.p, E.p.gap_open, E.p.gap_ext, band, 1, tbm, tboff, A.tb_pack3.p, A.tb_id3.p, A.tb_gaps3.p, A.bt_cnt3.p, A.bt_off3.p,              \
                        E.d_bt_runs.p + (base), (unsigned long long)(base), A.bt_pos3.p, A.bt_plain3.p, A.bt_err.p)
     if (!E.emit_bt) {
         if constexpr (PLAIN == 0) UC_TB_WALK(0, 0);
@@ -1553,7 +1559,8 @@ static uint64_t tb_run_bytes(Engine &E, int band, const TbBudget &budget) {
     if (P3.n > n_pk3 && E.emit_bt) launches += tb_run_plain(E, n_pk3, P3.n, budget);   // -a: long queries need a stored matrix
     else if (P3.n > n_pk3) {                              // long queries: int32 MODE 3 (no matrices)
         E.timed_ms_begin();
-        launches += launch_plan(E, P3, 7, A.tb_pack3.p, nullptr, nullptr, A.work, nullptr, /*only_long=*/true);
+        launches += launch_plan(E, P3, 7, A.tb_pack3.p, nullptr, nullptr, A.work, TB_LEN, /*only_long=*/true);
+        launches += launch_plan(E, P3, 3, A.tb_id3.p, nullptr, nullptr, A.work, TB_IDENT, /*only_long=*/true);
         if (E.p.want_tb) launches += launch_plan(E, P3, 3, A.tb_gaps3.p, nullptr, nullptr, A.work, TB_GAPS, /*only_long=*/true);
         tb_ms += E.timed_ms_end();
     }
@@ -1612,7 +1619,7 @@ static uint64_t tb_run_bytes(Engine &E, int band, const TbBudget &budget) {
 }
 
 // the traceback statistics of the flagged gate passers: gather, plan, run, apply.  pk: packed MODE 7 (tb_run_bytes); otherwise the int32
-// kernel carries the statistics through the DP (MODE 3, one pass per statistic).  band > 0: the walk marks the pairs whose path left the
+// kernel carries the statistics through the DP (MODE 3, one pass per statistic: TB_LEN, TB_IDENT, TB_GAPS).  band > 0: the walk marks the pairs whose path left the
 // band in tb_tmiss.
 static void tb_batch(Engine &E, const AlignBatch &B, const uint32_t *flag, bool pk, int band, const TbBudget &budget) {
     AlignScratch &A = scratch_of(E);
@@ -1621,7 +1628,7 @@ static void tb_batch(Engine &E, const AlignBatch &B, const uint32_t *flag, bool 
     const uint32_t nt = compact(E, A.tmp, flag, A.tb_tpos.p, n2);
     if (!nt) return;
     A.tb_q3.reserve(nt); A.tb_t3.reserve(nt); A.tb_src3.reserve(nt); A.tb_qs3.reserve(nt); A.tb_qe3.reserve(nt); A.tb_ts3.reserve(nt); A.tb_te3.reserve(nt);
-    A.tb_pack3.reserve(nt); A.tb_gaps3.reserve(nt); A.tb_sc3.reserve(nt);
+    A.tb_pack3.reserve(nt); A.tb_id3.reserve(nt); A.tb_gaps3.reserve(nt); A.tb_sc3.reserve(nt);
     hipLaunchKernelGGL(tb_gather_kernel, grid_for(n2), dim3(256), 0, s, n2, flag, A.tb_tpos.p, A.iota2.p, A.link.p, B.Lidx, A.q2.p,
                        A.t2.p, B.alns_b, A.tb_q3.p, A.tb_t3.p, A.tb_qs3.p, A.tb_qe3.p, A.tb_ts3.p, A.tb_te3.p, A.tb_src3.p, A.tb_sc3.p);
     SwPlan &P3 = A.tb_P3;
@@ -1638,10 +1645,12 @@ static void tb_batch(Engine &E, const AlignBatch &B, const uint32_t *flag, bool 
     } else if (!pk) {
         build_plan(E, P3, A.tmp, nt, A.tb_q3.p, A.tb_t3.p, A.tb_qe3.p, A.tb_te3.p, 2, A.tb_qs3.p, A.tb_ts3.p);
         E.timed_ms_begin();
-        launches = launch_plan(E, P3, 3, A.tb_pack3.p, nullptr, nullptr, A.work);
-        if (E.p.want_tb) {   // second statistic of the same traceback: number of gaps (BLAST-tab "gapopen")
+        launches = launch_plan(E, P3, 3, A.tb_pack3.p, nullptr, nullptr, A.work, TB_LEN);
+        launches += launch_plan(E, P3, 3, A.tb_id3.p, nullptr, nullptr, A.work, TB_IDENT);
+        passes = 2;
+        if (E.p.want_tb) {   // third statistic of the same traceback: number of gaps (BLAST-tab "gapopen")
             launches += launch_plan(E, P3, 3, A.tb_gaps3.p, nullptr, nullptr, A.work, TB_GAPS);
-            passes = 2;
+            passes = 3;
         }
         E.stats.sw_kernel_ms += E.timed_ms_end();
     } else {
@@ -1652,7 +1661,7 @@ static void tb_batch(Engine &E, const AlignBatch &B, const uint32_t *flag, bool 
     E.stats.sw_algorithmic_bytes += passes * P3.alg_bytes;
     E.stats.cells_run += passes * P3.cells;
     E.stats.n_sw_runs += (uint64_t)passes * P3.n;
-    hipLaunchKernelGGL(tb_apply_kernel, grid_for(nt), dim3(256), 0, s, nt, P3.idx.p, A.tb_src3.p, A.tb_pack3.p,
+    hipLaunchKernelGGL(tb_apply_kernel, grid_for(nt), dim3(256), 0, s, nt, P3.idx.p, A.tb_src3.p, A.tb_pack3.p, A.tb_id3.p,
                        E.p.want_tb ? A.tb_gaps3.p : (const int32_t *)nullptr, A.iota2.p, A.link.p, B.Lidx, E.p.min_seq_id, B.alns_b,
                        A.eflag.p, A.tb_ttie.p, (pk && band > 0) ? A.tb_tmiss.p : (uint32_t *)nullptr);
     if (E.emit_bt) {
@@ -1868,7 +1877,7 @@ void Engine::sw_pass(int tab, int mode, int band, bool raw, const std::vector<Sw
         UC_HIP(hipMemsetAsync(bn.p, 0, n * 4, stream));
         B.bt_pos_b = bpos.p; B.bt_n_b = bn.p;
     }
-    p.want_tb = 1;         // both statistics: (alignment length, identities) and the gap count (the TB_GAPS weighting of MODE 3)
+    p.want_tb = 1;         // every statistic: alignment length, identities and the gap count (the TB_GAPS weighting of MODE 3)
     p.min_seq_id = 0.0f;   // no gate on the result
     const TbBudget budget;
     if (mode == 3) tb_batch(*this, B, all.p, false, 0, budget);

@@ -55,8 +55,9 @@ struct SwArgs {
     int32_t *oscore, *oqe, *ote;
     int open, ext;
     // mode 3: what the traceback statistic adds per path step (diagonal step, identical AA on it, first residue of a gap,
-    // further gap residues).  Default = (alignment length << 16 | identities); (0,0,1,0) counts the gaps instead.
-    uint32_t tb_diag = 0x10000u, tb_ident = 1u, tb_open = 0x10000u, tb_ext = 0x10000u;
+    // further gap residues), summed along the path in bits 0..30; bit 31 is the walk's gap-direction tie mark.  Default = the alignment
+    // length; (0,1,0,0) counts the identities, (0,0,1,0) the gaps.  One pass per statistic: lengths reach 131,070 and identities 65,535.
+    uint32_t tb_diag = 1u, tb_ident = 0u, tb_open = 1u, tb_ext = 1u;
     // packed modes 4/6 (optional, null = not written): the end under the other tie-break order - first optimal row, then first column - which is the
     // answer of the transposed DP (the mirror of a mutual hit).  Last in the struct: the other kernels' argument offsets stay where they were.
     int32_t *oqe2 = nullptr, *ote2 = nullptr;

@@ -144,7 +144,7 @@ __global__ void __launch_bounds__(NW * 64) sw_group_kernel(const SwArgs a) {
         int bestcol = -1;
         int Tlast = -open, prevTup = -open;
         uint32_t fout = 0;
-        // TB state: packed (aln_len << 16 | idents) of the path into H / E per row, F flowing down the column
+        // TB state: the statistic of the pass (SwArgs::tb_*, bit 31 = tie mark) of the path into H / E per row, F flowing down the column
         uint32_t Hp[TB ? R : 1], Ep[TB ? R : 1];
         uint32_t HpLast = 0, prevHpUp = 0, FpOut = 0, cap = 0;
         const int qe_row = TB ? a.pqe[gp] : 0;
