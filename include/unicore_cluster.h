@@ -374,6 +374,10 @@ int uc_tree(const char *db_prefix, const char *profile_dir, const char *out_dir,
 /* ungapped diagonal score (E3) for n candidates (q[i], t[i], diag[i]) of the engine's DB */
 int uc_engine_ungapped_batch(uc_engine *e, uint64_t n, const uint32_t *q, const uint32_t *t,
                              const int32_t *diag, int32_t *score_out);
+/* E3 and the key pass of E4 for n candidates, with the prefilter's own launches: the scores (score_out may be null), the overlap residues
+ * E3 counts for the stage's algorithmic bytes, and the number of candidates with score >= min_score that E4 keeps */
+int uc_engine_ungapped_select(uc_engine *e, uint64_t n, const uint32_t *q, const uint32_t *t, const int32_t *diag, int32_t min_score,
+                              int32_t *score_out, uint64_t *overlap_out, uint64_t *kept_out);
 /* rule UC-1/X (--prefilter-mode 1) for queries [qbegin, qend) x targets [tbegin, tend) of the engine's DB: dense row-major
  * [qend - qbegin][tend - tbegin] arrays, the best ungapped score over ALL diagonals (capped at 255) and the smallest diagonal that
  * reaches it.  Computed tile by tile under tile_bytes (0 = the engine's default tile budget). */

@@ -70,7 +70,7 @@ SYMBOLS = (
     "uc_engine_hits_export_dev", "uc_engine_hits_import_dev", "uc_engine_setcover",
     "uc_hits_merge", "uc_engine_align", "uc_engine_alns_get", "uc_engine_edges_size", "uc_engine_edges_get",
     "uc_engine_stats", "uc_engine_reset_stats", "uc_setcover", "uc_write_cluster_db",
-    "uc_engine_ungapped_batch", "uc_engine_ungapped_all", "uc_engine_sw_batch", "uc_engine_sw_pass", "uc_engine_sw_pass2", "uc_engine_backtraces_size", "uc_engine_backtraces_get",
+    "uc_engine_ungapped_batch", "uc_engine_ungapped_select", "uc_engine_ungapped_all", "uc_engine_sw_batch", "uc_engine_sw_pass", "uc_engine_sw_pass2", "uc_engine_backtraces_size", "uc_engine_backtraces_get",
     "uc_backtrace_render", "uc_format_output_check", "uc_engine_tb_emit_pass", "uc_abi_version", "uc_stats_size", "uc_set_round_hook",
     "uc_t5_gemm_variant", "uc_t5_kernel_gemm", "uc_t5_kernel_rmsnorm", "uc_t5_kernel_attention", "uc_t5_kernel_cnn_head", "uc_t5_bias_table",
     "uc_cluster_graph", "uc_engine_cluster_graph", "uc_engine_reassign", "uc_engine_td_onchip", "uc_engine_linclust_pairs",
@@ -163,6 +163,7 @@ def lib():
     L.uc_msa_filter_dev.argtypes = [i32] + L.uc_msa_filter.argtypes
     L.uc_tree.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, u32, C.c_char_p, C.POINTER(UcOpts), C.POINTER(UcTreeStats)]
     L.uc_engine_ungapped_batch.argtypes = [vp, u64, vp, vp, vp, vp]
+    L.uc_engine_ungapped_select.argtypes = [vp, u64, vp, vp, vp, C.c_int32, vp, vp, vp]
     L.uc_engine_ungapped_all.argtypes = [vp, u32, u32, u32, u32, u64, vp, vp]
     L.uc_engine_sw_batch.argtypes = [vp, C.c_int, u64, vp, vp, vp, vp, vp, vp, vp]
     L.uc_engine_sw_pass.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, u64, vp, vp, vp, vp] + [vp] * 8
@@ -755,6 +756,16 @@ class Engine:
         out = np.zeros(len(q), np.int32)
         _check(lib().uc_engine_ungapped_batch(self._h, len(q), q.ctypes.data, t.ctypes.data, diag.ctypes.data, out.ctypes.data))
         return out
+
+    def ungapped_select(self, q, t, diag, min_score):
+        """E3 and E4's key pass on explicit candidates (uc_engine_ungapped_select): (scores, overlap residues counted, candidates kept)"""
+        q = np.ascontiguousarray(q, np.uint32); t = np.ascontiguousarray(t, np.uint32)
+        diag = np.ascontiguousarray(diag, np.int32)
+        out = np.zeros(len(q), np.int32)
+        ovl, kept = C.c_uint64(0), C.c_uint64(0)
+        _check(lib().uc_engine_ungapped_select(self._h, len(q), q.ctypes.data, t.ctypes.data, diag.ctypes.data, int(min_score), out.ctypes.data,
+                                               C.byref(ovl), C.byref(kept)))
+        return out, int(ovl.value), int(kept.value)
 
     def ungapped_all(self, qbegin=0, qend=None, tbegin=0, tend=None, tile_bytes=0):
         """Rule UC-1/X (--prefilter-mode 1) on queries [qbegin, qend) x targets [tbegin, tend): dense int32 arrays (score, diag) of that shape,

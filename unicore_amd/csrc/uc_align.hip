@@ -141,8 +141,7 @@ __global__ void __launch_bounds__(256) plan_key_kernel(uint32_t n, const uint32_
         bytes += 2ull * (ql + tl) + 32;
         cells += (unsigned long long)ql * tl;
     }
-    for (int o = 32; o > 0; o >>= 1) { bytes += __shfl_down(bytes, o, 64); cells += __shfl_down(cells, o, 64); }
-    if ((threadIdx.x & 63) == 0 && bytes) { atomicAdd(alg_bytes, bytes); atomicAdd(alg_bytes + 1, cells); }
+    block_add2(bytes, cells, alg_bytes, alg_bytes + 1);
 }
 
 __global__ void __launch_bounds__(256) plan_gather_kernel(uint32_t n, const uint64_t *key, const uint32_t *idx, const uint32_t *t,
@@ -310,8 +309,7 @@ __global__ void __launch_bounds__(256) cells_kernel(uint32_t n, const uint32_t *
     unsigned long long c = 0;
     for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256)
         if (!flag || flag[i]) c += (unsigned long long)len[q[i]] * len[t[i]];
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o, 64);
-    if ((threadIdx.x & 63) == 0 && c) atomicAdd(out, c);
+    block_add(c, out);
 }
 
 // ---- start pass shared between mutual hits ----
@@ -405,15 +403,13 @@ __global__ void __launch_bounds__(256) cells_tb_kernel(uint32_t n2, const uint32
             const uc_aln a = alns[idx0[link[i]]];
             c += (unsigned long long)(a.qend - a.qstart + 1) * (unsigned long long)(a.tend - a.tstart + 1);
         }
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o, 64);
-    if ((threadIdx.x & 63) == 0 && c) atomicAdd(out, c);
+    block_add(c, out);
 }
 // algorithmic cells of the start pass: (qEnd+1) x (tEnd+1) per gate passer
 __global__ void __launch_bounds__(256) cells_box_kernel(uint32_t n, const int32_t *qe, const int32_t *te, unsigned long long *out) {
     unsigned long long c = 0;
     for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) c += (unsigned long long)(qe[i] + 1) * (unsigned long long)(te[i] + 1);
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o, 64);
-    if ((threadIdx.x & 63) == 0 && c) atomicAdd(out, c);
+    block_add(c, out);
 }
 
 __global__ void __launch_bounds__(256) gate_scatter_kernel(uint32_t n, const uint32_t *flag, const uint32_t *pos, const uint32_t *sq,
@@ -906,7 +902,7 @@ static void build_plan(Engine &E, SwPlan &P, DevBuf<char> &tmp, uint32_t n, cons
     if (qs) { P.sqs.reserve(n); P.sts.reserve(n); }
     P.bytes.reserve(2); P.bounds.reserve(2 * NB);
     UC_HIP(hipMemsetAsync(P.bytes.p, 0, 16, s));
-    hipLaunchKernelGGL(plan_key_kernel, grid_for(n), dim3(256), 0, s, n, q, t, qe, te, qs, ts, E.ddb.len, tab, P.key.p, P.idx_in.p, P.bytes.p);
+    hipLaunchKernelGGL(plan_key_kernel, grid_for(n, E.count_grid_cap), dim3(256), 0, s, n, q, t, qe, te, qs, ts, E.ddb.len, tab, P.key.p, P.idx_in.p, P.bytes.p);
     rocprim_call(tmp, [&](void *t, size_t &b) { return rocprim::radix_sort_pairs(t, b, P.key.p, P.key2.p, P.idx_in.p, P.idx.p, (size_t)n, 0u, 45u, s); });
     hipLaunchKernelGGL(plan_gather_kernel, grid_for(n), dim3(256), 0, s, n, P.key2.p, P.idx.p, t, qe, te, qs, ts, P.sq.p, P.st.p, P.sqe.p, P.ste.p, P.sqs.p, P.sts.p, P.head.p);
     if (aux) {
@@ -1319,7 +1315,7 @@ static void forward_pass(Engine &E, AlignBatch &B) {
     run_plan(E, A.P0, 0, A.su.p, A.qeu.p, A.teu.p, A.work, A.tmp, /*ovf_only=*/true);
     hipLaunchKernelGGL(uscatter_kernel, grid_for(nu), dim3(256), 0, s, nu, n, A.P0.idx.p, A.jrep.p, A.mirror.p, A.su.p, A.qeu.p, A.teu.p,
                        packed_prefix(A.P0).pairs, SW_PK_OVF_HOST, A.s0.p, A.qe0.p, A.te0.p);
-    hipLaunchKernelGGL(cells_kernel, grid_for(n), dim3(256), 0, s, n, A.fq.p, A.ft.p, (const uint32_t *)nullptr, E.ddb.len, A.d_cells.p);
+    hipLaunchKernelGGL(cells_kernel, grid_for(n, E.count_grid_cap), dim3(256), 0, s, n, A.fq.p, A.ft.p, (const uint32_t *)nullptr, E.ddb.len, A.d_cells.p);
     B.Lsq = A.fq.p; B.Lst = A.ft.p; B.Lidx = A.uidx.p;
 }
 
@@ -1334,7 +1330,7 @@ static void rev_correction_pass(Engine &E, AlignBatch &B) {
     hipLaunchKernelGGL(gate_kernel, grid_for(n), dim3(256), 0, s, n, B.Lsq, A.s0.p, (const int32_t *)nullptr, A.d_ms.p, B.qbegin, A.gflag.p);
     if (B.dedup) {
         A.rcopy.reserve(n);
-        hipLaunchKernelGGL(cells_kernel, grid_for(n), dim3(256), 0, s, n, B.Lsq, B.Lst, A.gflag.p, E.ddb.len, A.d_cells.p + 1);
+        hipLaunchKernelGGL(cells_kernel, grid_for(n, E.count_grid_cap), dim3(256), 0, s, n, B.Lsq, B.Lst, A.gflag.p, E.ddb.len, A.d_cells.p + 1);
         hipLaunchKernelGGL(rev_dedup_kernel, grid_for(n), dim3(256), 0, s, n, A.mirror.p, A.gflag.p, A.rcopy.p);
         hipLaunchKernelGGL(rev_unflag_kernel, grid_for(n), dim3(256), 0, s, n, A.rcopy.p, A.gflag.p);
     }
@@ -1422,7 +1418,7 @@ static void start_pass(Engine &E, AlignBatch &B) {
     A.iota2.reserve(n2); A.s2s.reserve(n2); A.q2os.reserve(n2); A.t2os.reserve(n2);
     hipLaunchKernelGGL(iota_kernel, grid_for(n2), dim3(256), 0, s, n2, A.iota2.p);
     UC_HIP(hipMemsetAsync(A.d_cells.p, 0, 8, s));
-    hipLaunchKernelGGL(cells_box_kernel, grid_for(n2), dim3(256), 0, s, n2, A.qe2.p, A.te2.p, A.d_cells.p);
+    hipLaunchKernelGGL(cells_box_kernel, grid_for(n2, E.count_grid_cap), dim3(256), 0, s, n2, A.qe2.p, A.te2.p, A.d_cells.p);
     if (B.dedup && B.tab == 1) {
         start_pass_known(E, B);
     } else {
@@ -1929,7 +1925,7 @@ static void traceback_stats(Engine &E, const AlignBatch &B) {
     UC_HIP(hipMemsetAsync(A.tb_ttie.p, 0, (size_t)n2 * 4, s));
     unsigned long long hc = 0;
     UC_HIP(hipMemsetAsync(A.d_cells.p, 0, 8, s));
-    hipLaunchKernelGGL(cells_tb_kernel, grid_for(n2), dim3(256), 0, s, n2, A.eflag.p, A.link.p, B.Lidx, B.alns_b, A.d_cells.p);
+    hipLaunchKernelGGL(cells_tb_kernel, grid_for(n2, E.count_grid_cap), dim3(256), 0, s, n2, A.eflag.p, A.link.p, B.Lidx, B.alns_b, A.d_cells.p);
     UC_HIP(hipMemcpyAsync(&hc, A.d_cells.p, 8, hipMemcpyDeviceToHost, s));
     UC_HIP(hipStreamSynchronize(s));
     E.stats.cells_tb += hc;

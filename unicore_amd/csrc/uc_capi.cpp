@@ -449,6 +449,16 @@ int uc_engine_ungapped_batch(uc_engine *e, uint64_t n, const uint32_t *q, const 
     });
 }
 
+int uc_engine_ungapped_select(uc_engine *e, uint64_t n, const uint32_t *q, const uint32_t *t, const int32_t *diag, int32_t min_score, int32_t *score_out,
+                              uint64_t *overlap_out, uint64_t *kept_out) {
+    return guard([&] {
+        require(e, "engine");
+        require(overlap_out, "overlap_out"); require(kept_out, "kept_out");
+        if (n) { require(q, "q"); require(t, "t"); require(diag, "diag"); }
+        e->e->ungapped_select(n, q, t, diag, min_score, score_out, overlap_out, kept_out);
+    });
+}
+
 int uc_engine_ungapped_all(uc_engine *e, uint32_t qbegin, uint32_t qend, uint32_t tbegin, uint32_t tend, uint64_t tile_bytes, int32_t *score_out, int32_t *diag_out) {
     return guard([&] {
         require(e, "engine");

@@ -85,6 +85,40 @@ __host__ __device__ inline TbBand tb_band_of(int qs, int qe, int tl, int G, int 
     return b;
 }
 
+// ---- counter sums -------------------------------------------------------------------------------------------------------------
+// Atomics of one launch on one address are served one after the other, so a kernel that ends in one atomicAdd per wave runs as long as its
+// atomics take, whatever it streams.  block_add sums a per-thread value over the workgroup - wave shuffle, one partial per wave through LDS - and
+// thread 0 adds the total with ONE atomic, none when the total is zero.  It holds a barrier: EVERY thread of the workgroup calls it exactly once, behind
+// the grid-stride loop and never under a divergent condition or after an early return.  One call per kernel (the partials are one LDS array per
+// form): a kernel with two counters takes block_add2.  T = unsigned long long or uint32_t; workgroups of up to 1024 threads.
+#ifdef __HIPCC__
+template <typename T>
+__device__ __forceinline__ void block_add(unsigned long long v, T *dst) {
+    __shared__ unsigned long long part[16];
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long s = 0;
+        for (uint32_t w = 0; w < (blockDim.x + 63) >> 6; w++) s += part[w];
+        if (s) atomicAdd(dst, (T)s);
+    }
+}
+template <typename T>
+__device__ __forceinline__ void block_add2(unsigned long long va, unsigned long long vb, T *da, T *db) {
+    __shared__ unsigned long long part[2][16];
+    for (int o = 32; o > 0; o >>= 1) { va += __shfl_down(va, o, 64); vb += __shfl_down(vb, o, 64); }
+    if ((threadIdx.x & 63) == 0) { part[0][threadIdx.x >> 6] = va; part[1][threadIdx.x >> 6] = vb; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long sa = 0, sb = 0;
+        for (uint32_t w = 0; w < (blockDim.x + 63) >> 6; w++) { sa += part[0][w]; sb += part[1][w]; }
+        if (sa) atomicAdd(da, (T)sa);
+        if (sb) atomicAdd(db, (T)sb);
+    }
+}
+#endif
+
 // host launchers (uc_sw.hip / uc_prefilter.hip)
 void launch_sw_class(int G, int R, int mode, const SwArgs &a, uint32_t n_tasks, hipStream_t s);
 void launch_sw_pk_class(int G, int R, int mode, const SwArgs &a, uint32_t n_tasks, hipStream_t s);

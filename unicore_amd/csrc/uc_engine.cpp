@@ -54,6 +54,7 @@ Engine::Engine(const Params &pp, int dev) : p(pp) {
         UC_HIP(hipEventCreateWithFlags(&ev_join[i], hipEventDisableTiming));
     }
     if (const char *ns = getenv("UC_STREAMS")) n_streams = std::max(1, std::min(N_AUX + 1, atoi(ns)));
+    if (const char *gc = getenv("UC_COUNT_GRID_CAP")) count_grid_cap = (uint32_t)std::max(1, std::min(16384, atoi(gc)));
     d_S3.reserve(A * A);
     d_SA.reserve(A * A);
     UC_HIP(hipMemcpy(d_S3.p, p.S3, A * A, hipMemcpyHostToDevice));

@@ -132,6 +132,7 @@ struct PinnedBuf {   // page-locked host staging buffer (hipHostMalloc): D2H cop
     }
 };
 
+constexpr uint32_t COUNT_GRID_CAP = 2048;   // 8 workgroups of 256 threads per CU on 256 CUs: every wave slot filled once, the rest by grid stride
 inline dim3 grid_for(uint64_t n, uint32_t cap = 16384) {
     const uint64_t b = (n + 255) / 256;
     return dim3((uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(b, cap)));
@@ -239,6 +240,9 @@ struct Engine {
     hipStream_t aux[N_AUX] = {};
     hipEvent_t ev_fork = nullptr, ev_join[N_AUX] = {};
     int n_streams = N_AUX + 1;   // UC_STREAMS=1 serializes the class kernels on the engine stream (profiling: per-kernel durations then add up to the event time)
+    // grid cap of the streaming kernels that end in a counter sum (block_add, uc_device.h): one atomic per workgroup, so the cap bounds the same-address
+    // atomics of a launch.  UC_COUNT_GRID_CAP, read once per engine, is for the tests: tiny inputs on 1 or 3 workgroups
+    uint32_t count_grid_cap = COUNT_GRID_CAP;
 
     // host view of the DB
     HostDb hdb;
@@ -363,6 +367,8 @@ struct Engine {
     std::vector<uint32_t> linclust_pairs_impl(uint64_t *install, int m_override);
     // kernel-level
     void ungapped_batch(uint64_t n, const uint32_t *q, const uint32_t *t, const int32_t *diag, int32_t *out);
+    void ungapped_select(uint64_t n, const uint32_t *q, const uint32_t *t, const int32_t *diag, int min_score, int32_t *score_out, uint64_t *overlap_out,
+                         uint64_t *kept_out);      // uc_prefilter.hip
     // rule UC-1/X: dense [q1 - q0][t1 - t0] scores and diagonals, computed tile by tile under tile_bytes (0 = UNGAPPED_ALL_TILE_BYTES)   (uc_ungapped_all.hip)
     void ungapped_all(uint32_t q0, uint32_t q1, uint32_t t0, uint32_t t1, uint64_t tile_bytes, int32_t *score_out, int32_t *diag_out);
     void sw_batch(int mode, const std::vector<PairIn> &pairs, int32_t *score, int32_t *qe, int32_t *te);

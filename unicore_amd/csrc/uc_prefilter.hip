@@ -483,8 +483,7 @@ __global__ void __launch_bounds__(256) position_runs_kernel(const uint32_t *qk, 
         nr[idx] = x.nr; src[idx] = x.roff; ph[idx] = x.hits;
         sims += x.nsim;
     }
-    for (int o = 32; o > 0; o >>= 1) sims += __shfl_down(sims, o, 64);
-    if ((threadIdx.x & 63) == 0 && sims) atomicAdd(counters + 0, sims);
+    block_add(sims, counters + 0);
 }
 
 // per query: k-mer hits and runs (differences of the running sums over positions at the sequence boundaries)
@@ -1413,8 +1412,7 @@ __global__ void __launch_bounds__(256) select_key_kernel(uint64_t n, const uint3
         key[i] = ok ? ((uint64_t)cq[i] << 32) | ((uint64_t)(255 - s) << 24) | ct[i] : ~0ull;
         kept += ok;
     }
-    for (int o = 32; o > 0; o >>= 1) kept += __shfl_down(kept, o, 64);
-    if ((threadIdx.x & 63) == 0 && kept) atomicAdd(n_kept, kept);
+    block_add(kept, n_kept);
 }
 
 // E4 truncation: entry i of the (query, score desc, target) sorted list survives iff its rank inside its
@@ -1737,6 +1735,7 @@ static uint64_t distinct_runs(Engine &E, PrefilterPass &PP, const SuperBatch &SB
         UC_HIP(hipMemcpyAsync(c5, S.d_counters.p, 40, hipMemcpyDeviceToHost, E.stream));
         UC_HIP(hipStreamSynchronize(E.stream));
         n_druns = c5[3];
+        if (getenv("UC_TIMING")) fprintf(stderr, "unicore-cluster[timing]: similar k-mers of %u distinct k-mers: %llu index runs\n", nd, (unsigned long long)n_druns);
         if (n_druns > PP.DRUN_MAX && nqa > 1) return n_druns;
         if (n_druns > drun_cap) {
             if (n_druns >= (1ull << 32)) fail(UC_ERR_GENERIC, "%u distinct k-mers of query %u produce %llu index ranges", nd, SB.begin, (unsigned long long)n_druns);
@@ -1794,7 +1793,7 @@ static PlanResult plan_superbatch(Engine &E, PrefilterPass &PP, SuperBatch &SB, 
     UC_HIP(hipMemsetAsync(S.d_counters.p, 0, 8, E.stream));
     UC_HIP(hipMemsetAsync(S.d_nr.p + NP, 0, 4, E.stream));
     UC_HIP(hipMemsetAsync(S.d_ph.p + NP, 0, 4, E.stream));
-    hipLaunchKernelGGL(position_runs_kernel, grid_for(NP), dim3(256), 0, E.stream, S.d_qk.p, NP, S.d_kid.p, S.d_rec.p, S.d_nr.p, S.d_src.p, S.d_ph.p, S.d_counters.p);
+    hipLaunchKernelGGL(position_runs_kernel, grid_for(NP, E.count_grid_cap), dim3(256), 0, E.stream, S.d_qk.p, NP, S.d_kid.p, S.d_rec.p, S.d_nr.p, S.d_src.p, S.d_ph.p, S.d_counters.p);
     auto hin = rocprim::make_transform_iterator(S.d_ph.p, WidenU32());
     auto rin = rocprim::make_transform_iterator(S.d_nr.p, WidenU32());
     rocprim_call(S.d_temp, [&](void *t, size_t &b) { return rocprim::exclusive_scan(t, b, hin, S.d_cumh.p, (uint64_t)0, (size_t)NP + 1, rocprim::plus<uint64_t>(), E.stream); });
@@ -1963,7 +1962,8 @@ static uint64_t select_diagonals(Engine &E, PrefilterPass &PP, const QueryBatch 
         UC_HIP(hipMemsetAsync(S.d_counters.p + 6, 0, 8, E.stream));
         if (B.n_sort) {
             S.d_wflag.reserve((B.n_sort + 63) / 64 + 64);
-            hipLaunchKernelGGL(diag_select_kernel, grid_for(B.n_sort), dim3(256), 0, E.stream, B.sorted, B.n_sort, E.p.min_diag_hits, PP.fmt, B.qa,
+            // every wave ends on one returning atomic on the candidate cursor (its last, partial stage): the capped grid bounds them
+            hipLaunchKernelGGL(diag_select_kernel, grid_for(B.n_sort, E.count_grid_cap), dim3(256), 0, E.stream, B.sorted, B.n_sort, E.p.min_diag_hits, PP.fmt, B.qa,
                                S.d_counters.p + 6, PP.cand_cap, S.d_cq.p, S.d_ct.p, S.d_cd.p, PP.mirror_q0, S.d_wflag.p);
             hipLaunchKernelGGL(diag_long_kernel, grid_for((B.n_sort + 63) / 64), dim3(256), 0, E.stream, B.sorted, B.n_sort, E.p.min_diag_hits, PP.fmt, B.qa,
                                S.d_counters.p + 6, PP.cand_cap, S.d_cq.p, S.d_ct.p, S.d_cd.p, PP.mirror_q0, (const uint8_t *)S.d_wflag.p);
@@ -1972,6 +1972,8 @@ static uint64_t select_diagonals(Engine &E, PrefilterPass &PP, const QueryBatch 
         UC_HIP(hipMemcpyAsync(&nc, S.d_counters.p + 6, 8, hipMemcpyDeviceToHost, E.stream));
         UC_HIP(hipStreamSynchronize(E.stream));
         if (nc <= PP.cand_cap) {
+            if (getenv("UC_TIMING"))
+                fprintf(stderr, "unicore-cluster[timing]: diagonal selection: %llu candidates of %llu sorted keys, %llu selected on chip\n", nc, (unsigned long long)B.n_sort, (unsigned long long)B.n_rec);
             if (B.n_rec)      // their number is known exactly: no cap, cursor or retry
                 hipLaunchKernelGGL(cand_gather_kernel, grid_for((uint64_t)(B.qb - B.qa) * 64), dim3(256), 0, E.stream, (const uint32_t *)S.d_keys.p, S.d_qbase.p,
                                    S.d_qcand.p, S.d_qmir.p, S.d_coff.p, B.qb - B.qa, PP.fmt, B.qa, (uint64_t)nc, S.d_cq.p, S.d_ct.p, S.d_cd.p);
@@ -2000,7 +2002,7 @@ static void select_and_append(Engine &E, PrefilterPass &PP, uint64_t n_cand) {
     E.timed_ms_begin();
     S.d_skey.reserve(n_cand); S.d_skey2.reserve(n_cand); S.d_cd2.reserve(n_cand);
     UC_HIP(hipMemsetAsync(S.d_counters.p + 1, 0, 8, E.stream));
-    hipLaunchKernelGGL(select_key_kernel, grid_for(n_cand), dim3(256), 0, E.stream, n_cand, S.d_cq.p, S.d_ct.p, S.d_score.p, E.p.min_ungapped, S.d_skey.p, S.d_counters.p + 1);
+    hipLaunchKernelGGL(select_key_kernel, grid_for(n_cand, E.count_grid_cap), dim3(256), 0, E.stream, n_cand, S.d_cq.p, S.d_ct.p, S.d_score.p, E.p.min_ungapped, S.d_skey.p, S.d_counters.p + 1);
     unsigned kb = 33;      // the query field ends below bit 32 + log2(n) + 1: the all-ones key of a dropped candidate still sorts behind every kept one
     while (kb < 64 && (1ull << (kb - 32)) <= E.hdb.n) kb++;
     rocprim_call(S.d_temp, [&](void *t, size_t &b) { return rocprim::radix_sort_pairs(t, b, S.d_skey.p, S.d_skey2.p, S.d_cd.p, S.d_cd2.p, (size_t)n_cand, 0u, kb, E.stream); });
@@ -2432,6 +2434,35 @@ uint64_t Engine::merge_hits_dev(uint64_t n1, const uint32_t *q1, const uint32_t 
     stats.prefilter_kernel_ms += timed_ms_end();
     stats.stage_seconds[UC_ST_SELECT] += tm.seconds();
     return keep;
+}
+
+// E3 and the key pass of E4 on an explicit candidate list, with the launches of rescore_ungapped / select_and_append: the scores, the overlap residues
+// that E3 adds to the stage's algorithmic bytes and the number of candidates E4 keeps (score >= min_score)
+void Engine::ungapped_select(uint64_t n, const uint32_t *q, const uint32_t *t, const int32_t *diag, int min_score, int32_t *score_out,
+                             uint64_t *overlap_out, uint64_t *kept_out) {
+    if (!have_db) fail(UC_ERR_ARGS, "no database loaded");
+    *overlap_out = 0; *kept_out = 0;
+    if (n == 0) return;
+    UC_HIP(hipSetDevice(device));
+    for (uint64_t i = 0; i < n; i++)
+        if (q[i] >= hdb.n || t[i] >= hdb.n) fail(UC_ERR_ARGS, "ungapped_select: sequence id out of range");
+    DevBuf<uint32_t> dq, dt;
+    DevBuf<int32_t> dd, ds;
+    DevBuf<uint64_t> key;
+    DevBuf<unsigned long long> ctr;
+    dq.reserve(n); dt.reserve(n); dd.reserve(n); ds.reserve(n); key.reserve(n); ctr.reserve(2);
+    UC_HIP(hipMemcpyAsync(dq.p, q, n * 4, hipMemcpyHostToDevice, stream));
+    UC_HIP(hipMemcpyAsync(dt.p, t, n * 4, hipMemcpyHostToDevice, stream));
+    UC_HIP(hipMemcpyAsync(dd.p, diag, n * 4, hipMemcpyHostToDevice, stream));
+    UC_HIP(hipMemsetAsync(ctr.p, 0, 16, stream));
+    launch_ungapped(ddb, n, dq.p, dt.p, dd.p, ds.p, ctr.p, stream);
+    hipLaunchKernelGGL(select_key_kernel, grid_for(n, count_grid_cap), dim3(256), 0, stream, n, dq.p, dt.p, ds.p, min_score, key.p, ctr.p + 1);
+    UC_HIP(hipGetLastError());
+    unsigned long long h[2] = {0, 0};
+    UC_HIP(hipMemcpyAsync(h, ctr.p, 16, hipMemcpyDeviceToHost, stream));
+    if (score_out) UC_HIP(hipMemcpyAsync(score_out, ds.p, n * 4, hipMemcpyDeviceToHost, stream));
+    UC_HIP(hipStreamSynchronize(stream));
+    *overlap_out = h[0]; *kept_out = h[1];
 }
 
 void preload_prefilter_module() { hipFuncAttributes fa; (void)hipFuncGetAttributes(&fa, (const void *)kmer_extract_kernel); }

@@ -38,21 +38,15 @@ __device__ __forceinline__ uint32_t ra_wave_slot(bool take, uint32_t *counter) {
 // ctr: [0] edges in the buffer, [1] rejected members, [2] accepted re-search pairs (self pairs dropped), [3] members, [4] malformed entries of A
 // A must be idempotent and in range; a member's key is (representative << 32 | member)
 __global__ void __launch_bounds__(256) ra_key_kernel(uint32_t n, const uint32_t *A, uint64_t *key, uint32_t *ctr) {
-    const uint32_t stride = gridDim.x * 256, n_up = (n + 63) & ~63u;      // whole waves enter the loop: the ballots see every lane
-    for (uint32_t x = blockIdx.x * 256 + threadIdx.x; x < n_up; x += stride) {
-        bool member = false, bad = false;
-        if (x < n) {
-            const uint32_t a = A[x];
-            bad = a >= n || A[a] != a;
-            member = !bad && a != x;
-            key[x] = member ? ((uint64_t)a << 32) | x : RA_NO_KEY;
-        }
-        const unsigned long long mm = __ballot(member), mb = __ballot(bad);
-        if ((threadIdx.x & 63) == 0) {
-            if (mm) atomicAdd(&ctr[3], (uint32_t)__popcll(mm));
-            if (mb) atomicAdd(&ctr[4], (uint32_t)__popcll(mb));
-        }
+    unsigned long long n_member = 0, n_bad = 0;
+    for (uint32_t x = blockIdx.x * 256 + threadIdx.x; x < n; x += gridDim.x * 256) {
+        const uint32_t a = A[x];
+        const bool bad = a >= n || A[a] != a;
+        const bool member = !bad && a != x;
+        key[x] = member ? ((uint64_t)a << 32) | x : RA_NO_KEY;
+        n_member += member; n_bad += bad;
     }
+    block_add2(n_member, n_bad, &ctr[3], &ctr[4]);
 }
 // the sorted member keys are the hit lists: query = representative, target = member, score = diag = 0; the last member of a run finds the
 // run's start (lower bound of representative << 32) and writes the list length
@@ -71,16 +65,17 @@ __global__ void __launch_bounds__(256) ra_lists_kernel(uint64_t nm, const uint64
 }
 // one pass over the records of those lists: the member's flag, the accepted (representative, member) appended to the edge buffer, both counted
 __global__ void __launch_bounds__(256) ra_verdict_kernel(uint64_t nm, const uc_aln *alns, const uint32_t *hq, const uint32_t *ht, uint32_t *rej, uint32_t *edges, uint32_t *ctr) {
-    const uint64_t stride = (uint64_t)gridDim.x * 256, nm_up = (nm + 63) & ~63ull;
+    const uint64_t stride = (uint64_t)gridDim.x * 256, nm_up = (nm + 63) & ~63ull;      // whole waves enter the loop: the ballot of ra_wave_slot sees every lane
+    unsigned long long n_rej = 0;
     for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < nm_up; i += stride) {
         const bool in = i < nm;
         const bool acc = in && alns[i].accepted == 1;
         const uint32_t slot = ra_wave_slot(acc, &ctr[0]);
         if (acc) { edges[2ull * slot] = hq[i]; edges[2ull * slot + 1] = ht[i]; }
         if (in && !acc) rej[ht[i]] = 1u;
-        const unsigned long long mr = __ballot(in && !acc);
-        if (mr && (threadIdx.x & 63) == 0) atomicAdd(&ctr[1], (uint32_t)__popcll(mr));
+        n_rej += in && !acc;
     }
+    block_add(n_rej, &ctr[1]);
 }
 __global__ void __launch_bounds__(256) ra_rep_flag_kernel(uint32_t n, const uint32_t *A, uint32_t *is_rep) {
     for (uint32_t x = blockIdx.x * 256 + threadIdx.x; x < n; x += gridDim.x * 256) is_rep[x] = A[x] == x ? 1u : 0u;
@@ -96,6 +91,7 @@ __global__ void __launch_bounds__(256) ra_seeds_kernel(uint32_t n, const uint32_
 // the accepted pairs of the re-search, local ids of D' -> global ids, appended behind the verified edges (m = sequences of D': bounds the lookup)
 __global__ void __launch_bounds__(256) ra_map_kernel(uint64_t ne, const uint32_t *local, const uint32_t *ids, uint32_t m, uint32_t *edges, uint32_t *ctr) {
     const uint64_t stride = (uint64_t)gridDim.x * 256, ne_up = (ne + 63) & ~63ull;
+    unsigned long long n_take = 0;
     for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < ne_up; i += stride) {
         uint32_t a = 0, b = 0;
         bool take = false;
@@ -105,9 +101,9 @@ __global__ void __launch_bounds__(256) ra_map_kernel(uint64_t ne, const uint32_t
         }
         const uint32_t slot = ra_wave_slot(take, &ctr[0]);
         if (take) { edges[2ull * slot] = a; edges[2ull * slot + 1] = b; }
-        const unsigned long long mt = __ballot(take);
-        if (mt && (threadIdx.x & 63) == 0) atomicAdd(&ctr[2], (uint32_t)__popcll(mt));
+        n_take += take;
     }
+    block_add(n_take, &ctr[2]);
 }
 
 }  // namespace
@@ -133,7 +129,7 @@ void Engine::reassign(const uint32_t *assign_in, uint32_t *assign_out, uint8_t *
     UC_HIP(hipMemsetAsync(S.ctr.p, 0, 8 * 4, s));
     UC_HIP(hipMemsetAsync(S.cnt.p, 0, (size_t)n * 4, s));
     UC_HIP(hipMemsetAsync(S.rej.p, 0, (size_t)n * 4, s));
-    hipLaunchKernelGGL(ra_key_kernel, grid_for(n), dim3(256), 0, s, n, (const uint32_t *)S.assign.p, S.key.p, S.ctr.p);
+    hipLaunchKernelGGL(ra_key_kernel, grid_for(n, count_grid_cap), dim3(256), 0, s, n, (const uint32_t *)S.assign.p, S.key.p, S.ctr.p);
     uint32_t h_ctr[8] = {};
     UC_HIP(hipMemcpyAsync(h_ctr, S.ctr.p, 8 * 4, hipMemcpyDeviceToHost, s));
     UC_HIP(hipStreamSynchronize(s));

@@ -152,10 +152,7 @@ __global__ void __launch_bounds__(256) ungapped_kernel(const DeviceDb db, uint64
         score[c] = min(best, 255);
         ovl += (unsigned long long)max(i1 - i0, 0);
     }
-    if (overlap_sum) {   // algorithmic-byte accounting of stage E3: one atomic per wave
-        for (int o = 32; o > 0; o >>= 1) ovl += __shfl_down(ovl, o, 64);
-        if ((threadIdx.x & 63) == 0 && ovl) atomicAdd(overlap_sum, ovl);
-    }
+    if (overlap_sum) block_add(ovl, overlap_sum);   // algorithmic-byte accounting of stage E3 (a kernel argument: the whole workgroup takes the branch)
 }
 
 void launch_ungapped(const DeviceDb &db, uint64_t n, const uint32_t *q, const uint32_t *t, const int32_t *diag,
