@@ -628,7 +628,7 @@ def test_per_query_threshold_table_rule(O, small, tmp_path):
 
 
 def test_device_set_cover_equals_the_sequential_rule(O):
-    """E7 runs on the GPU as parallel rounds of local maxima (uc_align.hip: set_cover_graph): the assignment must be the sequential
+    """E7 runs on the GPU as parallel rounds of local maxima (uc_cluster_graph.hip: set_cover_graph): the assignment must be the sequential
     greedy rule's (most unassigned nodes first, ties: smallest id) on every graph shape — long paths and rings (one pick per round at the
     front of a count tie: the worst case for the number of rounds), stars, cliques that share members, hub chains, duplicate / self edges,
     isolated nodes — against both the oracle and the all-host product cover"""

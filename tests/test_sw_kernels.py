@@ -14,7 +14,7 @@ import util
 
 pytestmark = pytest.mark.gpu
 
-# the class tables of uc_align.hip (h_tab): row caps and pairs per workgroup task.  The library reports the class of every pair; the sweep
+# the class tables of uc_sw_plan.hip (h_tab): row caps and pairs per workgroup task.  The library reports the class of every pair; the sweep
 # asserts it equals the one computed from these lists, so a change to either side shows up here.
 CAPS = {0: [64, 128, 192, 256, 320, 384, 448, 512, 640, 768, 896, 1024, 1280, 1536, 1792, 2048],
         1: [32, 64, 96, 128, 160, 192, 224, 256, 288, 320, 352, 384, 448, 512, 576, 640, 704, 768, 896, 1024, 1152, 1280, 1408, 1536,

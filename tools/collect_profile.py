@@ -60,7 +60,7 @@ if os.path.exists(sb + "/out_kernel_stats.csv"):
             o.write("bench line of the same run: sw_kernel_ms_per_step %.3f, launches %d, avg_launch_ms %.4f (HIP events on the engine stream)\n"
                     % (d["sw_kernel_ms_per_step"], d["roofline"]["launches"], d["roofline"]["avg_launch_ms"]))
         o.write(subprocess.run([sys.executable, os.path.join(ROOT, "tools", "sw_class_times.py"), os.path.relpath(sb, ROOT)], cwd=ROOT, capture_output=True, text=True).stdout)
-# prefilter traffic (everything that is not a gapped-SW / set-cover / planner kernel of uc_align.hip)
+# prefilter traffic (everything that is not a gapped-SW / set-cover / planner kernel of uc_sw_plan.hip, uc_align.hip, uc_traceback.hip, uc_cluster_graph.hip)
 PRE = ("kmer_extract", "kmer_offsets", "sim_runs", "filter_kernel", "run_range", "run_order", "compact_kernel", "diag_select", "ungapped_kernel", "select_key", "rank_flag",
        "hit_scatter", "hit_count", "expand_kernel", "query_kmer", "distinct_kmer", "rank_offsets", "rank_rec", "position_runs", "query_totals", "position_expand")
 pt = {}

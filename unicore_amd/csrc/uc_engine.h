@@ -184,7 +184,15 @@ uint64_t ungapped_all_candidates(Engine &E, const UngappedAllWork &W, uint32_t q
 // ---- E7: the clustering graph on the device and the work buffers of the greedy incremental rule (--cluster-mode 2, uc_greedy_inc.hip) ----
 // CSR of the undirected graph on the accepted pairs: node v's neighbours are adj[off[v] .. off[v + 1]), ascending, unique, no self loops
 struct DevGraph { const uint64_t *off = nullptr; const uint32_t *adj = nullptr; uint64_t n_adj = 0; };
-// kept in the engine's AlignScratch beside the sc_* buffers of the set cover, so that a warm call allocates nothing
+// the graph build and the greedy set cover (uc_cluster_graph.hip): build_cluster_graph fills e .. doff (the CSR arrays doff / dadj are what the
+// other two rules read through DevGraph), set_cover_graph the round state assign .. m1
+struct SetCoverScratch {
+    DevBuf<uint32_t> e, flag, pos, dadj, bad, assign, cnt, work, work2, picks, newly, ctr;
+    DevBuf<uint64_t> m1;
+    DevBuf<uint64_t> key, key2, ukey, doff;
+    DevBuf<char> tmp;
+};
+// kept in the engine's AlignScratch beside the set cover's buffers, so that a warm call allocates nothing
 struct GreedyIncScratch {
     DevBuf<uint64_t> key, key2;                           // (length descending, id ascending) sort keys
     DevBuf<uint32_t> order, rank, state, work, work2, ctr, assign, err, tail_id, tail_rep;
@@ -200,9 +208,9 @@ struct ReassignScratch {
 
 struct PrefilterScratch;                                  // uc_prefilter.hip
 void free_scratch(PrefilterScratch *p);
-struct AlignScratch;                                      // uc_align.hip
+struct AlignScratch;                                      // uc_align_internal.h
 void free_scratch(AlignScratch *p);
-bool release_tb_matrices(AlignScratch *p);   // the traceback-byte buffer, unless a MODE 7 batch loop is using it right now (uc_align.hip)
+bool release_tb_matrices(AlignScratch *p);   // the traceback-byte buffer, unless a MODE 7 batch loop is using it right now (uc_traceback.hip)
 
 // A destroyed engine parks its work buffers here (one set per device) and the next engine of the process takes them
 // over: freeing and re-allocating tens of GB between two uc_cluster calls is usually free, but now and then the next
@@ -346,10 +354,9 @@ struct Engine {
     void set_cover_own_edges(uint32_t n, uint32_t *assign);   // the engine's own (device-resident) edge list
     void set_cover_graph(uint32_t n, const uint32_t *h_edges, const uint32_t *dev_edges, uint64_t n_edges, uint32_t *assign);
     // the graph build both clustering rules share (n_edges > 0; from a host or a device edge list), and the subgraph that the undecided nodes
-    // (mark[v] == 0xFFFFFFFF) of a work list induce, renumbered by ascending id, for a host finish          (uc_align.hip)
+    // (mark[v] == 0xFFFFFFFF) of a work list induce, renumbered by ascending id, for a host finish          (uc_cluster_graph.hip)
     DevGraph build_cluster_graph(uint32_t n, const uint32_t *h_edges, const uint32_t *dev_edges, uint64_t n_edges);
     void induced_subgraph(const DevGraph &G, uint32_t left, const uint32_t *d_work, const uint32_t *d_mark, std::vector<uint32_t> &back, std::vector<uint32_t> &e2);
-    GreedyIncScratch &greedy_inc_scratch();
     // rule UC-1/G (--cluster-mode 2): greedy incremental clustering of the resident database's n sequences on the device     (uc_greedy_inc.hip)
     void greedy_inc_graph(uint32_t n, const uint32_t *h_edges, const uint32_t *dev_edges, uint64_t n_edges, uint32_t *assign);
     // E7 by rule (0 = set cover, 2 = greedy incremental) from a host edge list, and by p.cluster_mode from a device edge list (n_edges < 2^31)
@@ -359,7 +366,6 @@ struct Engine {
     // its representative, the rejected ones searched again against representatives + rejected, the run's clustering rule on what was accepted.
     // rejected_out (nullable): n flags; counts: members verified, rejected, accepted re-search pairs (self pairs dropped), final clusters      (uc_reassign.hip)
     void reassign(const uint32_t *assign_in, uint32_t *assign_out, uint8_t *rejected_out, uint64_t counts[4]);
-    ReassignScratch &reassign_scratch();
     // E8a: (centre, member) candidate pairs of the linear-time pre-step for the resident DB, sorted by (centre, member), unique (uc_linclust.hip)
     // m_override > 0 replaces p.kmer_per_seq for this call (kernel-level tests: one engine serves every m)
     std::vector<uint32_t> linclust_pairs(int m_override = 0);

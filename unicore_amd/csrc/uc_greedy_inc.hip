@@ -2,7 +2,7 @@
 // The sequential rule (uc_setcover.cpp: greedy_incremental) walks the nodes by rank - length descending, ties by ascending id - and makes every node
 // that is still unassigned a representative that takes its unassigned neighbours.  Equivalently: the representatives are the lexicographically first
 // maximal independent set in rank order, and every other node belongs to its representative neighbour of the SMALLEST rank.  That form runs in parallel
-// rounds over a work list of undecided nodes, a wave per node like the set cover's rounds (uc_align.hip):
+// rounds over a work list of undecided nodes, a wave per node like the set cover's rounds (uc_cluster_graph.hip):
 //   (a) an undecided node whose lower-rank neighbours are all MEMBER becomes REP          (gi_rep_kernel)
 //   (b) an undecided node with a REP neighbour becomes MEMBER, the others are kept         (gi_member_kernel: decision and compaction in one pass)
 // and after ALL rounds assign[v] = the REP neighbour of the smallest rank (gi_assign_kernel): a representative of lower rank may be decided in a later
@@ -17,7 +17,7 @@
 
 #include <rocprim/rocprim.hpp>
 
-#include "uc_engine.h"
+#include "uc_align_internal.h"
 
 namespace uc {
 
@@ -93,7 +93,7 @@ void Engine::greedy_inc_graph(uint32_t n, const uint32_t *h_edges, const uint32_
     const DevGraph G = build_cluster_graph(n, h_edges, dev_edges, n_edges);
     const bool timing = getenv("UC_TIMING") != nullptr;
     Timer t_rounds;
-    GreedyIncScratch &S = greedy_inc_scratch();
+    GreedyIncScratch &S = scratch_of(*this).gi;
     S.key.reserve(n); S.key2.reserve(n); S.order.reserve(n); S.rank.reserve(n); S.state.reserve(n); S.work.reserve(n); S.work2.reserve(n);
     S.ctr.reserve(4); S.assign.reserve(n); S.err.reserve(1);
     hipLaunchKernelGGL(gi_key_kernel, grid_for(n), dim3(256), 0, stream, n, (const uint32_t *)d_len.p, S.key.p);

@@ -1871,7 +1871,7 @@ static QueryBatch cut_batch(Engine &E, PrefilterPass &PP, const SuperBatch &SB, 
 }
 
 // n > 0 counts (0/1 flags, survivors per query) -> their exclusive scan in u64 positions (where each entry's share goes) -> the total (one host
-// synchronisation, the u64 form of uc_align.hip's compact(); it also fetches the u32 at `also` for a caller that has one more value to read)
+// synchronisation, the u64 form of uc_sw_plan.hip's compact(); it also fetches the u32 at `also` for a caller that has one more value to read)
 static uint64_t compact_u64(Engine &E, DevBuf<char> &tmp, uint32_t *cnt, uint64_t *pos, uint64_t n, const uint32_t *also = nullptr, uint32_t *also_out = nullptr) {
     auto in = rocprim::make_transform_iterator(cnt, WidenU32());
     rocprim_call(tmp, [&](void *t, size_t &b) { return rocprim::exclusive_scan(t, b, in, pos, (uint64_t)0, (size_t)n, rocprim::plus<uint64_t>(), E.stream); });

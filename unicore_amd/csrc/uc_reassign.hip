@@ -17,7 +17,7 @@
 
 #include <rocprim/rocprim.hpp>
 
-#include "uc_engine.h"
+#include "uc_align_internal.h"
 
 namespace uc {
 
@@ -121,7 +121,7 @@ void Engine::reassign(const uint32_t *assign_in, uint32_t *assign_out, uint8_t *
     double ms_lists = 0, ms_verify = 0, ms_verdict = 0, ms_research = 0, ms_cluster = 0;
     auto lap = [&](double &acc) { acc += t_part.seconds() * 1e3; t_part = Timer(); };
     hipStream_t s = stream;
-    ReassignScratch &S = reassign_scratch();
+    ReassignScratch &S = scratch_of(*this).ra;
 
     // ---- 1: member lists from A
     S.assign.reserve(n); S.key.reserve(n); S.key2.reserve(n); S.ctr.reserve(8); S.cnt.reserve(n); S.rej.reserve(n);

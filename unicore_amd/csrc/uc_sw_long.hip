@@ -16,7 +16,7 @@
 namespace uc {
 
 constexpr int LONG_G = 64;
-constexpr int LONG_NW = (int)SW_LONG_TASK_PAIRS;   // waves (= pairs) per workgroup; uc_align.hip cuts the long-query tasks to this size
+constexpr int LONG_NW = (int)SW_LONG_TASK_PAIRS;   // waves (= pairs) per workgroup; uc_sw_plan.hip cuts the long-query tasks to this size
 constexpr int long_rows_per_lane(int mode) { return mode == 3 ? 16 : 32; }   // MODE 3 carries two more register arrays
 
 template <int MODE>

@@ -65,7 +65,7 @@ __global__ void __launch_bounds__(NW * 64) sw_pk_kernel(const SwArgs a) {
     // end position every cell of the diagonal band the traceback can reach (tb_band_of, uc_device.h; r05) stores ONE byte, H mod 256,
     // into a per-pair matrix in HBM, laid out by anti-diagonal step so that the lanes inside the band store NL*RB contiguous bytes per step.  No decision is computed here (r04: six compare bits per
     // cell had cost 16 of the pass's 27 VALU instructions per row and step; a byte of H costs the byte shuffle only).  A
-    // second kernel (tb_walk_kernel, uc_align.hip) walks every pair's matrix from the end cell, whose H it knows (the
+    // second kernel (tb_walk_kernel, uc_sw_plan.hip) walks every pair's matrix from the end cell, whose H it knows (the
     // score): neighbouring cells differ by less than 128, so every H it needs is exact again, and every decision of the
     // traceback (diagonal / F / E, gap opened or extended) is a comparison of H values: alignment length, identities, gaps.
     constexpr bool TBB = MODE == 7;
@@ -465,7 +465,7 @@ void launch_sw_pk_class_mode(int G, int R, const SwArgs &a, uint32_t n_tasks, hi
 #define UC_SW_CASE(GG, RR)                                                                              \
     if (G == GG && R == RR) {                                                                           \
         constexpr int BW = (((RR + 3) / 4) | 1);                                                        \
-        /* small workgroups share one LDS profile; G = 64 with R < 14: the wave-wide classes of sparse known-score plans (table 3 of uc_align.hip) */ \
+        /* small workgroups share one LDS profile; G = 64 with R < 14: the wave-wide classes of sparse known-score plans (table 3 of uc_sw_plan.hip) */ \
         constexpr int NW = GG == 16 ? 2 : (GG == 32 ? 4 : (RR < 14 ? 2 : 8));                           \
         const size_t lds = (size_t)2 * SW_NLET * GG * BW * 4 + 16;                                      \
         static PerDeviceOnce once;                                                                      \
