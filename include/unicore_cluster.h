@@ -192,7 +192,8 @@ int uc_engine_hits_get(const uc_engine *e, uint32_t *counts, uc_hit *hits);
 /* the same for the queries [qbegin,qend) only: counts may be NULL; hits must hold the sum of their counts (at BASELINE
  * configs[2] scale the whole list is gigabytes, a sample of queries is not) */
 int uc_engine_hits_get_range(const uc_engine *e, uint32_t qbegin, uint32_t qend, uint32_t *counts, uc_hit *hits);
-/* replace the engine's hit lists (counts[n_seqs] + flat hits grouped by query) */
+/* replace the engine's hit lists (counts[n_seqs] + flat hits grouped by query).  A list names a target once (spec E4): UC_ERR_ARGS for a
+ * list that repeats one - the gapped stage would take the second entry for the mirror (t, q) of the first.  A refused list changes nothing. */
 int uc_engine_hits_set(uc_engine *e, const uint32_t *counts, const uc_hit *hits);
 /* replace the engine's hit lists by the merge of n_parts shard lists (each: counts[n_seqs] + flat hits),
  * keeping per query the top max_seqs under the frozen order (score desc, target asc) */

@@ -299,7 +299,7 @@ void uco_simd_align_pairs(const uco_db *db, const uint32_t *pairs, uint64_t np, 
             const uint32_t q = pairs[2 * b];
             if (e - b > cap) { cap = (size_t)(e - b) * 2; tg = (uint32_t *)realloc(tg, cap * sizeof(uint32_t)); }
             for (uint64_t k = b; k < e; k++) tg[k - b] = pairs[2 * k + 1];
-            const int32_t ms = uco_min_score(p, (int)(db->off[q + 1] - db->off[q]), dbres);
+            const int32_t ms = uco_min_score_q(p, q, (int)(db->off[q + 1] - db->off[q]), dbres);       /* rule UC-1/E: the table's entry if one is set */
             uco_simd_align_query(db, q, tg, (uint32_t)(e - b), p, ms, out + b);
         }
         free(tg);

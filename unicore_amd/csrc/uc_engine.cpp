@@ -245,20 +245,28 @@ void Engine::ungapped_batch(uint64_t n, const uint32_t *q, const uint32_t *t, co
 void Engine::set_hits(const uint32_t *counts, const uc_hit *h, bool check_max_seqs) {
     const uint32_t n = hdb.n;
     UC_HIP(hipSetDevice(device));
-    hit_cnt.assign(counts, counts + n);
-    hit_off.assign((size_t)n + 1, 0);
+    // the list is checked as a whole before the engine takes any of it: a refused list leaves the installed one as it was
+    std::vector<uint64_t> off((size_t)n + 1, 0);
     for (uint32_t i = 0; i < n; i++) {
         if (check_max_seqs && counts[i] > (uint32_t)p.max_seqs) fail(UC_ERR_ARGS, "hit list of query %u longer than max_seqs", i);
-        hit_off[i + 1] = hit_off[i] + counts[i];
+        off[i + 1] = off[i] + counts[i];
     }
-    n_hits = hit_off[n];
-    std::vector<uint32_t> hq(n_hits), ht(n_hits);
-    std::vector<int32_t> hs(n_hits), hd(n_hits);
+    const uint64_t nh = off[n];
+    std::vector<uint32_t> hq(nh), ht(nh);
+    std::vector<int32_t> hs(nh), hd(nh);
+    // a list names a target once (spec E4): the gapped stage keys mutual hits by the unordered pair, so a repeated (q, t) would be taken for
+    // the mirror (t, q) of its first entry and be given a transposed record.  stamp[t] = 1 + the last query that listed t
+    std::vector<uint32_t> stamp(nh ? n : 0, 0);
     for (uint32_t q = 0; q < n; q++)
-        for (uint64_t k = hit_off[q]; k < hit_off[q + 1]; k++) {
+        for (uint64_t k = off[q]; k < off[q + 1]; k++) {
             if (h[k].target >= n) fail(UC_ERR_ARGS, "hit target out of range");
+            if (stamp[h[k].target] == q + 1) fail(UC_ERR_ARGS, "hit list of query %u names target %u more than once", q, h[k].target);
+            stamp[h[k].target] = q + 1;
             hq[k] = q; ht[k] = h[k].target; hs[k] = h[k].score; hd[k] = h[k].diag;
         }
+    hit_cnt.assign(counts, counts + n);
+    hit_off.swap(off);
+    n_hits = nh;
     const size_t cap = std::max<uint64_t>(n_hits, 1);
     d_hq.reserve(cap); d_ht.reserve(cap); d_hs.reserve(cap); d_hd.reserve(cap);
     if (n_hits) {
