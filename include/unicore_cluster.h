@@ -371,6 +371,50 @@ typedef struct uc_tree_stats {
 int uc_tree(const char *db_prefix, const char *profile_dir, const char *out_dir, uint32_t threshold, const char *aligner_options, const uc_opts *o,
             uc_tree_stats *stats_out);
 
+/* ---- the built-in tree builder `nj` (rule UC-N): pairwise protein distances over an aligned FASTA and neighbour joining (Saitou-Nei
+ * with the Studier-Keppler criterion), the inference step of `unicore tree -t nj` and `unicore gene-tree -t nj` (tree.rs:139-161 and genetree.rs hand it
+ * to an external program).  Every output is defined bit for bit; every host function (no device needed) has a _dev sibling that runs the HIP kernels
+ * of uc_nj.hip on `device` (-1 = the current one) and gives the same integers and the same fp64 bits.  Limits, all UC_ERR_ARGS before the device is
+ * touched: 2 <= n <= 16384, 1 <= w < 2^31.
+ * uc_nj_counts (UC-N/D): cells is n rows of w bytes, row-major.  A cell is informative iff it is an ASCII letter other than X / x; letters compare
+ *   case-insensitively.  comp / diff [n (n - 1) / 2], (i, j) with i < j at i n - i (i + 1) / 2 + (j - i - 1): the columns where both cells are
+ *   informative, and those of them where the letters differ.  threads: host threads of the host twin (0 = 1); the device side reads
+ *   UC_TREE_BUDGET_BYTES (default 512 MiB) per call and serves n x w beyond it in column slices (results do not depend on it).
+ * uc_nj_distances: p = diff / comp; model 0 (kimura): t = 1 - p - 0.2 p p, d = 5 if comp == 0 or t <= 0, else min(5, -log(t)); model 1 (p): d = p, or 5
+ *   if comp == 0.  D [n x n] fp64, symmetric, 0 on the diagonal.
+ * uc_nj_join (UC-N/J): D is not modified.  join_a / join_b / len_a / len_b [n - 3]: step s joins the nodes in slots i < j (leaves are nodes 0 .. n - 1,
+ *   step s creates node n + s) at lengths len_a / len_b; root_node / root_len [3]: the trifurcation (n == 2: both leaves at half their distance, the
+ *   third entry UC_NJ_NO_NODE / 0).  No length is negative or -0.0.
+ * uc_nj_newick: names [n] NUL-terminated; one line `(A:la,B:lb,C:lc);\n`, children in record order, lengths %.6f, a name holding any of ()[]:;,' or
+ *   white space in single quotes with ' doubled.  need (optional) receives the length without the NUL; buf may be NULL with cap 0 to ask for it; a
+ *   buffer that is too small (cap < need + 1) is UC_ERR_ARGS.
+ * uc_nj_geometry: the tile height (rows) and the LDS column chunk of the count kernel. */
+#define UC_NJ_NO_NODE 0xffffffffu
+#define UC_NJ_MODEL_KIMURA 0
+#define UC_NJ_MODEL_P 1
+int uc_nj_counts(uint32_t n, uint64_t w, const uint8_t *cells, uint32_t threads, uint32_t *comp, uint32_t *diff);
+int uc_nj_counts_dev(int32_t device, uint32_t n, uint64_t w, const uint8_t *cells, uint32_t threads, uint32_t *comp, uint32_t *diff);
+int uc_nj_distances(const uint32_t *comp, const uint32_t *diff, uint32_t n, uint32_t model, double *D);
+int uc_nj_join(uint32_t n, const double *D, uint32_t *join_a, uint32_t *join_b, double *len_a, double *len_b, uint32_t *root_node, double *root_len);
+int uc_nj_join_dev(int32_t device, uint32_t n, const double *D, uint32_t *join_a, uint32_t *join_b, double *len_a, double *len_b, uint32_t *root_node,
+                   double *root_len);
+int uc_nj_newick(const char *const *names, uint32_t n, const uint32_t *join_a, const uint32_t *join_b, const double *len_a, const double *len_b,
+                 const uint32_t *root_node, const double *root_len, char *buf, uint64_t cap, uint64_t *need);
+int uc_nj_geometry(uint32_t *tile_rows, uint32_t *chunk_columns);
+/* == the inference step of `unicore tree -t nj`: reads the aligned FASTA msa_fasta (any line wrapping; a name ends at the first white space; a duplicate
+ * or empty name is UC_ERR_IO; rows of unequal width are UC_ERR_ARGS), counts on o->device, transforms under `model` ("kimura", "p"; NULL = kimura;
+ * anything else UC_ERR_ARGS), joins and writes the Newick line to out_nwk.  UC_TREE_HOST=1 (read per call) runs the host twins and needs no GPU;
+ * UC_TREE_DUMP=1 also writes <out_nwk>.dist.tsv (i, j, comp, diff, d as %.17g).  o->verbosity is Unicore's own 0..4 scale. */
+#define UC_NJ_NPHASE 5
+typedef struct uc_nj_stats {
+    uint64_t n_rows, n_columns;
+    uint64_t n_pairs_incomparable;       /* comp == 0 */
+    uint64_t n_pairs_capped;             /* d == 5.0 */
+    uint64_t n_lengths_clamped;          /* branch lengths stored as 0 */
+    double seconds[UC_NJ_NPHASE];        /* host wall: [0] reading, [1] counts, [2] transform, [3] joins, [4] writing */
+} uc_nj_stats;
+int uc_tree_infer(const char *msa_fasta, const char *out_nwk, const char *model, const uc_opts *o, uc_nj_stats *stats_out);
+
 /* ---- kernel-level entry points (parity tests call the HIP kernels through these) -------------- */
 /* ungapped diagonal score (E3) for n candidates (q[i], t[i], diag[i]) of the engine's DB */
 int uc_engine_ungapped_batch(uc_engine *e, uint64_t n, const uint32_t *q, const uint32_t *t,

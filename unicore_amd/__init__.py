@@ -51,6 +51,15 @@ class UcTreeStats(C.Structure):
 TREE_PHASES = ("read", "pair_scores", "centres", "centre_alignments", "layout_render_filter", "write", "total")
 
 
+class UcNjStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("n_rows", "n_columns", "n_pairs_incomparable", "n_pairs_capped", "n_lengths_clamped")] + [("seconds", C.c_double * 5)]
+
+
+NJ_PHASES = ("read", "counts", "transform", "join", "write")
+NJ_MODELS = {"kimura": 0, "p": 1}
+NJ_NO_NODE = 0xFFFFFFFF  # == UC_NJ_NO_NODE: the third root entry of a two-leaf tree
+
+
 class UcT5Stats(C.Structure):
     _fields_ = [("n_seqs", C.c_uint64), ("n_tokens", C.c_uint64), ("flops", C.c_double), ("gpu_ms", C.c_double),
                 ("n_replicas", C.c_uint32), ("reserved0", C.c_uint32), ("gpu_ms_sum", C.c_double),
@@ -76,6 +85,7 @@ SYMBOLS = (
     "uc_cluster_graph", "uc_engine_cluster_graph", "uc_engine_reassign", "uc_engine_td_onchip", "uc_engine_linclust_pairs",
     "uc_profile_count", "uc_profile_count_dev", "uc_profile",
     "uc_msa_center", "uc_msa_center_dev", "uc_msa_star", "uc_msa_star_dev", "uc_msa_filter", "uc_msa_filter_dev", "uc_tree",
+    "uc_nj_counts", "uc_nj_counts_dev", "uc_nj_distances", "uc_nj_join", "uc_nj_join_dev", "uc_nj_newick", "uc_nj_geometry", "uc_tree_infer",
 )
 NO_GENE = 0xFFFFFFFF  # == UC_NO_GENE: a TSV row whose gene name is not in the map
 ABI_VERSION = 9      # == UC_ABI_VERSION of include/unicore_cluster.h this binding mirrors
@@ -162,6 +172,14 @@ def lib():
     L.uc_msa_filter.argtypes = [u32, vp, vp, vp, u32, vp, vp, vp]
     L.uc_msa_filter_dev.argtypes = [i32] + L.uc_msa_filter.argtypes
     L.uc_tree.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, u32, C.c_char_p, C.POINTER(UcOpts), C.POINTER(UcTreeStats)]
+    L.uc_nj_counts.argtypes = [u32, u64, vp, u32, vp, vp]
+    L.uc_nj_counts_dev.argtypes = [i32] + L.uc_nj_counts.argtypes
+    L.uc_nj_distances.argtypes = [vp, vp, u32, u32, vp]
+    L.uc_nj_join.argtypes = [u32] + [vp] * 7
+    L.uc_nj_join_dev.argtypes = [i32] + L.uc_nj_join.argtypes
+    L.uc_nj_newick.argtypes = [C.POINTER(C.c_char_p), u32] + [vp] * 6 + [vp, u64, C.POINTER(u64)]
+    L.uc_nj_geometry.argtypes = [C.POINTER(u32), C.POINTER(u32)]
+    L.uc_tree_infer.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(UcOpts), C.POINTER(UcNjStats)]
     L.uc_engine_ungapped_batch.argtypes = [vp, u64, vp, vp, vp, vp]
     L.uc_engine_ungapped_select.argtypes = [vp, u64, vp, vp, vp, C.c_int32, vp, vp, vp]
     L.uc_engine_ungapped_all.argtypes = [vp, u32, u32, u32, u32, u64, vp, vp]
@@ -401,6 +419,87 @@ def tree(db, profile_dir, out_dir, threshold=50, aligner_options="", verbosity=1
     _check(lib().uc_tree(db.encode(), profile_dir.encode(), out_dir.encode(), threshold, (aligner_options or "").encode(), C.byref(o), C.byref(st)))
     d = {k: int(getattr(st, k)) for k, _ in UcTreeStats._fields_ if k != "seconds"}
     d["seconds"] = dict(zip(TREE_PHASES, st.seconds))
+    return d
+
+
+def nj_geometry():
+    """The count kernel's geometry (uc_nj_geometry): {"tile": rows of a pair tile, "chunk": columns staged through LDS at a time}."""
+    t, c = C.c_uint32(), C.c_uint32()
+    _check(lib().uc_nj_geometry(C.byref(t), C.byref(c)))
+    return {"tile": t.value, "chunk": c.value}
+
+
+def nj_counts(cells, device=None, threads=1):
+    """UC-N/D (uc_nj_counts / uc_nj_counts_dev): cells is n rows of w bytes (a 2-D uint8 array, or a list of equally long byte strings).  Returns
+    (comp, diff), uint32 over the packed upper triangle (i < j at i n - i (i + 1) / 2 + (j - i - 1)): the columns where both cells are informative
+    (an ASCII letter other than X / x) and those of them where the letters differ, case folded.  device as in msa_center; threads: the host twin's."""
+    if isinstance(cells, (list, tuple)):
+        if len({len(r) for r in cells}) > 1:
+            raise ValueError("rows of unequal width")
+        cells = np.frombuffer(b"".join(bytes(r) for r in cells), np.uint8).reshape(len(cells), -1) if cells else np.zeros((0, 0), np.uint8)
+    ce = np.ascontiguousarray(cells, np.uint8)
+    if ce.ndim != 2:
+        raise ValueError("cells is n rows x w columns")
+    n, w = ce.shape
+    tri = max(n * (n - 1) // 2, 1)
+    comp, diff = np.zeros(tri, np.uint32), np.zeros(tri, np.uint32)
+    args = [n, w, _ptr(ce), threads, comp.ctypes.data, diff.ctypes.data]
+    _check(lib().uc_nj_counts(*args) if device is None else lib().uc_nj_counts_dev(device, *args))
+    return comp[: n * (n - 1) // 2], diff[: n * (n - 1) // 2]
+
+
+def nj_distances(comp, diff, n, model="kimura"):
+    """uc_nj_distances (host only): the n x n fp64 distance matrix of the counts under `model` ("kimura": min(5, -log(1 - p - 0.2 p p)), "p": p;
+    5 where nothing compares).  An unknown model is UC_ERR_ARGS."""
+    co, di = np.ascontiguousarray(comp, np.uint32), np.ascontiguousarray(diff, np.uint32)
+    if len(co) != len(di) or (2 <= n <= 16384 and len(co) != n * (n - 1) // 2):
+        raise ValueError("comp and diff hold n (n - 1) / 2 entries each")
+    if model not in NJ_MODELS:
+        raise UcError(UC_ERR_ARGS, "nj: unknown model '%s' (kimura, p)" % model)
+    D = np.zeros((max(n, 1), max(n, 1)), np.float64)
+    _check(lib().uc_nj_distances(_ptr(co), _ptr(di), n, NJ_MODELS[model], D.ctypes.data))
+    return D
+
+
+def nj_join(D, device=None):
+    """UC-N/J (uc_nj_join / uc_nj_join_dev): neighbour joining on the symmetric n x n fp64 matrix D (not modified).  Returns a dict: join_a, join_b
+    (uint32, n - 3: the nodes joined by every step; leaves are 0 .. n - 1, step s creates node n + s), len_a, len_b (fp64), root_node [3],
+    root_len [3] (n == 2: two entries, the third NJ_NO_NODE / 0).  device as in msa_center."""
+    d = np.ascontiguousarray(D, np.float64)
+    if d.ndim != 2 or d.shape[0] != d.shape[1]:
+        raise ValueError("D is n x n")
+    n = d.shape[0]
+    steps = max(n - 3, 0)
+    ja, jb = np.zeros(max(steps, 1), np.uint32), np.zeros(max(steps, 1), np.uint32)
+    la, lb = np.zeros(max(steps, 1), np.float64), np.zeros(max(steps, 1), np.float64)
+    rn, rl = np.zeros(3, np.uint32), np.zeros(3, np.float64)
+    args = [n, _ptr(d), ja.ctypes.data, jb.ctypes.data, la.ctypes.data, lb.ctypes.data, rn.ctypes.data, rl.ctypes.data]
+    _check(lib().uc_nj_join(*args) if device is None else lib().uc_nj_join_dev(device, *args))
+    return {"join_a": ja[:steps], "join_b": jb[:steps], "len_a": la[:steps], "len_b": lb[:steps], "root_node": rn, "root_len": rl}
+
+
+def nj_newick(names, joins):
+    """uc_nj_newick (host only): the tree of nj_join's dict over the leaf names (str or bytes) as one Newick line with its newline (str)."""
+    nm = [x if isinstance(x, bytes) else x.encode() for x in names]
+    arr = (C.c_char_p * max(len(nm), 1))(*nm)
+    a = [np.ascontiguousarray(joins[k], t) for k, t in (("join_a", np.uint32), ("join_b", np.uint32), ("len_a", np.float64), ("len_b", np.float64),
+                                                        ("root_node", np.uint32), ("root_len", np.float64))]
+    need = C.c_uint64()
+    ptrs = [_ptr(x) for x in a]
+    _check(lib().uc_nj_newick(arr, len(nm), *ptrs, None, 0, C.byref(need)))
+    buf = C.create_string_buffer(need.value + 1)
+    _check(lib().uc_nj_newick(arr, len(nm), *ptrs, C.cast(buf, C.c_void_p), need.value + 1, C.byref(need)))
+    return buf.value.decode()
+
+
+def tree_infer(fasta, out, model="kimura", verbosity=1, device=-1, threads=1):
+    """== the inference step of `unicore tree -t nj` (uc_tree_infer): reads the aligned FASTA `fasta`, counts on the device, transforms under
+    `model`, joins and writes the Newick line to `out`.  UC_TREE_HOST=1 in the environment runs the host twins (no GPU needed); UC_TREE_DUMP=1
+    also writes <out>.dist.tsv.  Returns the stats dict (counts and seconds per phase)."""
+    o, st = make_opts("", threads, verbosity, device), UcNjStats()
+    _check(lib().uc_tree_infer(fasta.encode(), out.encode(), None if model is None else model.encode(), C.byref(o), C.byref(st)))
+    d = {k: int(getattr(st, k)) for k, _ in UcNjStats._fields_ if k != "seconds"}
+    d["seconds"] = dict(zip(NJ_PHASES, st.seconds))
     return d
 
 

@@ -1,4 +1,5 @@
-// unicore_main.cpp — C++ host mirror of the reference's `unicore cluster`, `unicore search`, `unicore profile` and `unicore tree --no-inference` module surfaces.
+// unicore_main.cpp — C++ host mirror of the reference's `unicore cluster`, `unicore search`, `unicore profile`, `unicore tree` and `unicore gene-tree` module
+// surfaces (the two tree modules with the built-in builder `nj`; the reference's builders are external programs).
 // (The reference host is Rust; no Rust toolchain exists in this image — SURVEY.md 0.2/D3 — so the host
 // above the C ABI is C++ with the same names, argument meaning and error behaviour.)
 //   CLI surface      /root/reference/src/util/arg_parser.rs:225-246  (Commands::Cluster), :271-293 (Commands::Profile), :296-330 (Commands::Tree)
@@ -12,7 +13,9 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <dirent.h>
 #include <unistd.h>
+#include <algorithm>
 #include <fstream>
 #include <string>
 #include <thread>
@@ -224,17 +227,18 @@ int profile_main(int argc, char **argv) {
 }
 
 void usage_tree(FILE *to) {
-    fputs("Usage: unicore tree [OPTIONS] --no-inference <DB> <INPUT> <OUTPUT>\n\n"
+    fputs("Usage: unicore tree [OPTIONS] <--no-inference|--tree-builder nj> <DB> <INPUT> <OUTPUT>\n\n"
          "Arguments:\n"
          "  <DB>      Input database (createdb output)\n"
          "  <INPUT>   Input directory containing core structures (profile output)\n"
          "  <OUTPUT>  Output directory\n\n"
          "Options:\n"
          "  -a, --aligner <ALIGNER>                  Multiple sequence aligner [star]; foldmason, mafft-linsi and mafft are external programs and are refused [default: star]\n"
-         "  -t, --tree-builder <TREE_BUILDER>        Phylogenetic tree builder [iqtree, fasttree, raxml-ng]; parsed, not run [default: iqtree]\n"
+         "  -t, --tree-builder <TREE_BUILDER>        Phylogenetic tree builder [nj, iqtree, fasttree, raxml-ng]; nj (neighbour joining, built in) writes\n"
+         "                                           <OUTPUT>/nj.nwk; the others are external programs: parsed, not run [default: iqtree]\n"
          "  -o, --aligner-options <ALIGNER_OPTIONS>  Foldseek-style options for the gapped stage behind the star aligner, e.g. -o \"--gap-open 12\"\n"
-         "  -n, --no-inference                       Stop the tree module after alignment (before tree inference); required: inference is not built in\n"
-         "  -p, --tree-options <TREE_OPTIONS>        Options for tree builder; parsed, not used\n"
+         "  -n, --no-inference                       Stop the tree module after alignment (before tree inference); required unless the builder is nj\n"
+         "  -p, --tree-options <TREE_OPTIONS>        Options for tree builder; nj: \"--model kimura|p\" [default: kimura]; parsed, not used for the others\n"
          "  -d, --threshold <THRESHOLD>              Gap threshold for multiple sequence alignment [0 - 100] [default: 50]\n"
          "  -c, --threads <THREADS>                  Number of threads to use; 0 to use all [default: 0]\n"
          "  -v, --verbosity <VERBOSITY>              Verbosity (0: quiet, 1: +errors, 2: +warnings, 3: +info, 4: +debug) [default: 3]\n"
@@ -246,12 +250,37 @@ void usage_tree(FILE *to) {
     exit(CLAP_USAGE);
 }
 
-// Commands::Tree (arg_parser.rs:296-330) + modules::tree::run up to `if no_inference { return }` (tree.rs:17-134): files, tree.chk and messages are
-// uc_tree's, which takes Unicore's own verbosity scale.  The aligner is the built-in centre-star MSA; the reference's aligners and every tree builder
-// are external programs, which this host does not start.
+// the options of the built-in builder: "--model kimura|p" (also --model=...); any other word is refused by name.  Returns the model
+std::string nj_model_of(const std::string &tree_options) {
+    std::vector<std::string> words;
+    for (size_t p = 0; p < tree_options.size();) {
+        while (p < tree_options.size() && isspace((unsigned char)tree_options[p])) p++;
+        const size_t b = p;
+        while (p < tree_options.size() && !isspace((unsigned char)tree_options[p])) p++;
+        if (p > b) words.push_back(tree_options.substr(b, p - b));
+    }
+    std::string model = "kimura";
+    for (size_t k = 0; k < words.size(); k++) {
+        if (words[k] == "--model") {
+            if (k + 1 >= words.size()) error(ERR_GENERAL, "tree builder nj: --model needs a value (kimura, p)");
+            model = words[++k];
+        } else if (words[k].rfind("--model=", 0) == 0) model = words[k].substr(8);
+        else error(ERR_GENERAL, "tree builder nj does not know the option '" + words[k] + "' (--model kimura|p)");
+    }
+    if (model != "kimura" && model != "p") error(ERR_GENERAL, "tree builder nj does not know the model '" + model + "' (kimura, p)");
+    return model;
+}
+
+[[noreturn]] void refuse_external_builder(const std::string &builder) {
+    error(ERR_GENERAL, "tree inference would start the external program " + builder + ", which this build does not do; pass -n/--no-inference and run it on combined.fasta");
+}
+
+// Commands::Tree (arg_parser.rs:296-330) + modules::tree::run (tree.rs:17-161): files, tree.chk and messages up to the concatenation are uc_tree's, which
+// takes Unicore's own verbosity scale.  The aligner is the built-in centre-star MSA and the one builder that runs is the built-in `nj` (uc_tree_infer);
+// the reference's aligners and tree builders are external programs, which this host does not start.
 int tree_main(int argc, char **argv) {
     std::vector<std::string> pos;
-    std::string aligner = "star", builder = "iqtree", aligner_options;
+    std::string aligner = "star", builder = "iqtree", aligner_options, tree_options;
     bool no_inference = false;
     uint32_t threshold = 50;      // arg_parser.rs:322
     int verbosity = 3;
@@ -274,8 +303,8 @@ int tree_main(int argc, char **argv) {
         else if (a.rfind("--tree-builder=", 0) == 0) builder = a.substr(15);
         else if (a == "-o" || a == "--aligner-options") aligner_options = value();
         else if (a.rfind("--aligner-options=", 0) == 0) aligner_options = a.substr(18);
-        else if (a == "-p" || a == "--tree-options") (void)value();
-        else if (a.rfind("--tree-options=", 0) == 0) {}
+        else if (a == "-p" || a == "--tree-options") tree_options = value();
+        else if (a.rfind("--tree-options=", 0) == 0) tree_options = a.substr(15);
         else if (a == "-n" || a == "--no-inference") no_inference = true;
         else if (a == "-d" || a == "--threshold") parse_threshold(value());
         else if (a.rfind("--threshold=", 0) == 0) parse_threshold(a.substr(12));
@@ -292,17 +321,134 @@ int tree_main(int argc, char **argv) {
     if (aligner == "foldmason" || aligner == "mafft" || aligner == "mafft-linsi")      // tree.rs:42-45: ERR_BINARY_NOT_FOUND in the reference
         error(ERR_GENERAL, "aligner " + aligner + " is an external program, which this build does not start; the built-in aligner is 'star'");
     if (aligner != "star") error(ERR_GENERAL, "Unrecognized aligner");                  // tree.rs:118
-    if (builder != "iqtree" && builder != "fasttree" && builder != "raxml-ng") error(ERR_GENERAL, "Unrecognized tree builder");   // tree.rs:146
-    if (!no_inference)
-        error(ERR_GENERAL, "tree inference would start the external program " + builder + ", which this build does not do; pass -n/--no-inference and run it on combined.fasta");
+    const bool nj = builder == "nj";
+    if (!nj && builder != "iqtree" && builder != "fasttree" && builder != "raxml-ng") error(ERR_GENERAL, "Unrecognized tree builder");   // tree.rs:146
+    const std::string model = nj ? nj_model_of(tree_options) : "";
+    if (!no_inference && !nj) refuse_external_builder(builder);
     uc_opts o;
     memset(&o, 0, sizeof o);
     o.struct_size = sizeof o;
     o.threads = 1;
     o.verbosity = verbosity;
     o.device = -1;
-    const int rc = uc_tree(pos[0].c_str(), pos[1].c_str(), pos[2].c_str(), threshold, aligner_options.c_str(), &o, nullptr);
+    int rc = uc_tree(pos[0].c_str(), pos[1].c_str(), pos[2].c_str(), threshold, aligner_options.c_str(), &o, nullptr);
     if (rc != 0) error(ERR_GENERAL, std::string("tree failed with code ") + std::to_string(rc) + "\n" + uc_last_error());
+    if (no_inference) return 0;      // tree.rs:135-137 skips the alignment when combined.fasta exists and infers all the same
+    print_message("Inferring phylogenetic tree...", 3);      // tree.rs:150
+    rc = uc_tree_infer((pos[2] + "/combined.fasta").c_str(), (pos[2] + "/nj.nwk").c_str(), model.c_str(), &o, nullptr);
+    if (rc != 0) error(ERR_GENERAL, std::string("tree inference failed with code ") + std::to_string(rc) + "\n" + uc_last_error());
+    println_message(" Done", 3);
+    write_checkpoint(pos[2] + "/tree.chk", "1");             // tree.rs:161
+    return 0;
+}
+
+void usage_gene_tree(FILE *to) {
+    fputs("Usage: unicore gene-tree [OPTIONS] --tree-builder nj <INPUT>\n\n"
+         "Arguments:\n"
+         "  <INPUT>  Input directory containing species phylogenetic tree (Output of the Tree module)\n\n"
+         "Options:\n"
+         "  -n, --names <NAMES>                      File containing core structures for computing phylogenetic tree; all of them if not given\n"
+         "  -t, -T, --tree-builder <TREE_BUILDER>    Phylogenetic tree builder [nj, iqtree, fasttree, raxml-ng]; nj (neighbour joining, built in) writes\n"
+         "                                           fasta/<gene>/nj.nwk; the others are external programs and are refused [default: iqtree]\n"
+         "  -p, --tree-options <TREE_OPTIONS>        Options for tree builder; nj: \"--model kimura|p\" [default: kimura]\n"
+         "  -f, --realign                            Refused: re-aligning single genes is not built in\n"
+         "  -c, --threads <THREADS>                  Number of threads to use; 0 to use all [default: 0]\n"
+         "  -v, --verbosity <VERBOSITY>              Verbosity (0: quiet, 1: +errors, 2: +warnings, 3: +info, 4: +debug) [default: 3]\n"
+         "  -h, --help                               Print help\n", to);
+}
+
+[[noreturn]] void clap_error_gene_tree(const std::string &what) {
+    fprintf(stderr, "error: %s\n\nUsage: unicore gene-tree [OPTIONS] --tree-builder nj <INPUT>\n\nFor more information, try '--help'.\n", what.c_str());
+    exit(CLAP_USAGE);
+}
+
+// Commands::GeneTree (arg_parser.rs:334-367) + modules::genetree::run (genetree.rs:9-147) with the built-in builder: one tree per gene of a tree output
+// directory, fasta/<gene>/<gene>.fa.filtered -> fasta/<gene>/nj.nwk.  The reference walks read_dir; here the genes are taken in ascending byte order.
+int gene_tree_main(int argc, char **argv) {
+    std::vector<std::string> pos;
+    std::string builder = "iqtree", tree_options, names;
+    bool realign = false;
+    int verbosity = 3;
+    for (int i = 2; i < argc; i++) {
+        std::string a = argv[i];
+        auto value = [&]() -> std::string {
+            if (i + 1 >= argc) clap_error_gene_tree("a value is required for '" + a + "' but none was supplied");
+            return argv[++i];
+        };
+        if (a == "-t" || a == "-T" || a == "--tree-builder") builder = value();
+        else if (a.rfind("--tree-builder=", 0) == 0) builder = a.substr(15);
+        else if (a == "-n" || a == "--names") names = value();
+        else if (a.rfind("--names=", 0) == 0) names = a.substr(8);
+        else if (a == "-p" || a == "--tree-options") tree_options = value();
+        else if (a.rfind("--tree-options=", 0) == 0) tree_options = a.substr(15);
+        else if (a == "-f" || a == "--realign") realign = true;
+        else if (a == "-a" || a == "--aligner" || a == "-o" || a == "--aligner-options" || a == "-d" || a == "--threshold") (void)value();      // read by --realign only
+        else if (a == "-c" || a == "--threads") (void)value();
+        else if (a == "-v" || a == "--verbosity") verbosity = atoi(value().c_str());
+        else if (a == "-h" || a == "--help") { usage_gene_tree(stdout); return 0; }
+        else if (a.size() > 1 && a[0] == '-') clap_error_gene_tree("unexpected argument '" + a + "' found");
+        else pos.push_back(a);
+    }
+    if (pos.empty()) clap_error_gene_tree("the following required arguments were not provided");
+    if (pos.size() > 1) clap_error_gene_tree("unexpected argument '" + pos[1] + "' found");
+    if (verbosity < 0 || verbosity > 4) clap_error_gene_tree("invalid value for '--verbosity <VERBOSITY>'");
+    g_verbosity = verbosity;
+    const std::string input = pos[0], fasta = input + "/fasta";
+    struct stat sb;
+    if (stat(input.c_str(), &sb) != 0) error(ERR_GENERAL, "Input directory does not exist");                                             // genetree.rs:22-24
+    if (stat(fasta.c_str(), &sb) != 0) error(ERR_GENERAL, "Input directory does not contain core structure fasta directories");          // genetree.rs:27-29
+    if (builder == "iqtree" || builder == "fasttree" || builder == "raxml-ng") refuse_external_builder(builder);
+    if (builder != "nj") error(ERR_GENERAL, "Unrecognized tree builder");                                                                // genetree.rs:47
+    const std::string model = nj_model_of(tree_options);
+    if (realign) error(ERR_GENERAL, "--realign would align every gene again, which gene-tree does not do in this build; run `unicore tree` for a new alignment");
+    std::vector<std::string> wanted;
+    if (!names.empty()) {                                                                                                                // genetree.rs:52-61
+        std::ifstream f(names);
+        if (!f) error(ERR_GENERAL, "Names file does not exist");
+        for (std::string line; std::getline(f, line);) { if (!line.empty() && line.back() == '\r') line.pop_back(); wanted.push_back(line); }
+    }
+    std::vector<std::string> genes;
+    DIR *d = opendir(fasta.c_str());
+    if (!d) error(ERR_GENERAL, "Input directory does not contain core structure fasta directories");
+    while (const dirent *e = readdir(d)) {
+        const std::string g = e->d_name;
+        if (g != "." && g != "..") genes.push_back(g);
+    }
+    closedir(d);
+    std::sort(genes.begin(), genes.end());
+    if (!wanted.empty()) {                                                                                                               // genetree.rs:72-83
+        std::vector<std::string> kept;
+        for (const std::string &g : genes) {
+            const std::string stem = g.substr(0, g.rfind('.') == std::string::npos || g.rfind('.') == 0 ? g.size() : g.rfind('.'));      // Path::file_stem
+            if (std::find(wanted.begin(), wanted.end(), stem) != wanted.end()) kept.push_back(g);
+        }
+        if (kept.empty()) error(ERR_GENERAL, "No gene names matched");
+        genes = kept;
+    }
+    uc_opts o;
+    memset(&o, 0, sizeof o);
+    o.struct_size = sizeof o;
+    o.threads = 1;
+    o.verbosity = verbosity;
+    o.device = -1;
+    print_message("\rInferring gene specific phylogenetic trees 0/" + std::to_string(genes.size()) + "...", 3);                          // genetree.rs:112
+    for (size_t k = 0; k < genes.size(); k++) {
+        const std::string dir = fasta + "/" + genes[k], msa = dir + "/" + genes[k] + ".fa.filtered";
+        size_t rows = 0;
+        {
+            std::ifstream f(msa, std::ios::binary);
+            const bool opened = (bool)f;
+            if (opened) for (std::string line; std::getline(f, line);) rows += !line.empty() && line[0] == '>';
+            else if (g_verbosity >= 2) fprintf(stderr, "\nWarning: gene %s has no filtered alignment %s; it gets no tree\n", genes[k].c_str(), msa.c_str());
+            if (opened && rows < 2 && g_verbosity >= 2) fprintf(stderr, "\nWarning: gene %s has %zu row(s); a tree needs two; it gets no tree\n", genes[k].c_str(), rows);
+        }
+        if (rows >= 2) {
+            const int rc = uc_tree_infer(msa.c_str(), (dir + "/nj.nwk").c_str(), model.c_str(), &o, nullptr);
+            if (rc != 0) error(ERR_GENERAL, "gene-tree failed on " + genes[k] + " with code " + std::to_string(rc) + "\n" + uc_last_error());
+        }
+        print_message("\rInferring gene specific phylogenetic trees " + std::to_string(k + 1) + "/" + std::to_string(genes.size()) + "...", 3);   // genetree.rs:142
+    }
+    println_message("Done", 3);                                                                                                           // genetree.rs:144
     return 0;
 }
 
@@ -320,6 +466,12 @@ int main(int argc, char **argv) {
     }
     if (!strcmp(argv[1], "tree") && argc > 2) {      // bare `unicore tree` keeps its earlier answer below (ERR_MODULE_NOT_IMPLEMENTED)
         const int rc = tree_main(argc, argv);
+        fflush(stdout);
+        fflush(stderr);
+        _exit(rc);
+    }
+    if (!strcmp(argv[1], "gene-tree") && argc > 2) {      // the bare module name keeps its earlier answer below
+        const int rc = gene_tree_main(argc, argv);
         fflush(stdout);
         fflush(stderr);
         _exit(rc);

@@ -1,0 +1,78 @@
+// uc_nj.h — the built-in tree builder `nj` of `unicore tree` / `unicore gene-tree` (rule UC-N): argument blocks, the checks both
+// sides share, the host twins (uc_nj_host.cpp) and the device side (uc_nj.hip).  Host and device take the same arrays and give the same outputs:
+// integers as integers, fp64 values by their bits.
+#pragma once
+#include <cstdint>
+
+#include "uc_common.h"
+
+// UC-N/J rounds every operation on its own: no fused multiply-add may be formed from the expressions below.  The device compiler contracts by
+// default, so the pragma is what keeps a * b + c two roundings there; the host build names no -march and so has no FMA instruction to form.
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+#if defined(__HIPCC__)
+#define UC_NJ_HD __host__ __device__
+#else
+#define UC_NJ_HD
+#endif
+
+namespace uc {
+
+constexpr uint32_t NJ_MIN_ROWS = 2, NJ_MAX_ROWS = 16384;      // D is 2 GiB at the top
+constexpr uint32_t NJ_TILE = 64;                               // rows of a pair tile of the count kernel (a tile is NJ_TILE x NJ_TILE pairs)
+constexpr uint32_t NJ_CHUNK = 256;                             // columns of both row tiles staged through LDS at a time
+constexpr double NJ_CAP = 5.0;                                 // the largest distance (UC-N/D)
+constexpr uint32_t NJ_NO_NODE = 0xffffffffu;                   // root_node[2] of a two-leaf tree
+
+// ---- UC-N/D: comp / diff of every row pair
+struct NjCountArgs {
+    uint32_t n;                   // rows
+    uint64_t w;                   // columns of every row
+    const uint8_t *cells;         // n x w bytes, row-major
+    uint32_t threads;             // host twin only (0 = 1)
+    uint32_t *comp, *diff;        // n (n - 1) / 2 each: (i, j) with i < j at i n - i (i + 1) / 2 + (j - i - 1), as MsaCenterArgs::scores
+};
+void nj_counts_validate(const NjCountArgs &a);
+void nj_counts_host(const NjCountArgs &a);
+void nj_counts_device(int device, const NjCountArgs &a);
+
+// the code of a cell: 0 = uninformative, 1 .. 26 = the letters without X, case folded
+UC_NJ_HD inline uint8_t nj_code(uint8_t c) {
+    const uint8_t u = (uint8_t)(c | 0x20);
+    return (u >= 'a' && u <= 'z' && u != 'x') ? (uint8_t)(u - 'a' + 1) : (uint8_t)0;
+}
+
+// model: 0 kimura, 1 p; D is n x n, symmetric, zero on the diagonal.  counts (nullable, 2): pairs without a comparable column, pairs at the cap
+void nj_distances_host(const uint32_t *comp, const uint32_t *diff, uint32_t n, uint32_t model, double *D, uint64_t *counts);
+
+// ---- UC-N/J: the joins
+struct NjJoinArgs {
+    uint32_t n;
+    const double *D;              // n x n, not modified
+    uint32_t *join_a, *join_b;    // n - 3 (n > 3): the nodes in slot i and slot j of every step
+    double *len_a, *len_b;        // n - 3
+    uint32_t *root_node;          // 3 (n == 2: two, the third is NJ_NO_NODE)
+    double *root_len;             // 3
+};
+// the arithmetic of a step, written once for both sides; m = the active slots of the step
+UC_NJ_HD inline double nj_pos(double v) { return v > 0.0 ? v : 0.0; }
+UC_NJ_HD inline double nj_q(uint32_t m, double dij, double ri, double rj) { return (((double)(m - 2) * dij) - ri) - rj; }
+UC_NJ_HD inline void nj_branch(uint32_t m, double dij, double ri, double rj, double &li, double &lj) {
+    li = 0.5 * dij + (ri - rj) / (2.0 * (double)(m - 2));
+    lj = dij - li;
+    if (!(li > 0.0)) { li = 0.0; lj = nj_pos(dij); }      // a reduced distance of a matrix that is no tree metric can be negative itself
+    else if (!(lj > 0.0)) { lj = 0.0; li = nj_pos(dij); }
+}
+UC_NJ_HD inline double nj_new(double dik, double djk, double dij) { return 0.5 * ((dik + djk) - dij); }
+UC_NJ_HD inline void nj_root3(double dab, double dac, double dbc, double *len) {
+    len[0] = nj_pos(0.5 * ((dab + dac) - dbc));
+    len[1] = nj_pos(0.5 * ((dab + dbc) - dac));
+    len[2] = nj_pos(0.5 * ((dac + dbc) - dab));
+}
+// finite, >= 0 (no -0.0), symmetric, zero diagonal: the device reads rows as columns
+void nj_join_validate(const NjJoinArgs &a);
+void nj_join_host(const NjJoinArgs &a);
+void nj_join_device(int device, const NjJoinArgs &a);
+
+}  // namespace uc
