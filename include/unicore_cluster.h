@@ -415,6 +415,49 @@ typedef struct uc_nj_stats {
 } uc_nj_stats;
 int uc_tree_infer(const char *msa_fasta, const char *out_nwk, const char *model, const uc_opts *o, uc_nj_stats *stats_out);
 
+/* ---- bootstrap support for `nj` (rule UC-N/B): B replicate trees over columns drawn with replacement, and for every internal branch
+ * of the main tree the number of replicates that hold the same split.  The reference's `iqtree -B 1000` (tree.rs:139-161) labels its tree the same way.
+ * Every output is defined bit for bit; the _dev siblings run the HIP kernels of uc_nj_boot.hip with the replicate as a grid dimension.  Limits, all
+ * UC_ERR_ARGS before the device is touched: those of UC-N, and rep0 + n_rep <= 100000.
+ * Draws, modulo 2^64 with G = 0x9E3779B97F4A7C15 and mix = SplitMix64's finaliser: key = mix(seed + G (rep + 1)), x = mix(key + G (t + 1)), column t of
+ *   replicate rep is source column (x w) >> 64.  The host-only column entry point writes the w draws of one replicate.
+ * Replicate counts: comp / diff [n_rep][n (n - 1) / 2] of replicates rep0 .. rep0 + n_rep - 1: UC-N/D over the drawn columns.  The device side works
+ *   under UC_TREE_BUDGET_BYTES in batches of replicates and slices of source columns; no result depends on it.
+ * Batched joins: D [n_rep][n][n] (not modified); every output array is the single call's, replicate after replicate ([n_rep][n - 3], [n_rep][3]), and
+ *   equals UC-N/J on D[b] by bits.  n <= lds_rows of the geometry call runs one workgroup per replicate with D in LDS, larger n three launches per step
+ *   for the whole batch.
+ * Support: join s of the main tree creates node n + s; its split is {the leaves below it, the others}.  support [n - 3] receives the number of
+ *   replicates (join_a / join_b [n_rep][n - 3]) with the same split, compared as leaf sets.  n <= 3 writes nothing.
+ * Labelled Newick: the unlabelled line with (200 support[s] + n_rep) div (2 n_rep) - the percentage, rounded half up - between the `)` of node n + s and
+ *   its `:`; the root has no label; n_rep == 0 (support may be NULL) gives the unlabelled line. */
+int uc_nj_boot_columns(uint64_t w, uint64_t seed, uint32_t rep, uint32_t *cols);
+int uc_nj_boot_counts(uint32_t n, uint64_t w, const uint8_t *cells, uint64_t seed, uint32_t rep0, uint32_t n_rep, uint32_t threads, uint32_t *comp,
+                      uint32_t *diff);
+int uc_nj_boot_counts_dev(int32_t device, uint32_t n, uint64_t w, const uint8_t *cells, uint64_t seed, uint32_t rep0, uint32_t n_rep, uint32_t threads,
+                          uint32_t *comp, uint32_t *diff);
+int uc_nj_join_batch(uint32_t n, uint32_t n_rep, const double *D, uint32_t *join_a, uint32_t *join_b, double *len_a, double *len_b, uint32_t *root_node,
+                     double *root_len);
+int uc_nj_join_batch_dev(int32_t device, uint32_t n, uint32_t n_rep, const double *D, uint32_t *join_a, uint32_t *join_b, double *len_a, double *len_b,
+                         uint32_t *root_node, double *root_len);
+int uc_nj_support(uint32_t n, const uint32_t *join_a, const uint32_t *join_b, uint32_t n_rep, const uint32_t *rep_join_a, const uint32_t *rep_join_b,
+                  uint32_t *support);
+int uc_nj_newick_support(const char *const *names, uint32_t n, const uint32_t *join_a, const uint32_t *join_b, const double *len_a, const double *len_b,
+                         const uint32_t *root_node, const double *root_len, const uint32_t *support, uint32_t n_rep, char *buf, uint64_t cap,
+                         uint64_t *need);
+int uc_nj_boot_geometry(uint32_t *lds_rows);
+/* == `unicore tree -t nj -p "--bootstrap B --seed S"`: the main tree as the plain inference call computes it (unchanged in every bit), n_rep replicate
+ * trees, and out_nwk with the labels.  n_rep == 0 writes what the plain call writes.  UC_TREE_HOST=1 and UC_TREE_DUMP=1 as there; a dump with
+ * n_rep > 0 also writes <out_nwk>.boot.tsv (one line `s\tsupport` per join) and <out_nwk>.boottrees (the replicates' unlabelled lines, in order). */
+#define UC_NJ_BOOT_NPHASE 7
+typedef struct uc_nj_boot_stats {
+    uint64_t n_rows, n_columns, n_replicates;
+    uint64_t n_batches;                  /* batches of replicates the budget gave */
+    uint64_t support_min, support_sum;   /* over the n - 3 joins; 0 without an internal branch */
+    double seconds[UC_NJ_BOOT_NPHASE];   /* host wall: [0] reading, [1] main tree, [2] draws + counts, [3] transform, [4] joins, [5] support, [6] writing */
+} uc_nj_boot_stats;
+int uc_tree_infer_boot(const char *msa_fasta, const char *out_nwk, const char *model, uint32_t n_rep, uint64_t seed, const uc_opts *o,
+                       uc_nj_boot_stats *stats_out);
+
 /* ---- kernel-level entry points (parity tests call the HIP kernels through these) -------------- */
 /* ungapped diagonal score (E3) for n candidates (q[i], t[i], diag[i]) of the engine's DB */
 int uc_engine_ungapped_batch(uc_engine *e, uint64_t n, const uint32_t *q, const uint32_t *t,

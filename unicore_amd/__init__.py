@@ -60,6 +60,13 @@ NJ_MODELS = {"kimura": 0, "p": 1}
 NJ_NO_NODE = 0xFFFFFFFF  # == UC_NJ_NO_NODE: the third root entry of a two-leaf tree
 
 
+class UcNjBootStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("n_rows", "n_columns", "n_replicates", "n_batches", "support_min", "support_sum")] + [("seconds", C.c_double * 7)]
+
+
+NJ_BOOT_PHASES = ("read", "main_tree", "counts", "transform", "join", "support", "write")
+
+
 class UcT5Stats(C.Structure):
     _fields_ = [("n_seqs", C.c_uint64), ("n_tokens", C.c_uint64), ("flops", C.c_double), ("gpu_ms", C.c_double),
                 ("n_replicas", C.c_uint32), ("reserved0", C.c_uint32), ("gpu_ms_sum", C.c_double),
@@ -86,6 +93,8 @@ SYMBOLS = (
     "uc_profile_count", "uc_profile_count_dev", "uc_profile",
     "uc_msa_center", "uc_msa_center_dev", "uc_msa_star", "uc_msa_star_dev", "uc_msa_filter", "uc_msa_filter_dev", "uc_tree",
     "uc_nj_counts", "uc_nj_counts_dev", "uc_nj_distances", "uc_nj_join", "uc_nj_join_dev", "uc_nj_newick", "uc_nj_geometry", "uc_tree_infer",
+    "uc_nj_boot_columns", "uc_nj_boot_counts", "uc_nj_boot_counts_dev", "uc_nj_join_batch", "uc_nj_join_batch_dev", "uc_nj_support", "uc_nj_newick_support",
+    "uc_nj_boot_geometry", "uc_tree_infer_boot",
 )
 NO_GENE = 0xFFFFFFFF  # == UC_NO_GENE: a TSV row whose gene name is not in the map
 ABI_VERSION = 9      # == UC_ABI_VERSION of include/unicore_cluster.h this binding mirrors
@@ -180,6 +189,15 @@ def lib():
     L.uc_nj_newick.argtypes = [C.POINTER(C.c_char_p), u32] + [vp] * 6 + [vp, u64, C.POINTER(u64)]
     L.uc_nj_geometry.argtypes = [C.POINTER(u32), C.POINTER(u32)]
     L.uc_tree_infer.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(UcOpts), C.POINTER(UcNjStats)]
+    L.uc_nj_boot_columns.argtypes = [u64, u64, u32, vp]
+    L.uc_nj_boot_counts.argtypes = [u32, u64, vp, u64, u32, u32, u32, vp, vp]
+    L.uc_nj_boot_counts_dev.argtypes = [i32] + L.uc_nj_boot_counts.argtypes
+    L.uc_nj_join_batch.argtypes = [u32, u32] + [vp] * 7
+    L.uc_nj_join_batch_dev.argtypes = [i32] + L.uc_nj_join_batch.argtypes
+    L.uc_nj_support.argtypes = [u32, vp, vp, u32, vp, vp, vp]
+    L.uc_nj_newick_support.argtypes = [C.POINTER(C.c_char_p), u32] + [vp] * 6 + [vp, u32, vp, u64, C.POINTER(u64)]
+    L.uc_nj_boot_geometry.argtypes = [C.POINTER(u32)]
+    L.uc_tree_infer_boot.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, u32, u64, C.POINTER(UcOpts), C.POINTER(UcNjBootStats)]
     L.uc_engine_ungapped_batch.argtypes = [vp, u64, vp, vp, vp, vp]
     L.uc_engine_ungapped_select.argtypes = [vp, u64, vp, vp, vp, C.c_int32, vp, vp, vp]
     L.uc_engine_ungapped_all.argtypes = [vp, u32, u32, u32, u32, u64, vp, vp]
@@ -478,24 +496,100 @@ def nj_join(D, device=None):
     return {"join_a": ja[:steps], "join_b": jb[:steps], "len_a": la[:steps], "len_b": lb[:steps], "root_node": rn, "root_len": rl}
 
 
-def nj_newick(names, joins):
-    """uc_nj_newick (host only): the tree of nj_join's dict over the leaf names (str or bytes) as one Newick line with its newline (str)."""
+def nj_newick(names, joins, support=None, n_rep=0):
+    """uc_nj_newick / uc_nj_newick_support (host only): the tree of nj_join's dict over the leaf names (str or bytes) as one Newick line with its
+    newline (str).  With support (nj_support's array) and n_rep > 0 every internal node but the root carries its percentage, rounded half up."""
     nm = [x if isinstance(x, bytes) else x.encode() for x in names]
     arr = (C.c_char_p * max(len(nm), 1))(*nm)
     a = [np.ascontiguousarray(joins[k], t) for k, t in (("join_a", np.uint32), ("join_b", np.uint32), ("len_a", np.float64), ("len_b", np.float64),
                                                         ("root_node", np.uint32), ("root_len", np.float64))]
     need = C.c_uint64()
     ptrs = [_ptr(x) for x in a]
-    _check(lib().uc_nj_newick(arr, len(nm), *ptrs, None, 0, C.byref(need)))
+    if support is None and not n_rep:
+        call = lambda buf, cap: lib().uc_nj_newick(arr, len(nm), *ptrs, buf, cap, C.byref(need))
+    else:
+        su = None if support is None else np.ascontiguousarray(support, np.uint32)
+        call = lambda buf, cap: lib().uc_nj_newick_support(arr, len(nm), *ptrs, None if su is None else _ptr(su), n_rep, buf, cap, C.byref(need))
+    _check(call(None, 0))
     buf = C.create_string_buffer(need.value + 1)
-    _check(lib().uc_nj_newick(arr, len(nm), *ptrs, C.cast(buf, C.c_void_p), need.value + 1, C.byref(need)))
+    _check(call(C.cast(buf, C.c_void_p), need.value + 1))
     return buf.value.decode()
 
 
-def tree_infer(fasta, out, model="kimura", verbosity=1, device=-1, threads=1):
+def nj_boot_geometry():
+    """uc_nj_boot_geometry: {"lds_rows": the largest n whose batched join loop runs in LDS, one workgroup per replicate}."""
+    r = C.c_uint32()
+    _check(lib().uc_nj_boot_geometry(C.byref(r)))
+    return {"lds_rows": r.value}
+
+
+def nj_boot_columns(w, seed, rep):
+    """UC-N/B (uc_nj_boot_columns, host only): the w source columns replicate `rep` draws under `seed`, uint32."""
+    cols = np.zeros(max(min(w, 1 << 31), 1), np.uint32)
+    _check(lib().uc_nj_boot_columns(w, seed & (2 ** 64 - 1), rep, cols.ctypes.data))
+    return cols[:w]
+
+
+def nj_boot_counts(rows, seed, rep0, n_rep, device=None, threads=1):
+    """UC-N/B (uc_nj_boot_counts / uc_nj_boot_counts_dev): rows as nj_counts takes them.  Returns (comp, diff), uint32 [n_rep][n (n - 1) / 2]: the
+    counts of replicates rep0 .. rep0 + n_rep - 1 over their drawn columns.  device as in msa_center; threads: the host twin's."""
+    if isinstance(rows, (list, tuple)):
+        if len({len(r) for r in rows}) > 1:
+            raise ValueError("rows of unequal width")
+        rows = np.frombuffer(b"".join(bytes(r) for r in rows), np.uint8).reshape(len(rows), -1) if rows else np.zeros((0, 0), np.uint8)
+    ce = np.ascontiguousarray(rows, np.uint8)
+    if ce.ndim != 2:
+        raise ValueError("rows is n rows x w columns")
+    n, w = ce.shape
+    tri = n * (n - 1) // 2
+    comp, diff = np.zeros((max(n_rep, 1), max(tri, 1)), np.uint32), np.zeros((max(n_rep, 1), max(tri, 1)), np.uint32)
+    args = [n, w, _ptr(ce), seed & (2 ** 64 - 1), rep0, n_rep, threads, comp.ctypes.data, diff.ctypes.data]
+    _check(lib().uc_nj_boot_counts(*args) if device is None else lib().uc_nj_boot_counts_dev(device, *args))
+    return comp[:n_rep, :tri], diff[:n_rep, :tri]
+
+
+def nj_join_batch(D, device=None):
+    """UC-N/J on a batch (uc_nj_join_batch / uc_nj_join_batch_dev): D is [n_rep][n][n] fp64 (not modified).  Returns nj_join's dict with a leading
+    replicate axis on every array; replicate b equals nj_join(D[b]) by bits.  device as in msa_center."""
+    d = np.ascontiguousarray(D, np.float64)
+    if d.ndim != 3 or d.shape[1] != d.shape[2]:
+        raise ValueError("D is n_rep x n x n")
+    B, n = d.shape[0], d.shape[1]
+    steps = max(n - 3, 0)
+    ja, jb = np.zeros((max(B, 1), max(steps, 1)), np.uint32), np.zeros((max(B, 1), max(steps, 1)), np.uint32)
+    la, lb = np.zeros((max(B, 1), max(steps, 1)), np.float64), np.zeros((max(B, 1), max(steps, 1)), np.float64)
+    rn, rl = np.zeros((max(B, 1), 3), np.uint32), np.zeros((max(B, 1), 3), np.float64)
+    args = [n, B, _ptr(d), ja.ctypes.data, jb.ctypes.data, la.ctypes.data, lb.ctypes.data, rn.ctypes.data, rl.ctypes.data]
+    _check(lib().uc_nj_join_batch(*args) if device is None else lib().uc_nj_join_batch_dev(device, *args))
+    return {"join_a": ja[:B, :steps], "join_b": jb[:B, :steps], "len_a": la[:B, :steps], "len_b": lb[:B, :steps], "root_node": rn[:B], "root_len": rl[:B]}
+
+
+def nj_support(n, joins, rep_join_a, rep_join_b):
+    """UC-N/B (uc_nj_support, host only): joins is the main tree's nj_join dict over n leaves, rep_join_a / rep_join_b [n_rep][n - 3] the replicates'
+    (nj_join_batch's arrays).  Returns uint32 [n - 3]: for the split of every join of the main tree, the replicates that hold the same split."""
+    steps = max(n - 3, 0)
+    ja, jb = np.ascontiguousarray(joins["join_a"], np.uint32), np.ascontiguousarray(joins["join_b"], np.uint32)
+    ra, rb = np.ascontiguousarray(rep_join_a, np.uint32).reshape(-1, max(steps, 1)), np.ascontiguousarray(rep_join_b, np.uint32).reshape(-1, max(steps, 1))
+    if len(ja) != steps or len(jb) != steps or ra.shape != rb.shape or (steps and ra.shape[1] != steps):
+        raise ValueError("join arrays hold n - 3 entries per tree")
+    B = ra.shape[0] if steps else 0
+    out = np.zeros(max(steps, 1), np.uint32)
+    _check(lib().uc_nj_support(n, _ptr(ja), _ptr(jb), B, _ptr(ra), _ptr(rb), out.ctypes.data))
+    return out[:steps]
+
+
+def tree_infer(fasta, out, model="kimura", verbosity=1, device=-1, threads=1, bootstrap=0, seed=1):
     """== the inference step of `unicore tree -t nj` (uc_tree_infer): reads the aligned FASTA `fasta`, counts on the device, transforms under
     `model`, joins and writes the Newick line to `out`.  UC_TREE_HOST=1 in the environment runs the host twins (no GPU needed); UC_TREE_DUMP=1
-    also writes <out>.dist.tsv.  Returns the stats dict (counts and seconds per phase)."""
+    also writes <out>.dist.tsv.  Returns the stats dict (counts and seconds per phase).  bootstrap > 0 (uc_tree_infer_boot): `bootstrap`
+    replicate trees drawn under `seed` label every internal branch of the same tree with its support; the stats dict is then the bootstrap's
+    (replicates, batches, smallest and summed support, seconds per phase) and a dump also writes <out>.boot.tsv and <out>.boottrees."""
+    if bootstrap:
+        o, st = make_opts("", threads, verbosity, device), UcNjBootStats()
+        _check(lib().uc_tree_infer_boot(fasta.encode(), out.encode(), None if model is None else model.encode(), bootstrap, seed & (2 ** 64 - 1), C.byref(o), C.byref(st)))
+        d = {k: int(getattr(st, k)) for k, _ in UcNjBootStats._fields_ if k != "seconds"}
+        d["seconds"] = dict(zip(NJ_BOOT_PHASES, st.seconds))
+        return d
     o, st = make_opts("", threads, verbosity, device), UcNjStats()
     _check(lib().uc_tree_infer(fasta.encode(), out.encode(), None if model is None else model.encode(), C.byref(o), C.byref(st)))
     d = {k: int(getattr(st, k)) for k, _ in UcNjStats._fields_ if k != "seconds"}

@@ -10,6 +10,8 @@
 // The three `foldseek` spawns of cluster.rs:45-76 become three in-process calls through the C ABI.
 #include <sys/stat.h>
 
+#include <cerrno>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -238,7 +240,9 @@ void usage_tree(FILE *to) {
          "                                           <OUTPUT>/nj.nwk; the others are external programs: parsed, not run [default: iqtree]\n"
          "  -o, --aligner-options <ALIGNER_OPTIONS>  Foldseek-style options for the gapped stage behind the star aligner, e.g. -o \"--gap-open 12\"\n"
          "  -n, --no-inference                       Stop the tree module after alignment (before tree inference); required unless the builder is nj\n"
-         "  -p, --tree-options <TREE_OPTIONS>        Options for tree builder; nj: \"--model kimura|p\" [default: kimura]; parsed, not used for the others\n"
+         "  -p, --tree-options <TREE_OPTIONS>        Options for tree builder; nj: \"--model kimura|p\" [default: kimura], \"--bootstrap B\" replicates label\n"
+         "                                           every internal branch with its support in percent [default: 0], \"--seed S\" of their draws\n"
+         "                                           [default: 1]; parsed, not used for the others\n"
          "  -d, --threshold <THRESHOLD>              Gap threshold for multiple sequence alignment [0 - 100] [default: 50]\n"
          "  -c, --threads <THREADS>                  Number of threads to use; 0 to use all [default: 0]\n"
          "  -v, --verbosity <VERBOSITY>              Verbosity (0: quiet, 1: +errors, 2: +warnings, 3: +info, 4: +debug) [default: 3]\n"
@@ -250,8 +254,19 @@ void usage_tree(FILE *to) {
     exit(CLAP_USAGE);
 }
 
-// the options of the built-in builder: "--model kimura|p" (also --model=...); any other word is refused by name.  Returns the model
-std::string nj_model_of(const std::string &tree_options) {
+// the options of the built-in builder: "--model kimura|p", "--bootstrap B" (0 .. 100000) and "--seed S" (64 bits), each also as --word=value; any other
+// word is refused by name, a value that is no number in range too
+struct NjOptions { std::string model = "kimura"; uint32_t bootstrap = 0; uint64_t seed = 1; };
+
+uint64_t nj_number_of(const std::string &word, const std::string &v, uint64_t most) {
+    bool ok = !v.empty() && v.size() <= 20 && v.find_first_not_of("0123456789") == std::string::npos;
+    unsigned long long x = 0;
+    if (ok) { errno = 0; x = strtoull(v.c_str(), nullptr, 10); ok = errno == 0 && x <= most; }
+    if (!ok) error(ERR_GENERAL, "tree builder nj: '" + v + "' is not a value for " + word + " (a number from 0 to " + std::to_string(most) + ")");
+    return x;
+}
+
+NjOptions nj_options_of(const std::string &tree_options) {
     std::vector<std::string> words;
     for (size_t p = 0; p < tree_options.size();) {
         while (p < tree_options.size() && isspace((unsigned char)tree_options[p])) p++;
@@ -259,16 +274,35 @@ std::string nj_model_of(const std::string &tree_options) {
         while (p < tree_options.size() && !isspace((unsigned char)tree_options[p])) p++;
         if (p > b) words.push_back(tree_options.substr(b, p - b));
     }
-    std::string model = "kimura";
+    NjOptions o;
     for (size_t k = 0; k < words.size(); k++) {
-        if (words[k] == "--model") {
-            if (k + 1 >= words.size()) error(ERR_GENERAL, "tree builder nj: --model needs a value (kimura, p)");
-            model = words[++k];
-        } else if (words[k].rfind("--model=", 0) == 0) model = words[k].substr(8);
-        else error(ERR_GENERAL, "tree builder nj does not know the option '" + words[k] + "' (--model kimura|p)");
+        auto value = [&](const char *name, const char *what, std::string &v) {      // --name V or --name=V
+            const std::string eq = std::string(name) + "=";
+            if (words[k] == name) {
+                if (k + 1 >= words.size()) error(ERR_GENERAL, std::string("tree builder nj: ") + name + " needs a value (" + what + ")");
+                v = words[++k];
+                return true;
+            }
+            if (words[k].rfind(eq, 0) == 0) { v = words[k].substr(eq.size()); return true; }
+            return false;
+        };
+        std::string v;
+        if (value("--model", "kimura, p", v)) o.model = v;
+        else if (value("--bootstrap", "replicates, 0 .. 100000", v)) o.bootstrap = (uint32_t)nj_number_of("--bootstrap", v, 100000);
+        else if (value("--seed", "a 64-bit number", v)) o.seed = nj_number_of("--seed", v, UINT64_MAX);
+        else error(ERR_GENERAL, "tree builder nj does not know the option '" + words[k] + "' (--model kimura|p, --bootstrap B, --seed S)");
     }
-    if (model != "kimura" && model != "p") error(ERR_GENERAL, "tree builder nj does not know the model '" + model + "' (kimura, p)");
-    return model;
+    if (o.model != "kimura" && o.model != "p") error(ERR_GENERAL, "tree builder nj does not know the model '" + o.model + "' (kimura, p)");
+    return o;
+}
+
+// the inference call of both modules: the plain entry point without --bootstrap, so that every byte written is what it wrote before the option existed
+// (threads: -c, 0 = all; only the replicates' host side - transform, support - is spread over them)
+int nj_infer(const std::string &msa, const std::string &out, const NjOptions &nj, const uc_opts &o, int threads) {
+    if (!nj.bootstrap) return uc_tree_infer(msa.c_str(), out.c_str(), nj.model.c_str(), &o, nullptr);
+    uc_opts ob = o;
+    ob.threads = threads > 0 ? threads : (int)std::min(16u, std::max(1u, std::thread::hardware_concurrency()));      // n^2 logs a replicate: more do not pay
+    return uc_tree_infer_boot(msa.c_str(), out.c_str(), nj.model.c_str(), nj.bootstrap, nj.seed, &ob, nullptr);
 }
 
 [[noreturn]] void refuse_external_builder(const std::string &builder) {
@@ -283,7 +317,7 @@ int tree_main(int argc, char **argv) {
     std::string aligner = "star", builder = "iqtree", aligner_options, tree_options;
     bool no_inference = false;
     uint32_t threshold = 50;      // arg_parser.rs:322
-    int verbosity = 3;
+    int verbosity = 3, threads = 0;
     for (int i = 2; i < argc; i++) {
         std::string a = argv[i];
         auto value = [&]() -> std::string {
@@ -308,7 +342,7 @@ int tree_main(int argc, char **argv) {
         else if (a == "-n" || a == "--no-inference") no_inference = true;
         else if (a == "-d" || a == "--threshold") parse_threshold(value());
         else if (a.rfind("--threshold=", 0) == 0) parse_threshold(a.substr(12));
-        else if (a == "-c" || a == "--threads") (void)value();      // the module's host side has no threaded part
+        else if (a == "-c" || a == "--threads") threads = atoi(value().c_str());      // read by the bootstrap of nj alone
         else if (a == "-v" || a == "--verbosity") verbosity = atoi(value().c_str());
         else if (a == "-h" || a == "--help") { usage_tree(stdout); return 0; }
         else if (a.size() > 1 && a[0] == '-') clap_error_tree("unexpected argument '" + a + "' found");
@@ -323,7 +357,7 @@ int tree_main(int argc, char **argv) {
     if (aligner != "star") error(ERR_GENERAL, "Unrecognized aligner");                  // tree.rs:118
     const bool nj = builder == "nj";
     if (!nj && builder != "iqtree" && builder != "fasttree" && builder != "raxml-ng") error(ERR_GENERAL, "Unrecognized tree builder");   // tree.rs:146
-    const std::string model = nj ? nj_model_of(tree_options) : "";
+    const NjOptions nj_opts = nj ? nj_options_of(tree_options) : NjOptions();
     if (!no_inference && !nj) refuse_external_builder(builder);
     uc_opts o;
     memset(&o, 0, sizeof o);
@@ -335,7 +369,7 @@ int tree_main(int argc, char **argv) {
     if (rc != 0) error(ERR_GENERAL, std::string("tree failed with code ") + std::to_string(rc) + "\n" + uc_last_error());
     if (no_inference) return 0;      // tree.rs:135-137 skips the alignment when combined.fasta exists and infers all the same
     print_message("Inferring phylogenetic tree...", 3);      // tree.rs:150
-    rc = uc_tree_infer((pos[2] + "/combined.fasta").c_str(), (pos[2] + "/nj.nwk").c_str(), model.c_str(), &o, nullptr);
+    rc = nj_infer(pos[2] + "/combined.fasta", pos[2] + "/nj.nwk", nj_opts, o, threads);
     if (rc != 0) error(ERR_GENERAL, std::string("tree inference failed with code ") + std::to_string(rc) + "\n" + uc_last_error());
     println_message(" Done", 3);
     write_checkpoint(pos[2] + "/tree.chk", "1");             // tree.rs:161
@@ -350,7 +384,9 @@ void usage_gene_tree(FILE *to) {
          "  -n, --names <NAMES>                      File containing core structures for computing phylogenetic tree; all of them if not given\n"
          "  -t, -T, --tree-builder <TREE_BUILDER>    Phylogenetic tree builder [nj, iqtree, fasttree, raxml-ng]; nj (neighbour joining, built in) writes\n"
          "                                           fasta/<gene>/nj.nwk; the others are external programs and are refused [default: iqtree]\n"
-         "  -p, --tree-options <TREE_OPTIONS>        Options for tree builder; nj: \"--model kimura|p\" [default: kimura]\n"
+         "  -p, --tree-options <TREE_OPTIONS>        Options for tree builder; nj: \"--model kimura|p\" [default: kimura], \"--bootstrap B\" replicates label\n"
+         "                                           every internal branch with its support in percent [default: 0], \"--seed S\" of their draws\n"
+         "                                           [default: 1], the same for every gene\n"
          "  -f, --realign                            Refused: re-aligning single genes is not built in\n"
          "  -c, --threads <THREADS>                  Number of threads to use; 0 to use all [default: 0]\n"
          "  -v, --verbosity <VERBOSITY>              Verbosity (0: quiet, 1: +errors, 2: +warnings, 3: +info, 4: +debug) [default: 3]\n"
@@ -368,7 +404,7 @@ int gene_tree_main(int argc, char **argv) {
     std::vector<std::string> pos;
     std::string builder = "iqtree", tree_options, names;
     bool realign = false;
-    int verbosity = 3;
+    int verbosity = 3, threads = 0;
     for (int i = 2; i < argc; i++) {
         std::string a = argv[i];
         auto value = [&]() -> std::string {
@@ -383,7 +419,7 @@ int gene_tree_main(int argc, char **argv) {
         else if (a.rfind("--tree-options=", 0) == 0) tree_options = a.substr(15);
         else if (a == "-f" || a == "--realign") realign = true;
         else if (a == "-a" || a == "--aligner" || a == "-o" || a == "--aligner-options" || a == "-d" || a == "--threshold") (void)value();      // read by --realign only
-        else if (a == "-c" || a == "--threads") (void)value();
+        else if (a == "-c" || a == "--threads") threads = atoi(value().c_str());      // read by the bootstrap of nj alone
         else if (a == "-v" || a == "--verbosity") verbosity = atoi(value().c_str());
         else if (a == "-h" || a == "--help") { usage_gene_tree(stdout); return 0; }
         else if (a.size() > 1 && a[0] == '-') clap_error_gene_tree("unexpected argument '" + a + "' found");
@@ -399,7 +435,7 @@ int gene_tree_main(int argc, char **argv) {
     if (stat(fasta.c_str(), &sb) != 0) error(ERR_GENERAL, "Input directory does not contain core structure fasta directories");          // genetree.rs:27-29
     if (builder == "iqtree" || builder == "fasttree" || builder == "raxml-ng") refuse_external_builder(builder);
     if (builder != "nj") error(ERR_GENERAL, "Unrecognized tree builder");                                                                // genetree.rs:47
-    const std::string model = nj_model_of(tree_options);
+    const NjOptions nj_opts = nj_options_of(tree_options);      // every gene draws under the same seed
     if (realign) error(ERR_GENERAL, "--realign would align every gene again, which gene-tree does not do in this build; run `unicore tree` for a new alignment");
     std::vector<std::string> wanted;
     if (!names.empty()) {                                                                                                                // genetree.rs:52-61
@@ -443,7 +479,7 @@ int gene_tree_main(int argc, char **argv) {
             if (opened && rows < 2 && g_verbosity >= 2) fprintf(stderr, "\nWarning: gene %s has %zu row(s); a tree needs two; it gets no tree\n", genes[k].c_str(), rows);
         }
         if (rows >= 2) {
-            const int rc = uc_tree_infer(msa.c_str(), (dir + "/nj.nwk").c_str(), model.c_str(), &o, nullptr);
+            const int rc = nj_infer(msa, dir + "/nj.nwk", nj_opts, o, threads);
             if (rc != 0) error(ERR_GENERAL, "gene-tree failed on " + genes[k] + " with code " + std::to_string(rc) + "\n" + uc_last_error());
         }
         print_message("\rInferring gene specific phylogenetic trees " + std::to_string(k + 1) + "/" + std::to_string(genes.size()) + "...", 3);   // genetree.rs:142

@@ -3,6 +3,8 @@
 // integers as integers, fp64 values by their bits.
 #pragma once
 #include <cstdint>
+#include <string>
+#include <vector>
 
 #include "uc_common.h"
 
@@ -12,6 +14,7 @@
 #pragma clang fp contract(off)
 #endif
 #if defined(__HIPCC__)
+#include <hip/hip_runtime.h>      // __umul64hi of the draws
 #define UC_NJ_HD __host__ __device__
 #else
 #define UC_NJ_HD
@@ -74,5 +77,74 @@ UC_NJ_HD inline void nj_root3(double dab, double dac, double dbc, double *len) {
 void nj_join_validate(const NjJoinArgs &a);
 void nj_join_host(const NjJoinArgs &a);
 void nj_join_device(int device, const NjJoinArgs &a);
+
+// ---- the pieces of uc_nj_host.cpp that the bootstrap (uc_nj_boot_host.cpp) builds on
+// comp / diff of every row pair over n rows of `words` 64-bit words of codes (eight columns a word, padding 0), spread over `threads`
+void nj_count_codes(const uint64_t *code, uint64_t n, uint64_t words, uint32_t threads, uint32_t *comp, uint32_t *diff);
+// the Newick line; support (nullable) [n - 3] with n_rep > 0 labels node n + s with the percentage (200 support[s] + n_rep) div (2 n_rep)
+std::string nj_newick_line(const char *const *names, uint32_t n, const uint32_t *ja, const uint32_t *jb, const double *la, const double *lb, const uint32_t *root,
+                           const double *rlen, const uint32_t *support, uint32_t n_rep);
+// the tree of the alignment itself, as uc_tree_infer computes it (phases 0 .. 3 of st.seconds), and the files uc_tree_infer writes for it
+struct NjMainTree {
+    std::vector<std::string> names;
+    uint32_t n = 0, model = 0;
+    uint64_t w = 0;
+    int device = -1, threads = 1;
+    bool on_host = false, dump = false;
+    std::vector<uint8_t> cells;                      // n x w
+    std::vector<uint32_t> comp, diff, ja, jb;
+    std::vector<double> D, la, lb;
+    uint32_t root[3];
+    double rlen[3];
+};
+void nj_main_tree(const char *msa_fasta, const char *model_name, const uc_opts *o, NjMainTree &T, uc_nj_stats &st);
+void nj_write_main_tree(const char *out_nwk, const NjMainTree &T, const uint32_t *support, uint32_t n_rep);
+
+// ---- UC-N/B: bootstrap support.  Draws: SplitMix64's finaliser over (seed, replicate, draw); a draw depends on nothing else
+constexpr uint32_t NJ_BOOT_MAX_REPS = 100000;
+constexpr uint32_t NJ_LDS_ROWS = 128;                          // the largest n whose join loop runs in LDS: n (n | 1) doubles and the vectors fit 160 KiB
+constexpr uint64_t NJ_GOLDEN = 0x9E3779B97F4A7C15ull;
+UC_NJ_HD inline uint64_t nj_mix(uint64_t z) {
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+UC_NJ_HD inline uint64_t nj_boot_key(uint64_t seed, uint32_t rep) { return nj_mix(seed + NJ_GOLDEN * ((uint64_t)rep + 1)); }
+UC_NJ_HD inline uint64_t nj_boot_mulhi(uint64_t a, uint64_t b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __umul64hi(a, b);
+#else
+    return (uint64_t)(((unsigned __int128)a * b) >> 64);
+#endif
+}
+UC_NJ_HD inline uint32_t nj_boot_col(uint64_t key, uint64_t t, uint64_t w) { return (uint32_t)nj_boot_mulhi(nj_mix(key + NJ_GOLDEN * (t + 1)), w); }
+
+struct NjBootCountArgs {
+    uint32_t n;
+    uint64_t w;
+    const uint8_t *cells;         // n x w bytes, row-major
+    uint64_t seed;
+    uint32_t rep0, n_rep;         // replicates rep0 .. rep0 + n_rep - 1
+    uint32_t threads;             // host twin only (0 = 1)
+    uint32_t *comp, *diff;        // [n_rep][n (n - 1) / 2]
+};
+void nj_boot_counts_validate(const NjBootCountArgs &a);
+void nj_boot_counts_host(const NjBootCountArgs &a);
+void nj_boot_counts_device(int device, const NjBootCountArgs &a);
+
+struct NjJoinBatchArgs {
+    uint32_t n, n_rep;
+    const double *D;              // [n_rep][n][n], not modified
+    uint32_t *join_a, *join_b;    // [n_rep][n - 3]
+    double *len_a, *len_b;        // [n_rep][n - 3]
+    uint32_t *root_node;          // [n_rep][3]
+    double *root_len;             // [n_rep][3]
+    uint32_t threads;             // host twin only (0 = 1)
+};
+void nj_join_batch_validate(const NjJoinBatchArgs &a);
+void nj_join_batch_host(const NjJoinBatchArgs &a);
+void nj_join_batch_device(int device, const NjJoinBatchArgs &a);
+// UC_TREE_BUDGET_BYTES, as nj_counts_device reads it (default 512 MiB, at least 1)
+uint64_t nj_tree_budget();
 
 }  // namespace uc

@@ -45,24 +45,28 @@ void nj_counts_host(const NjCountArgs &a) {
         const uint8_t *c = a.cells + i * w;
         for (uint64_t x = 0; x < w; x++) o[x] = nj_code(c[x]);
     }
+    nj_count_codes(code.data(), n, words, a.threads, a.comp, a.diff);
+}
+
+void nj_count_codes(const uint64_t *code, uint64_t n, uint64_t words, uint32_t threads, uint32_t *comp_out, uint32_t *diff_out) {
     std::atomic<uint64_t> next{0};
     auto work = [&] {
         for (uint64_t i; (i = next.fetch_add(1)) + 1 < n;) {
-            const uint64_t *x = code.data() + i * words;
+            const uint64_t *x = code + i * words;
             uint64_t k = i * n - i * (i + 1) / 2;
             for (uint64_t j = i + 1; j < n; j++, k++) {
-                const uint64_t *y = code.data() + j * words;
+                const uint64_t *y = code + j * words;
                 uint64_t comp = 0, diff = 0;
                 for (uint64_t t = 0; t < words; t++) {
                     const uint64_t m = (x[t] + K7F) & (y[t] + K7F) & K80;
                     comp += (uint64_t)__builtin_popcountll(m);
                     diff += (uint64_t)__builtin_popcountll(m & ((x[t] ^ y[t]) + K7F));
                 }
-                a.comp[k] = (uint32_t)comp; a.diff[k] = (uint32_t)diff;
+                comp_out[k] = (uint32_t)comp; diff_out[k] = (uint32_t)diff;
             }
         }
     };
-    const uint32_t nt = std::max<uint32_t>(1, std::min<uint32_t>(a.threads, a.n));
+    const uint32_t nt = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(threads, n));
     std::vector<std::thread> pool;
     for (uint32_t t = 1; t < nt; t++) pool.emplace_back(work);
     work();
@@ -172,12 +176,20 @@ void append_len(std::string &out, double v) {
     out += b;
 }
 
-std::string newick(const char *const *names, uint32_t n, const uint32_t *ja, const uint32_t *jb, const double *la, const double *lb, const uint32_t *root,
-                   const double *rlen) {
+}  // namespace
+
+std::string nj_newick_line(const char *const *names, uint32_t n, const uint32_t *ja, const uint32_t *jb, const double *la, const double *lb, const uint32_t *root,
+                           const double *rlen, const uint32_t *support, uint32_t n_rep) {
     check_rows(n);
     need(names, "names"); need(root, "root_node"); need(rlen, "root_len");
     const uint32_t steps = n > 3 ? n - 3 : 0, kids = n == 2 ? 2 : 3;
     if (steps) { need(ja, "join_a"); need(jb, "join_b"); need(la, "len_a"); need(lb, "len_b"); }
+    const bool labels = steps && n_rep > 0;      // UC-N/B: the root carries none
+    if (labels) {
+        need(support, "support");
+        if (n_rep > NJ_BOOT_MAX_REPS) fail(UC_ERR_ARGS, "nj: %u replicates; 0 .. %u", n_rep, NJ_BOOT_MAX_REPS);
+        for (uint32_t s = 0; s < steps; s++) if (support[s] > n_rep) fail(UC_ERR_ARGS, "nj: support %u of %u replicates at join %u", support[s], n_rep, s);
+    }
     for (uint32_t i = 0; i < n; i++) need(names[i], "a name");
     // every node hangs from exactly one parent, and a step joins nodes that exist before it
     std::vector<uint8_t> used((size_t)n + steps, 0);
@@ -200,13 +212,18 @@ std::string newick(const char *const *names, uint32_t n, const uint32_t *ja, con
             const uint32_t s = f.v - n;
             if (f.st == 0) { out += '('; st.back().st = 1; st.push_back(Frame{ja[s], 0}); }
             else if (f.st == 1) { append_len(out, la[s]); out += ','; st.back().st = 2; st.push_back(Frame{jb[s], 0}); }
-            else { append_len(out, lb[s]); out += ')'; st.pop_back(); }
+            else {
+                append_len(out, lb[s]); out += ')'; st.pop_back();
+                if (labels) out += std::to_string((200ull * support[s] + n_rep) / (2ull * n_rep));      // the percentage, rounded half up
+            }
         }
         append_len(out, rlen[t]);
     }
     out += ");\n";
     return out;
 }
+
+namespace {
 
 struct Msa { std::vector<std::string> names; std::vector<std::string> rows; };
 
@@ -235,71 +252,85 @@ Msa read_msa(const std::string &path) {
     return M;
 }
 
-void tree_infer(const char *msa_fasta, const char *out_nwk, const char *model_name, const uc_opts *o, uc_nj_stats *st_out) {
-    int device = -1, threads = 1;
+}  // namespace
+
+void nj_main_tree(const char *msa_fasta, const char *model_name, const uc_opts *o, NjMainTree &T, uc_nj_stats &st) {
     if (o) {
         if (o->struct_size != sizeof(uc_opts)) fail(UC_ERR_ARGS, "uc_opts.struct_size mismatch (%u != %zu)", o->struct_size, sizeof(uc_opts));
-        device = o->device; threads = o->threads > 0 ? o->threads : 1;
+        T.device = o->device; T.threads = o->threads > 0 ? o->threads : 1;
     }
-    uint32_t model = UC_NJ_MODEL_KIMURA;
-    if (model_name && !strcmp(model_name, "p")) model = UC_NJ_MODEL_P;
+    T.model = UC_NJ_MODEL_KIMURA;
+    if (model_name && !strcmp(model_name, "p")) T.model = UC_NJ_MODEL_P;
     else if (model_name && strcmp(model_name, "kimura") != 0) fail(UC_ERR_ARGS, "nj: unknown model '%s' (kimura, p)", model_name);
-    const bool on_host = env_is_one("UC_TREE_HOST"), dump = env_is_one("UC_TREE_DUMP");
-    uc_nj_stats st;
+    T.on_host = env_is_one("UC_TREE_HOST"); T.dump = env_is_one("UC_TREE_DUMP");
     memset(&st, 0, sizeof st);
     Timer t_part;
     auto lap = [&](int phase) { st.seconds[phase] += t_part.seconds(); t_part = Timer(); };
 
-    const Msa M = read_msa(msa_fasta);
+    Msa M = read_msa(msa_fasta);
     if (M.rows.size() < NJ_MIN_ROWS || M.rows.size() > NJ_MAX_ROWS)
         fail(UC_ERR_ARGS, "%s: %zu rows; a tree needs %u .. %u", msa_fasta, M.rows.size(), NJ_MIN_ROWS, NJ_MAX_ROWS);
     const uint32_t n = (uint32_t)M.rows.size();
     const uint64_t w = M.rows[0].size();
     for (uint32_t i = 1; i < n; i++)
         if (M.rows[i].size() != w) fail(UC_ERR_ARGS, "%s: row %s has %zu columns, the first row %llu", msa_fasta, M.names[i].c_str(), M.rows[i].size(), (unsigned long long)w);
-    std::vector<uint8_t> cells((size_t)n * std::max<uint64_t>(w, 1));
-    for (uint32_t i = 0; i < n; i++) memcpy(cells.data() + (size_t)i * w, M.rows[i].data(), w);
+    T.n = n; T.w = w;
+    T.cells.resize((size_t)n * std::max<uint64_t>(w, 1));
+    for (uint32_t i = 0; i < n; i++) memcpy(T.cells.data() + (size_t)i * w, M.rows[i].data(), w);
+    T.names = std::move(M.names);
     const uint64_t tri = (uint64_t)n * (n - 1) / 2;
-    std::vector<uint32_t> comp(tri), diff(tri);
-    const NjCountArgs ca{n, w, cells.data(), (uint32_t)threads, comp.data(), diff.data()};
+    T.comp.resize(tri); T.diff.resize(tri);
+    const NjCountArgs ca{n, w, T.cells.data(), (uint32_t)T.threads, T.comp.data(), T.diff.data()};
     nj_counts_validate(ca);
     st.n_rows = n; st.n_columns = w;
     lap(0);
-    if (on_host) nj_counts_host(ca); else nj_counts_device(device, ca);
+    if (T.on_host) nj_counts_host(ca); else nj_counts_device(T.device, ca);
     lap(1);
-    std::vector<double> D((size_t)n * n);
+    T.D.resize((size_t)n * n);
     uint64_t counts[2];
-    nj_distances_host(comp.data(), diff.data(), n, model, D.data(), counts);
+    nj_distances_host(T.comp.data(), T.diff.data(), n, T.model, T.D.data(), counts);
     st.n_pairs_incomparable = counts[0]; st.n_pairs_capped = counts[1];
     lap(2);
     const uint32_t steps = n > 3 ? n - 3 : 0;
-    std::vector<uint32_t> ja(std::max<uint32_t>(steps, 1)), jb(std::max<uint32_t>(steps, 1));
-    std::vector<double> la(std::max<uint32_t>(steps, 1)), lb(std::max<uint32_t>(steps, 1));
-    uint32_t root[3];
-    double rlen[3];
-    const NjJoinArgs ja_args{n, D.data(), ja.data(), jb.data(), la.data(), lb.data(), root, rlen};
-    if (on_host) nj_join_host(ja_args); else nj_join_device(device, ja_args);      // D comes from nj_distances_host: nothing nj_join_validate could refuse
-    for (uint32_t s = 0; s < steps; s++) st.n_lengths_clamped += (la[s] == 0.0) + (lb[s] == 0.0);
-    for (uint32_t t = 0; t < (n == 2 ? 2u : 3u); t++) st.n_lengths_clamped += rlen[t] == 0.0;
+    T.ja.resize(std::max<uint32_t>(steps, 1)); T.jb.resize(std::max<uint32_t>(steps, 1));
+    T.la.resize(std::max<uint32_t>(steps, 1)); T.lb.resize(std::max<uint32_t>(steps, 1));
+    const NjJoinArgs ja_args{n, T.D.data(), T.ja.data(), T.jb.data(), T.la.data(), T.lb.data(), T.root, T.rlen};
+    if (T.on_host) nj_join_host(ja_args); else nj_join_device(T.device, ja_args);      // D comes from nj_distances_host: nothing nj_join_validate could refuse
+    for (uint32_t s = 0; s < steps; s++) st.n_lengths_clamped += (T.la[s] == 0.0) + (T.lb[s] == 0.0);
+    for (uint32_t t = 0; t < (n == 2 ? 2u : 3u); t++) st.n_lengths_clamped += T.rlen[t] == 0.0;
     lap(3);
+}
+
+void nj_write_main_tree(const char *out_nwk, const NjMainTree &T, const uint32_t *support, uint32_t n_rep) {
+    const uint32_t n = T.n;
     std::vector<const char *> names(n);
-    for (uint32_t i = 0; i < n; i++) names[i] = M.names[i].c_str();
-    write_file(out_nwk, newick(names.data(), n, ja.data(), jb.data(), la.data(), lb.data(), root, rlen));
-    if (dump) {
+    for (uint32_t i = 0; i < n; i++) names[i] = T.names[i].c_str();
+    write_file(out_nwk, nj_newick_line(names.data(), n, T.ja.data(), T.jb.data(), T.la.data(), T.lb.data(), T.root, T.rlen, support, n_rep));
+    if (T.dump) {
         std::string txt;
         char b[128];
         uint64_t k = 0;
         for (uint32_t i = 0; i < n; i++)
             for (uint32_t j = i + 1; j < n; j++, k++) {
-                snprintf(b, sizeof b, "%u\t%u\t%u\t%u\t%.17g\n", i, j, comp[k], diff[k], D[(size_t)i * n + j]);
+                snprintf(b, sizeof b, "%u\t%u\t%u\t%u\t%.17g\n", i, j, T.comp[k], T.diff[k], T.D[(size_t)i * n + j]);
                 txt += b;
             }
         write_file(std::string(out_nwk) + ".dist.tsv", txt);
     }
-    lap(4);
+}
+
+namespace {
+
+void tree_infer(const char *msa_fasta, const char *out_nwk, const char *model_name, const uc_opts *o, uc_nj_stats *st_out) {
+    NjMainTree T;
+    uc_nj_stats st;
+    nj_main_tree(msa_fasta, model_name, o, T, st);
+    Timer t_write;
+    nj_write_main_tree(out_nwk, T, nullptr, 0);
+    st.seconds[4] += t_write.seconds();
     if (getenv("UC_TIMING"))
         fprintf(stderr, "unicore-cluster[timing]: tree_infer (%s): %u rows x %llu columns: read %.3f s, counts %.3f s, transform %.3f s, joins %.3f s, write %.3f s\n",
-                on_host ? "host" : "device", n, (unsigned long long)w, st.seconds[0], st.seconds[1], st.seconds[2], st.seconds[3], st.seconds[4]);
+                T.on_host ? "host" : "device", T.n, (unsigned long long)T.w, st.seconds[0], st.seconds[1], st.seconds[2], st.seconds[3], st.seconds[4]);
     if (st_out) *st_out = st;
 }
 
@@ -349,7 +380,7 @@ int uc_nj_join_dev(int32_t device, uint32_t n, const double *D, uint32_t *join_a
 int uc_nj_newick(const char *const *names, uint32_t n, const uint32_t *join_a, const uint32_t *join_b, const double *len_a, const double *len_b,
                  const uint32_t *root_node, const double *root_len, char *buf, uint64_t cap, uint64_t *need_out) {
     return guard([&] {
-        const std::string s = newick(names, n, join_a, join_b, len_a, len_b, root_node, root_len);
+        const std::string s = nj_newick_line(names, n, join_a, join_b, len_a, len_b, root_node, root_len, nullptr, 0);
         if (need_out) *need_out = s.size();
         if (!buf && !cap) return;
         if (!buf || cap < s.size() + 1) fail(UC_ERR_ARGS, "nj: the tree takes %zu bytes and the NUL, the buffer holds %llu", s.size(), (unsigned long long)cap);
