@@ -1,4 +1,5 @@
 """Shared helpers for the tests: seeded synthetic DBs, oracle<->engine option mirroring."""
+import ctypes as C
 import os
 import subprocess
 
@@ -110,7 +111,7 @@ def write_db(prefix, s3, sa, names=None):
 def oracle_params(O, opts=""):
     """Mirror a Foldseek-style option string onto oracle params (test-side restatement of the option
     semantics: -c, --cov-mode, -e, -s/--k-score, --max-seqs, --min-ungapped-score ...)."""
-    kw = {}
+    kw, mats = {}, {}
     tok = opts.split()
     i = 0
     sens = 4.0
@@ -134,14 +135,23 @@ def oracle_params(O, opts=""):
         elif f == "--comp-bias-corr": kw["_cb"] = int(v)
         elif f == "--comp-bias-corr-scale": kw["_cbs"] = float(v)
         elif f == "--length-gate": kw["len_gate"] = int(v)     # rule UC-1/L
+        elif f == "--mat3di": mats["S3"] = v                   # custom matrix files: the same file the engine gets, read by the oracle's own loader
+        elif f == "--mat-aa": mats["SA"] = v
+        elif f == "--spaced-kmer-pattern": kw["pattern"] = v
         elif f in ("--sw-kernel", "--sym-dedup"): pass      # engine-side execution choices, no effect on results
         else: raise ValueError(f)
         i += 2
     cb, cbs = kw.pop("_cb", 0), kw.pop("_cbs", 1.0)
     if cb:
         kw["comp_bias_milli"] = int(round(cbs * 1000))       # rule UC-1/B: scale in thousandths
+    bf = {"S3": kw.pop("bit_factor_3di", 0.0) if "S3" in mats else 0.0, "SA": kw.pop("bit_factor_aa", 0.0) if "SA" in mats else 0.0}
     p = O.default_params(**kw)
-    if kscore is None:
+    L = O.lib()
+    for track, path in mats.items():                          # load, then rescale by the file's own lambda: the engine's order (finalize_params)
+        assert L.uco_load_matrix(path.encode(), getattr(p, track)) == 0, path
+        if bf[track] > 0:
+            assert L.uco_rescale_matrix(C.addressof(getattr(p, track)), bf[track], L.uco_matrix_header_lambda(path.encode())) == 0
+    if kscore is None:                                        # derived from the LOADED matrix's diagonal
         diag = sum(p.S3[a * 21 + a] for a in range(20))
         kscore = int(np.floor(6 * diag / 20.0 + 3.0 - 2.0 * sens + 0.5))
     p.kmer_thr = kscore

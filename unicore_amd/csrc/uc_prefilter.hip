@@ -212,7 +212,7 @@ __global__ void __launch_bounds__(256) sim_runs_kernel(const DeviceDb db, KmerCf
     volatile uint32_t *qv = s_qv[wv], *qp = s_qp[wv], *qm = s_qm[wv];
     volatile uint32_t *pc = s_pc[wv], *pp = s_pp[wv];
     volatile uint64_t *pr = s_pr[wv];
-    const int thr = cfg.thr;
+    const int thr = cfg.thr, thrb = thr + 256;     // thrb: the threshold against the biased fields of restpack
 
     auto flush_runs = [&]() {   // whole wave
         const uint32_t n = *vn;
@@ -298,7 +298,7 @@ __global__ void __launch_bounds__(256) sim_runs_kernel(const DeviceDb db, KmerCf
         uint32_t lc = 0;                           // leaves of the work item in hand
         bool has_item = false;
         int L = 0, scur = 0;
-        uint64_t restpack = 0;                     // rest[m] (m = 1..6) in 8-bit fields, biased by 64
+        uint64_t restpack = 0;                     // rest[m] (m = 1..6) in 10-bit fields, biased by 256: five letters of a matrix in [-48, 48] add -240 .. 240
         for (;;) {
             // ---- decode the next 64 positions together (sequence search + letter loads: ~10 us of dependent loads that
             //      must not sit in front of every single hand-out) ----
@@ -325,7 +325,7 @@ __global__ void __launch_bounds__(256) sim_runs_kernel(const DeviceDb db, KmerCf
                         int rest = 0;
 #pragma unroll
                         for (int L_ = K - 1; L_ >= 0; L_--) {                         // level L_ decides position K - 1 - L_
-                            rp |= (uint64_t)(uint32_t)(rest + 64) << (8 * L_);      // field L_ holds the best score the levels behind L_ can still add
+                            rp |= (uint64_t)(uint32_t)(rest + 256) << (10 * L_);    // field L_ holds the best score the levels behind L_ can still add
                             rest += tab.rowmax[c[K - 1 - L_]];
                             cp |= c[K - 1 - L_] << (5 * L_);
                         }
@@ -373,10 +373,10 @@ __global__ void __launch_bounds__(256) sim_runs_kernel(const DeviceDb db, KmerCf
                 const int sc1 = tab.sc[a][kk], sc2 = tab.sc[a2][kk2];
                 const uint32_t o1 = tab.ord[a][kk], o2 = tab.ord[a2][kk2];
                 const uint32_t mulL = s_mul[L], mulM = s_mul[Lm];
-                const int restn = (int)((restpack >> (8 * L)) & 0xffu) - 64;
+                const int restb = (int)((restpack >> (10 * L)) & 0x3ffu);       // still biased: compared against thr + 256
                 const int cand = scur + sc1;
                 const bool act = !idle;
-                const bool ok = act && k < (uint32_t)KA && cand + restn >= thr;
+                const bool ok = act && k < (uint32_t)KA && cand + restb >= thrb;
                 const bool push = ok && L < K - 2, pop = act && !ok && L > 0;
                 leaf = ok && L == K - 2;                                        // the last level is taken in one step: every letter that keeps cand + S >= thr
                 leafv = vcur + o1 * mulL;
