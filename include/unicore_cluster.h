@@ -245,6 +245,9 @@ void uc_engine_reset_stats(uc_engine *e);
 /* the prefilter's on-chip diagonal selection since the last reset: out[0] queries it took, out[1] queries of the double-hit path, out[2] surviving
  * keys it took, out[3] surviving keys (= n_filtered_hits of that path); UC_TD_ONCHIP=0 leaves [0] and [2] at 0 */
 int uc_engine_td_onchip(const uc_engine *e, uint64_t *out /* 4 */);
+/* the packed gapped kernel since the last reset: out[0] class launches in which a workgroup served several tasks (queries' pair lists), out[1] the
+ * tasks of those launches; UC_SW_TASK_QUERIES=1 leaves both at 0.  Not part of uc_stats. */
+int uc_engine_sw_task_queries(const uc_engine *e, uint64_t *out /* 2 */);
 
 /* Kernel-level entry of the linear-time pre-step (E8a, uc_linclust.hip) on the engine's database; test support, uc_stats is untouched.
  * m <= 0: the engine's --kmer-per-seq, otherwise m in [1,1000] replaces it for this call.  install = 0: *n_out = number of sorted unique

@@ -6,7 +6,7 @@ rows = list(csv.DictReader(open(sys.argv[1])))
 mode = int(sys.argv[2]) if len(sys.argv) > 2 else 4
 ks = []
 for r in rows:
-    m = re.search(r"sw_pk_kernel<(\d+), (\d+), (\d+), (\d+)>", r["Kernel_Name"])
+    m = re.search(r"sw_pk_kernel<(\d+), (\d+), (\d+), (\d+)(?:, \d+)?>", r["Kernel_Name"])
     if m and int(m.group(3)) == mode:
         ks.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), int(m.group(1)), int(m.group(2)), int(r.get("Grid_Size_X", r.get("Grid_Size", 0)) or 0),
                    int(r.get("Workgroup_Size_X", r.get("Workgroup_Size", 0)) or 0), int(r.get("LDS_Block_Size", 0) or 0), r.get("Queue_Id", ""), r.get("Stream_Id", "")))

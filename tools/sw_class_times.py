@@ -6,7 +6,7 @@ rows = list(csv.DictReader(open(sys.argv[1].rstrip("/") + "/out_kernel_stats.csv
 div = float(sys.argv[2]) if len(sys.argv) > 2 else 1.0
 agg = collections.defaultdict(float); bymode = collections.defaultdict(float); byG = collections.defaultdict(float)
 for r in rows:
-    m = re.search(r"sw_pk_kernel<(\d+), (\d+), (\d+), (\d+)>", r["Name"])
+    m = re.search(r"sw_pk_kernel<(\d+), (\d+), (\d+), (\d+)(?:, \d+)?>", r["Name"])
     if not m:
         continue
     G, R, M, NW = map(int, m.groups()); t = int(r["TotalDurationNs"]) / 1e6 / div

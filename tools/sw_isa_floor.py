@@ -10,7 +10,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def kernel_body(asm, G, R, mode, NW):
-    name = "_ZN2uc12sw_pk_kernelILi%dELi%dELi%dELi%dEEEvNS_6SwArgsE" % (G, R, mode, NW)
+    name = "_ZN2uc12sw_pk_kernelILi%dELi%dELi%dELi%dELi1EEEvNS_6SwArgsE" % (G, R, mode, NW)   # K = 1
     out, on = [], False
     for l in asm:
         if l.startswith(name + ":"):

@@ -89,7 +89,7 @@ SYMBOLS = (
     "uc_engine_ungapped_batch", "uc_engine_ungapped_select", "uc_engine_ungapped_all", "uc_engine_sw_batch", "uc_engine_sw_pass", "uc_engine_sw_pass2", "uc_engine_backtraces_size", "uc_engine_backtraces_get",
     "uc_backtrace_render", "uc_format_output_check", "uc_engine_tb_emit_pass", "uc_abi_version", "uc_stats_size", "uc_set_round_hook",
     "uc_t5_gemm_variant", "uc_t5_kernel_gemm", "uc_t5_kernel_rmsnorm", "uc_t5_kernel_attention", "uc_t5_kernel_cnn_head", "uc_t5_bias_table",
-    "uc_cluster_graph", "uc_engine_cluster_graph", "uc_engine_reassign", "uc_engine_td_onchip", "uc_engine_linclust_pairs",
+    "uc_cluster_graph", "uc_engine_cluster_graph", "uc_engine_reassign", "uc_engine_td_onchip", "uc_engine_sw_task_queries", "uc_engine_linclust_pairs",
     "uc_profile_count", "uc_profile_count_dev", "uc_profile",
     "uc_msa_center", "uc_msa_center_dev", "uc_msa_star", "uc_msa_star_dev", "uc_msa_filter", "uc_msa_filter_dev", "uc_tree",
     "uc_nj_counts", "uc_nj_counts_dev", "uc_nj_distances", "uc_nj_join", "uc_nj_join_dev", "uc_nj_newick", "uc_nj_geometry", "uc_tree_infer",
@@ -165,6 +165,7 @@ def lib():
     L.uc_engine_reset_stats.argtypes = [vp]
     L.uc_engine_reset_stats.restype = None
     L.uc_engine_td_onchip.argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.uc_engine_sw_task_queries.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.uc_engine_linclust_pairs.argtypes = [vp, i32, i32, vp, u64, C.POINTER(u64)]
     L.uc_setcover.argtypes = [u32, vp, u64, vp]
     L.uc_cluster_graph.argtypes = [u32, vp, u64, vp, i32, vp]
@@ -938,6 +939,10 @@ class Engine:
         td = (C.c_uint64 * 4)()
         _check(lib().uc_engine_td_onchip(self._h, td))
         d["td_onchip_queries"], d["td_onchip_keys"] = int(td[0]), int(td[2])
+        # class launches of the packed gapped kernel that served several tasks per workgroup, and their tasks (uc_engine_sw_task_queries)
+        mq = (C.c_uint64 * 2)()
+        _check(lib().uc_engine_sw_task_queries(self._h, mq))
+        d["sw_multiquery_launches"], d["sw_multiquery_tasks"] = int(mq[0]), int(mq[1])
         return d
 
     def reset_stats(self):

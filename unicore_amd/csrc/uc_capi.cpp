@@ -361,6 +361,11 @@ void uc_engine_reset_stats(uc_engine *e) {
     memset(&s, 0, sizeof s);
     s.n_seqs = ns; s.n_residues = nr;
     for (uint64_t &x : e->e->td_onchip) x = 0;
+    for (uint64_t &x : e->e->sw_task_queries) x = 0;
+}
+
+int uc_engine_sw_task_queries(const uc_engine *e, uint64_t *out) {
+    return guard([&] { require(e, "engine"); require(out, "out"); for (int i = 0; i < 2; i++) out[i] = e->e->sw_task_queries[i]; });
 }
 
 int uc_engine_td_onchip(const uc_engine *e, uint64_t *out) {

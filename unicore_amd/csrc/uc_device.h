@@ -61,6 +61,7 @@ struct SwArgs {
     // packed modes 4/6 (optional, null = not written): the end under the other tie-break order - first optimal row, then first column - which is the
     // answer of the transposed DP (the mirror of a mutual hit).  Last in the struct: the other kernels' argument offsets stay where they were.
     int32_t *oqe2 = nullptr, *ote2 = nullptr;
+    uint32_t n_tasks = 0;      // packed kernel with several tasks per workgroup only (set by its launcher): tasks of the launch
 };
 
 constexpr int SW_MAX_ROWS = 2048;   // largest single-strip class (G=64, R=32)
@@ -121,7 +122,8 @@ __device__ __forceinline__ void block_add2(unsigned long long va, unsigned long 
 
 // host launchers (uc_sw.hip / uc_prefilter.hip)
 void launch_sw_class(int G, int R, int mode, const SwArgs &a, uint32_t n_tasks, hipStream_t s);
-void launch_sw_pk_class(int G, int R, int mode, const SwArgs &a, uint32_t n_tasks, hipStream_t s);
+// kmax > 1: the class may serve several tasks per workgroup (tcap = pairs per task of the class at most); returns the tasks per workgroup it launched with
+int launch_sw_pk_class(int G, int R, int mode, const SwArgs &a, uint32_t n_tasks, hipStream_t s, int kmax = 1, uint32_t tcap = 0);
 // queries beyond the systolic classes, MODE 0 / 1 / 2 / 3: row-blocked systolic kernel (uc_sw_long.hip); a.tasks = the long-query
 // tasks (<= SW_LONG_TASK_PAIRS pairs each), pair_base = plan index of the first long-query pair, work = 2 (MODE 3: 4) x stride ints per pair
 constexpr uint32_t SW_LONG_TASK_PAIRS = 8;

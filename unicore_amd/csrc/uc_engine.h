@@ -316,6 +316,7 @@ struct Engine {
     void prefilter_cells(uint32_t tbegin, uint32_t tend, const std::vector<std::pair<uint32_t, uint32_t>> &others);
     PrefilterScratch *pre = nullptr;                       // work buffers kept between prefilter calls
     AlignScratch *aln = nullptr;                           // ... and between align calls
+    uint64_t sw_task_queries[2] = {0, 0};                  // packed gapped kernel since the last reset: class launches with several tasks per workgroup, tasks they served
     uint64_t td_onchip[4] = {0, 0, 0, 0};                  // double-hit path since the last reset: queries taken by td_select_kernel, queries seen, surviving keys taken, surviving keys
     uint64_t last_align_hits = 0;                          // listed pairs of the last align() whose buffers `aln` still holds (0 after the set was given back)
     void drop_scratch();                                   // parks both (results stay): virtual-rank emulation

@@ -17,20 +17,20 @@ void launch_sw_class(int G, int R, int mode, const SwArgs &a, uint32_t n_tasks, 
     else launch_sw_class_m3(G, R, a, n_tasks, s);
 }
 
-void launch_sw_pk_class_m0(int G, int R, const SwArgs &a, uint32_t n_tasks, hipStream_t s);
-void launch_sw_pk_class_m1(int G, int R, const SwArgs &a, uint32_t n_tasks, hipStream_t s);
-void launch_sw_pk_class_m2(int G, int R, const SwArgs &a, uint32_t n_tasks, hipStream_t s);
-void launch_sw_pk_class_m4(int G, int R, const SwArgs &a, uint32_t n_tasks, hipStream_t s);
-void launch_sw_pk_class_m6(int G, int R, const SwArgs &a, uint32_t n_tasks, hipStream_t s);
-void launch_sw_pk_class_m7(int G, int R, const SwArgs &a, uint32_t n_tasks, hipStream_t s);
-void launch_sw_pk_class(int G, int R, int mode, const SwArgs &a, uint32_t n_tasks, hipStream_t s) {
-    if (n_tasks == 0) return;
-    if (mode == 0) launch_sw_pk_class_m0(G, R, a, n_tasks, s);
-    else if (mode == 1) launch_sw_pk_class_m1(G, R, a, n_tasks, s);
-    else if (mode == 2) launch_sw_pk_class_m2(G, R, a, n_tasks, s);
-    else if (mode == 4) launch_sw_pk_class_m4(G, R, a, n_tasks, s);
-    else if (mode == 6) launch_sw_pk_class_m6(G, R, a, n_tasks, s);
-    else launch_sw_pk_class_m7(G, R, a, n_tasks, s);
+int launch_sw_pk_class_m0(int G, int R, const SwArgs &a, uint32_t n_tasks, hipStream_t s, int kmax, uint32_t tcap);
+int launch_sw_pk_class_m1(int G, int R, const SwArgs &a, uint32_t n_tasks, hipStream_t s, int kmax, uint32_t tcap);
+int launch_sw_pk_class_m2(int G, int R, const SwArgs &a, uint32_t n_tasks, hipStream_t s, int kmax, uint32_t tcap);
+int launch_sw_pk_class_m4(int G, int R, const SwArgs &a, uint32_t n_tasks, hipStream_t s, int kmax, uint32_t tcap);
+int launch_sw_pk_class_m6(int G, int R, const SwArgs &a, uint32_t n_tasks, hipStream_t s, int kmax, uint32_t tcap);
+int launch_sw_pk_class_m7(int G, int R, const SwArgs &a, uint32_t n_tasks, hipStream_t s, int kmax, uint32_t tcap);
+int launch_sw_pk_class(int G, int R, int mode, const SwArgs &a, uint32_t n_tasks, hipStream_t s, int kmax, uint32_t tcap) {
+    if (n_tasks == 0) return 1;
+    if (mode == 0) return launch_sw_pk_class_m0(G, R, a, n_tasks, s, kmax, tcap);
+    if (mode == 1) return launch_sw_pk_class_m1(G, R, a, n_tasks, s, kmax, tcap);
+    if (mode == 2) return launch_sw_pk_class_m2(G, R, a, n_tasks, s, kmax, tcap);
+    if (mode == 4) return launch_sw_pk_class_m4(G, R, a, n_tasks, s, kmax, tcap);
+    if (mode == 6) return launch_sw_pk_class_m6(G, R, a, n_tasks, s, kmax, tcap);
+    return launch_sw_pk_class_m7(G, R, a, n_tasks, s, kmax, tcap);
 }
 
 // ---- device layout of the database (Engine::upload_db) ----

@@ -54,8 +54,16 @@ __device__ __forceinline__ uint32_t pk_max3(uint32_t a, uint32_t b, uint32_t c) 
     return r;
 }
 
-template <int G, int R, int MODE, int NW>
+// K > 1: slots of the K tasks one workgroup serves (K * tcap / 2 at most: the launcher checks) and how a table entry names one: task << 6 | slot
+constexpr int SW_MQ_SLOTS = 128;
+
+template <int G, int R, int MODE, int NW, int K = 1>
 __global__ void __launch_bounds__(NW * 64) sw_pk_kernel(const SwArgs a) {
+    // K = tasks per workgroup.  K = 1: one task, its slots in list order.  K > 1 (G < 64, not MODE 7): workgroup b serves the tasks [K b, K b + K) of the
+    // launch (the last one fewer), i.e. K neighbours of the plan's LPT order: one profile per task in LDS, and the lane groups pull the slots of ALL of them
+    // from one table sorted by step count, longest first.  With one short list per workgroup (configs[1]: 8 slots on 8 lane groups in the reversed-query and
+    // start passes) every wave issues for as long as its longest slot runs; K lists merged by length give every group several slots of similar length to even
+    // that out (tools/slot_balance.py, profiles/multi_query_tasks).  Pair order, results and counters are those of K = 1.
     // MODE 4 / 6 = MODE 0 / 2 with the optimum score of every pair KNOWN (a.pscore).  MODE 4 is the exact re-run of the
     // pairs whose end row was ambiguous; MODE 6 is THE start pass of the packed path (its optimum is the forward score).
     // No per-row maxima: the first step at which a lane's column maximum equals the known score is its first optimal
@@ -75,10 +83,15 @@ __global__ void __launch_bounds__(NW * 64) sw_pk_kernel(const SwArgs a) {
     constexpr int RW = (R + 3) / 4, BW = RW | 1, RSW = G * BW, NT = NW * 64;   // R % 4 == 2: the last profile dword is half used
     static_assert(R % 2 == 0 && R <= 32, "R must be even, <= 32");
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    static_assert(K == 1 || (K <= 4 && G < 64 && !TBB), "several tasks per workgroup: G < 64, not MODE 7");
+    constexpr int PB = 2 * SW_NLET * RSW;           // dwords of one task's profile
     uint32_t *P3 = lds, *PA = lds + SW_NLET * RSW;
-    uint32_t *slot_ctr = lds + 2 * SW_NLET * RSW;   // work counter of the task (one dword behind the profile)
+    uint32_t *slot_ctr = lds + K * PB;              // work counter of the workgroup (one dword behind the profiles)
+    // K > 1, behind the counter: (begin, count, query length, [task 0: slots of all tasks]) per task; the step count of every slot (<< 8 | its name); the slot table
+    [[maybe_unused]] uint32_t *tinfo = slot_ctr + 4, *sstep = tinfo + 4 * K;
+    [[maybe_unused]] uint8_t *stab = (uint8_t *)(sstep + SW_MQ_SLOTS);
 
-    const SwTask task = a.tasks[blockIdx.x];
+    const SwTask task = a.tasks[K * blockIdx.x];    // K > 1: the first of the workgroup's tasks
     const int tid = threadIdx.x, lane = tid & 63;
     const int g = lane % G;
     const uint32_t qoff = a.db.off[task.q];
@@ -106,8 +119,70 @@ __global__ void __launch_bounds__(NW * 64) sw_pk_kernel(const SwArgs a) {
         P3[c * RSW + gg * BW + k] = w3;
         PA[c * RSW + gg * BW + k] = wa;
     }
+    if constexpr (K > 1) {
+        // the other tasks' profiles (the loop above, one more index); every slot of the K tasks with its step count (entries in (task, slot) order); then
+        // the slots ranked by (step count descending, task, slot) into the table start_slot reads.  Both barriers stand before the slot loop: none inside it.
+        const uint32_t task0 = (uint32_t)K * blockIdx.x, nk = min((uint32_t)K, a.n_tasks - task0);
+        uint32_t base[K + 1];
+        base[0] = 0; base[1] = nslots;
+        if (tid == 0) { tinfo[0] = task.begin; tinfo[1] = task.count; tinfo[2] = (uint32_t)lq; }
+#pragma unroll
+        for (int t = 1; t < K; t++) {
+            base[t + 1] = base[t];
+            if ((uint32_t)t < nk) {
+                const SwTask tk = a.tasks[task0 + t];
+                const uint32_t qofft = a.db.off[tk.q];
+                const int lqt = (int)a.db.len[tk.q];
+                for (int idx = tid; idx < SW_NLET * G * RW; idx += NT) {
+                    const int c = idx / (G * RW), rem = idx % (G * RW), gg = rem / RW, k = rem % RW;
+                    uint32_t w3 = 0, wa = 0;
+#pragma unroll
+                    for (int b = 0; b < 4; b++) {
+                        const int row = gg * R + 4 * k + b;
+                        if (row < lqt && c < 21 && 4 * k + b < R) {
+                            const int qi = REVQ ? lqt - 1 - row : row;
+                            const int q3 = a.db.s3[qofft + qi], qa = a.db.sa[qofft + qi];
+                            w3 |= (uint32_t)(a.db.S3[q3 * 21 + c] + 64) << (8 * b);
+                            wa |= (uint32_t)(a.db.SA[qa * 21 + c] + 64) << (8 * b);
+                        }
+                    }
+                    P3[t * PB + c * RSW + gg * BW + k] = w3;
+                    PA[t * PB + c * RSW + gg * BW + k] = wa;
+                }
+                base[t + 1] += (tk.count + 1) >> 1;
+                if (tid == 0) { tinfo[4 * t] = tk.begin; tinfo[4 * t + 1] = tk.count; tinfo[4 * t + 2] = (uint32_t)lqt; }
+            }
+        }
+        const uint32_t mq_slots = min(base[K], (uint32_t)SW_MQ_SLOTS);   // slots of all tasks of the workgroup
+        if (tid == 0) tinfo[3] = mq_slots;
+        for (uint32_t e = tid; e < mq_slots; e += NT) {
+            uint32_t t = 0;
+#pragma unroll
+            for (int j = 1; j < K; j++) t += e >= base[j] ? 1u : 0u;
+            uint32_t eb = 0;
+#pragma unroll
+            for (int j = 1; j < K; j++) eb = t == (uint32_t)j ? base[j] : eb;
+            const SwTask tk = a.tasks[task0 + t];
+            const uint32_t i = e - eb, pA = tk.begin + 2 * i, pB = pA + (2 * i + 1 < tk.count ? 1u : 0u);
+            const int la = REVT ? a.pte[pA] + 1 : (int)a.db.len[a.pt[pA]], lb = REVT ? a.pte[pB] + 1 : (int)a.db.len[a.pt[pB]];
+            sstep[e] = ((uint32_t)((max(la, lb) + G) & ~1) << 8) | (t << 6) | i;
+        }
+    }
     if (tid == 0) *slot_ctr = 0;
     __syncthreads();
+    if constexpr (K > 1) {
+        const uint32_t mq_slots = tinfo[3];
+        for (uint32_t e = tid; e < mq_slots; e += NT) {
+            const uint32_t v = sstep[e], s = v >> 8;
+            uint32_t rank = 0;
+            for (uint32_t j = 0; j < mq_slots; j++) {
+                const uint32_t sj = sstep[j] >> 8;
+                rank += (sj > s || (sj == s && j < e)) ? 1u : 0u;
+            }
+            stab[rank] = (uint8_t)(v & 0xffu);
+        }
+        __syncthreads();
+    }
 
     // ---- per-group state (all group-uniform scalars live replicated in the group's lanes) ----
     uint32_t H[R], E[R], rowbest[(TRACK && !KNOWN) ? R : 1];   // E[r] holds the gap state ENTERING the next column (no separate H - open array)
@@ -170,7 +245,7 @@ __global__ void __launch_bounds__(NW * 64) sw_pk_kernel(const SwArgs a) {
             return r.a3 | (r.b3 << 16);
         }
     };
-    uint32_t off3 = (uint32_t)(g * BW) * 4u, offa = (uint32_t)(SW_NLET * RSW + g * BW) * 4u;
+    uint32_t off3 = (uint32_t)(g * BW) * 4u, offa = (uint32_t)(SW_NLET * RSW + g * BW) * 4u;   // K > 1: + the slot's task x profile bytes (start_slot)
     asm volatile("" : "+v"(off3), "+v"(offa));
     auto fetch_profile = [&]() __attribute__((always_inline)) {
         // byte offsets: letter * row-set stride + this lane's base in P3 / PA (two opaque registers, so that the PA base is
@@ -188,12 +263,22 @@ __global__ void __launch_bounds__(NW * 64) sw_pk_kernel(const SwArgs a) {
         if (g == 0) idx = atomicAdd(slot_ctr, 1u);
         if constexpr (G == 64) idx = (uint32_t)__builtin_amdgcn_readfirstlane((int)idx);   // wave-uniform from here on (SGPRs)
         else idx = (uint32_t)__shfl((int)idx, lane - g, 64);
-        active = idx < nslots;
+        if constexpr (K == 1) active = idx < nslots;
+        else active = idx < tinfo[3];
         if (!active) return;
+        [[maybe_unused]] uint32_t mq_begin = 0, mq_count = 0;
+        [[maybe_unused]] int mq_lq = 0;
+        if constexpr (K > 1) {   // the slot's own task: its pairs, its query length, its profile
+            const uint32_t code = stab[idx], t = code >> 6;
+            idx = code & 63u;
+            mq_begin = tinfo[4 * t]; mq_count = tinfo[4 * t + 1]; mq_lq = (int)tinfo[4 * t + 2];
+            off3 = (t * PB + (uint32_t)(g * BW)) * 4u;
+            offa = off3 + (uint32_t)(SW_NLET * RSW) * 4u;
+        }
         const uint32_t iA = 2 * idx, iB = iA + 1;
-        vB = iB < task.count;
-        gA = task.begin + iA;
-        gB = task.begin + (vB ? iB : iA);
+        vB = iB < (K == 1 ? task.count : mq_count);
+        gA = (K == 1 ? task.begin : mq_begin) + iA;
+        gB = (K == 1 ? task.begin : mq_begin) + (vB ? iB : iA);
         const uint32_t tA = a.pt[gA], tB = a.pt[gB];
         toffA = a.db.off[tA]; toffB = a.db.off[tB];
         tlenA = REVT ? a.pte[gA] + 1 : (int)a.db.len[tA];
@@ -225,8 +310,8 @@ __global__ void __launch_bounds__(NW * 64) sw_pk_kernel(const SwArgs a) {
                 mskA[k] = ma; mskB[k] = mb;
             }
         } else if constexpr (MASK) {
-            rowoffA = lq - 1 - a.pqe[gA];
-            rowoffB = lq - 1 - a.pqe[gB];
+            rowoffA = (K == 1 ? lq : mq_lq) - 1 - a.pqe[gA];
+            rowoffB = (K == 1 ? lq : mq_lq) - 1 - a.pqe[gB];
 #pragma unroll
             for (int k = 0; k < RW; k++) {
                 uint32_t ma = 0, mb = 0;
@@ -460,20 +545,50 @@ __global__ void __launch_bounds__(NW * 64) sw_pk_kernel(const SwArgs a) {
     }
 }
 
+// Tasks per workgroup of a class's multi-query variant (sw_pk_kernel<.., K>), 1 = the class has none.  A variant runs K times the waves of the class's
+// workgroup on K profiles, so LDS per wave stays what it is at K = 1; what decides K is that no class may hold a wave per SIMD less than at K = 1
+// (profiles/multi_query_tasks/kernel_resources.txt: -Rpass-analysis=kernel-resource-usage of every variant, w waves per SIMD):
+//  * G = 16 (2 waves at K = 1): K = 2 is a 4-wave workgroup, and w of them fit a CU whatever w is.  K = 4 (8 waves, for the classes whose w is even)
+//    was built and measured: no faster than K = 2 at configs[1] (profiles/multi_query_tasks/README.md), so one variant per class it is.
+//  * MODE 4 at R = 8, 10, 14: the K = 2 variant itself needs registers past a wave step (7 -> 6, 6 -> 5, 5 -> 4 waves): K = 1.  (16, 2): MODE 6 likewise
+//    (64 -> 65 VGPRs), and the class is all but empty.
+//  * G = 32: K profiles of 28-39 KB need 8-wave workgroups, and at 3 or 5 waves per SIMD (most of its classes in MODE 0 / 6) a CU would hold a wave per
+//    SIMD less; its modelled loss is 3 % (MODE 0) to 7.5 % against 7-39 % at G = 16.  G = 64: one group per wave, nothing to gain.
+//  * MODE 7: tb_size_kernel derives a pair's slot partner from the one-query task layout.
+constexpr int sw_pk_class_queries(int G, int R, int mode) {
+    if (G != 16 || R < 4) return 1;
+    if (mode == 4) return (R == 8 || R == 10 || R == 14) ? 1 : 2;
+    return (mode == 0 || mode == 1 || mode == 6) ? 2 : 1;
+}
+
+// kmax > 1: the class's lists are short (launch_plan) - serve sw_pk_class_queries() tasks per workgroup, if tcap (pairs per task of the class) lets the
+// slots of that many tasks fit the kernel's slot table.  Returns the tasks per workgroup of the launch.
 template <int MODE>
-void launch_sw_pk_class_mode(int G, int R, const SwArgs &a, uint32_t n_tasks, hipStream_t s) {
+int launch_sw_pk_class_mode(int G, int R, const SwArgs &a, uint32_t n_tasks, hipStream_t s, int kmax, uint32_t tcap) {
+#define UC_SW_LAUNCH(GG, RR, NW, KK)                                                                    \
+    {                                                                                                   \
+        const size_t lds = (size_t)KK * 2 * SW_NLET * GG * BW * 4 + 16 + (KK > 1 ? 16 * KK + 5 * SW_MQ_SLOTS : 0); \
+        static PerDeviceOnce once;                                                                      \
+        if (lds > 64 * 1024)                                                                            \
+            once([&] { (void)hipFuncSetAttribute((const void *)sw_pk_kernel<GG, RR, MODE, NW, KK>,       \
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); }); \
+        SwArgs ak = a;                                                                                  \
+        ak.n_tasks = n_tasks;                                                                           \
+        hipLaunchKernelGGL((sw_pk_kernel<GG, RR, MODE, NW, KK>), dim3((n_tasks + KK - 1) / KK), dim3(NW * 64), lds, s, ak); \
+        return KK;                                                                                      \
+    }
 #define UC_SW_CASE(GG, RR)                                                                              \
     if (G == GG && R == RR) {                                                                           \
         constexpr int BW = (((RR + 3) / 4) | 1);                                                        \
         /* small workgroups share one LDS profile; G = 64 with R < 14: the wave-wide classes of sparse known-score plans (table 3 of uc_sw_plan.hip) */ \
         constexpr int NW = GG == 16 ? 2 : (GG == 32 ? 4 : (RR < 14 ? 2 : 8));                           \
-        const size_t lds = (size_t)2 * SW_NLET * GG * BW * 4 + 16;                                      \
-        static PerDeviceOnce once;                                                                      \
-        if (lds > 64 * 1024)                                                                            \
-            once([&] { (void)hipFuncSetAttribute((const void *)sw_pk_kernel<GG, RR, MODE, NW>,           \
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); }); \
-        hipLaunchKernelGGL((sw_pk_kernel<GG, RR, MODE, NW>), dim3(n_tasks), dim3(NW * 64), lds, s, a);  \
-        return;                                                                                         \
+        constexpr int KC = sw_pk_class_queries(GG, RR, MODE);                                           \
+        if constexpr (KC > 1) {                                                                         \
+            const uint32_t ts = (tcap + 1) / 2;   /* slots per task at most */                          \
+            /* K times the waves on K profiles: LDS per wave, and with it the waves a CU holds, stay what they are at K = 1 */ \
+            if (kmax > 1 && ts <= 64 && KC * ts <= (uint32_t)SW_MQ_SLOTS) UC_SW_LAUNCH(GG, RR, NW * KC, KC) \
+        }                                                                                               \
+        UC_SW_LAUNCH(GG, RR, NW, 1)                                                                     \
     }
     // even R: 32-row class steps for G=16, 64 for G=32, 128 for G=64 (row padding 11.7 % -> 6.2 % at C2, tools/geom_stats.py)
     UC_SW_CASE(16, 2) UC_SW_CASE(16, 4) UC_SW_CASE(16, 6) UC_SW_CASE(16, 8) UC_SW_CASE(16, 10) UC_SW_CASE(16, 12)
@@ -485,6 +600,7 @@ void launch_sw_pk_class_mode(int G, int R, const SwArgs &a, uint32_t n_tasks, hi
         UC_SW_CASE(64, 2) UC_SW_CASE(64, 4) UC_SW_CASE(64, 6) UC_SW_CASE(64, 8) UC_SW_CASE(64, 10) UC_SW_CASE(64, 12)
     }
 #undef UC_SW_CASE
+#undef UC_SW_LAUNCH
     fprintf(stderr, "unicore-cluster: no packed SW kernel for class (G=%d, R=%d)\n", G, R);
     abort();
 }

@@ -2,8 +2,8 @@
 // MODE 2, uc_sw_pk_impl.hpp).
 #include "uc_sw_pk_impl.hpp"
 namespace uc {
-void launch_sw_pk_class_m6(int G, int R, const SwArgs &a, uint32_t n_tasks, hipStream_t s) {
-    launch_sw_pk_class_mode<6>(G, R, a, n_tasks, s);
+int launch_sw_pk_class_m6(int G, int R, const SwArgs &a, uint32_t n_tasks, hipStream_t s, int kmax, uint32_t tcap) {
+    return launch_sw_pk_class_mode<6>(G, R, a, n_tasks, s, kmax, tcap);
 }
 void preload_sw_pk_m6() { preload_sw_pk_mode<6>(); }
 }  // namespace uc

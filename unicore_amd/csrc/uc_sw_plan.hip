@@ -343,6 +343,16 @@ int pk_known_tab(uint32_t n_pairs, uint32_t n_queries) {
     return on && (double)n_pairs < 2.5 * (double)n_queries ? 3 : 1;
 }
 
+// below how many slots per task (mean over a class of a pass) the packed kernel serves several tasks per workgroup: a host-side choice like the one
+// above, results do not depend on it (UC_SW_TASK_QUERIES=1: never, for A/B runs; UC_SW_TASK_SLOTS: the threshold, for sweeps)
+static double sw_task_queries_slots() {
+    static const double v = [] {
+        if (getenv("UC_SW_TASK_QUERIES") && atoi(getenv("UC_SW_TASK_QUERIES")) == 1) return 0.0;
+        return getenv("UC_SW_TASK_SLOTS") ? atof(getenv("UC_SW_TASK_SLOTS")) : 24.0;
+    }();
+    return v;
+}
+
 // running maximum (inclusive) of a u32 array
 void max_scan_u32(Engine &E, DevBuf<char> &tmp, const uint32_t *in, uint32_t *out, uint32_t n) {
     rocprim_call(tmp, [&](void *t, size_t &b) { return rocprim::inclusive_scan(t, b, in, out, (size_t)n, MaxU32(), E.stream); });
@@ -473,8 +483,12 @@ uint64_t launch_plan(Engine &E, SwPlan &P, int mode, int32_t *os, int32_t *oqe, 
         ac.tasks = P.tasks.p + c0;
         hipStream_t st = slot % E.n_streams == 0 ? E.stream : E.aux[slot % E.n_streams - 1];
         slot++;
-        if (tab.pk[c]) launch_sw_pk_class(tab.G[c], tab.R[c], mode, ac, nt, st);
-        else launch_sw_class(tab.G[c], tab.R[c], imode, ac, nt, st);
+        if (tab.pk[c]) {
+            // short lists (few slots per task): the workgroups of the class serve several tasks each (sw_pk_kernel, K > 1)
+            const double slots = 0.5 * (double)(P.pair_base[c + 1] - P.pair_base[c]) / (double)(P.task_base[c + 1] - P.task_base[c]);
+            const int k = launch_sw_pk_class(tab.G[c], tab.R[c], mode, ac, nt, st, slots < sw_task_queries_slots() ? 2 : 1, tab.tcap[c]);
+            if (k > 1) { E.sw_task_queries[0]++; E.sw_task_queries[1] += nt; }
+        } else launch_sw_class(tab.G[c], tab.R[c], imode, ac, nt, st);
         UC_HIP(hipGetLastError());
         launches++;
     }
