@@ -8,7 +8,7 @@ where there is no GPU:
              query, so the records of one home are one slice: ragged all-to-all (point-to-point sends here: gloo has no alltoall),
              the home rank merges under (score desc, target asc) and keeps max_seqs     (exchange_two_phase, phase 1)
     exchange 2: surviving pairs go to the rank that OWNS them — a hash of the unordered pair's representative query (the shorter
-             sequence, ties: smaller id), so mutual hits meet on one rank               (pair_owner == uc_prefilter.hip pair_owner)
+             sequence, ties: smaller id), so mutual hits meet on one rank               (pair_owner == uc_hit_lists.hip pair_owner)
     gather   : accepted edges to rank 0, host set cover there                            (gather_edges)
 """
 import numpy as np
@@ -50,7 +50,7 @@ def grid_ranges(lens, world, target_shards=0):
 
 
 def pair_owner(a, b, lens, world):
-    """owner rank of the unordered pair {a, b} (arrays): the device hash of uc_prefilter.hip, restated"""
+    """owner rank of the unordered pair {a, b} (arrays): the device hash of uc_hit_lists.hip, restated"""
     a = np.asarray(a, np.int64); b = np.asarray(b, np.int64)
     la, lb = np.asarray(lens)[a], np.asarray(lens)[b]
     rep = np.where((la < lb) | ((la == lb) & (a < b)), a, b).astype(np.uint64)

@@ -14,7 +14,7 @@ to the oracle as THE SAME files (--mat3di / --mat-aa).  Every builder is seeded 
                     still similar to themselves.  (The threshold has to be the derived one: a negative --k-score means "not given" to the
                     engine, and under a threshold >= 0 no k-mer whose first five letters add less than -64 can pass with a sixth of at most 48.)
 
-`rest5` below is the quantity the similar-k-mer search of uc_prefilter.hip keeps per DFS level: the sum of the row maxima of the k-mer's letters that
+`rest5` below is the quantity the similar-k-mer search of uc_kmer_match.hip keeps per DFS level: the sum of the row maxima of the k-mer's letters that
 the levels behind the first one decide, i.e. of its first five letters in pattern order."""
 import os
 

@@ -76,7 +76,7 @@ def test_window_sweep_long_lengths_alone(O):
 @pytest.mark.parametrize("lmax,n", PC.EXTREME_SETS)
 def test_extreme_diagonal_preconditions(O, lmax, n):
     """family 2: the one-k-mer sequence against the longest one takes the most negative diagonal the biased field has to hold, the pair the other way
-    round ties diagonal 0 with every diagonal up to lmax - 10.  The field widths are recomputed here by the rule of key_format() in uc_prefilter.hip, not
+    round ties diagonal 0 with every diagonal up to lmax - 10.  The field widths are recomputed here by the rule of key_format() in uc_kmer_match.hip, not
     read from the engine (no statistic exposes them): what this shows is that the lengths and counts chosen sit on either side of a width change"""
     lengths = PC.extreme_lengths(lmax, n)
     assert len(lengths) == n and max(lengths) == lmax and lengths[0] == 10 and len(set(lengths)) == n

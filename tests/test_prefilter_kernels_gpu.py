@@ -1,9 +1,9 @@
-"""Kernel-level parity of the k-mer prefilter (uc_prefilter.hip, stages E1-E4) on repeats, ties and window edges: Engine.prefilter() against the
+"""Kernel-level parity of the k-mer prefilter (uc_kmer_match.hip, uc_kmer_filter.hip, uc_diag_select.hip, uc_hit_lists.hip and the driver uc_prefilter.hip, stages E1-E4) on repeats, ties and window edges: Engine.prefilter() against the
 oracle's E1-E4 run one query at a time with its stage counters, and - for homopolymers - against the closed form of spec UC-1 in plain integers
 (tests/prefilter_cases.py).  Per-query counts, target / score / diag of every hit in list order and the four stage counters must be EQUAL.  The
 preconditions that make each case reach its code path are proven on the CPU in tests/test_prefilter_cases.py.
 
-That these tests can fail was checked with three result-only mutations of uc_prefilter.hip on a scratch copy (never committed):
+That these tests can fail was checked with three result-only mutations of the prefilter's kernels (then in uc_prefilter.hip) on a scratch copy (never committed):
   diag_long_kernel taking the largest tied diagonal forward and the smallest for the mirrored pair (the two tie keys swapped) -> window sweep, tandem
       repeats, chunked runs, merge settings, loaded filter and X residues red (the closed form names the (query, target, diag) records);
   diag_long_kernel forgetting the run length carried across a window -> the same and the longest-sequence case red;

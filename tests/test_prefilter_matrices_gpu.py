@@ -1,4 +1,4 @@
-"""The k-mer prefilter (uc_prefilter.hip, stages E1-E4) under matrices that reach +-48 and under every k-mer pattern of tests/linclust_ref.py:
+"""The k-mer prefilter (uc_kmer_match.hip .. uc_hit_lists.hip and the driver uc_prefilter.hip, stages E1-E4) under matrices that reach +-48 and under every k-mer pattern of tests/linclust_ref.py:
 Engine.prefilter() against the oracle's E1-E4 one query at a time (per-query counts, every hit in list order, the four stage counters - all
 EQUAL), and for homopolymers against the closed form of spec UC-1 with the pattern's span.  Case builders: tests/matrix_cases.py; the preconditions
 (how many k-mers of each case leave the 8-bit field the similar-k-mer search used to keep its bound in, which X variants leave a k-mer under which

@@ -1,4 +1,4 @@
-"""The on-chip diagonal selection of the k-mer prefilter (td_select_kernel / cand_gather_kernel, uc_prefilter.hip) against the batch sort it replaces
+"""The on-chip diagonal selection of the k-mer prefilter (td_select_kernel / cand_gather_kernel, uc_diag_select.hip) against the batch sort it replaces
 and against the oracle.  Every case compares three runs of Engine.prefilter(): the default one, the one with UC_TD_ONCHIP=0 (every query through
 compact_kernel, the radix sort, diag_select_kernel and diag_long_kernel) and the oracle's E1-E4 - or the closed form of spec UC-1 where one exists.
 Per-query counts, target / score / diag of every hit in list order and the stage counters, n_filtered_hits included, must be EQUAL.

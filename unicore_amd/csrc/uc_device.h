@@ -120,7 +120,7 @@ __device__ __forceinline__ void block_add2(unsigned long long va, unsigned long 
 }
 #endif
 
-// host launchers (uc_sw.hip / uc_prefilter.hip)
+// host launchers (uc_sw.hip / uc_hit_lists.hip)
 void launch_sw_class(int G, int R, int mode, const SwArgs &a, uint32_t n_tasks, hipStream_t s);
 // kmax > 1: the class may serve several tasks per workgroup (tcap = pairs per task of the class at most); returns the tasks per workgroup it launched with
 int launch_sw_pk_class(int G, int R, int mode, const SwArgs &a, uint32_t n_tasks, hipStream_t s, int kmax = 1, uint32_t tcap = 0);

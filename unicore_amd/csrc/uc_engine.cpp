@@ -1,5 +1,5 @@
 // uc_engine.cpp — host orchestration of the per-GPU engine: DB upload, batching of the gapped stage
-// (E5/E6), kernel-level entry points.  Prefilter orchestration (E1-E4) lives in uc_prefilter.hip.
+// (E5/E6), kernel-level entry points.  Prefilter orchestration (E1-E4) lives in uc_prefilter.hip, its passes in uc_kmer_match.hip .. uc_hit_lists.hip.
 #include "uc_engine.h"
 
 #include <algorithm>

@@ -206,7 +206,7 @@ struct ReassignScratch {
     DevBuf<char> tmp;
 };
 
-struct PrefilterScratch;                                  // uc_prefilter.hip
+struct PrefilterScratch;                                  // uc_prefilter_internal.h
 void free_scratch(PrefilterScratch *p);
 struct AlignScratch;                                      // uc_align_internal.h
 void free_scratch(AlignScratch *p);
@@ -375,7 +375,7 @@ struct Engine {
     // kernel-level
     void ungapped_batch(uint64_t n, const uint32_t *q, const uint32_t *t, const int32_t *diag, int32_t *out);
     void ungapped_select(uint64_t n, const uint32_t *q, const uint32_t *t, const int32_t *diag, int min_score, int32_t *score_out, uint64_t *overlap_out,
-                         uint64_t *kept_out);      // uc_prefilter.hip
+                         uint64_t *kept_out);      // uc_hit_lists.hip
     // rule UC-1/X: dense [q1 - q0][t1 - t0] scores and diagonals, computed tile by tile under tile_bytes (0 = UNGAPPED_ALL_TILE_BYTES)   (uc_ungapped_all.hip)
     void ungapped_all(uint32_t q0, uint32_t q1, uint32_t t0, uint32_t t1, uint64_t tile_bytes, int32_t *score_out, int32_t *diag_out);
     void sw_batch(int mode, const std::vector<PairIn> &pairs, int32_t *score, int32_t *qe, int32_t *te);

@@ -89,7 +89,7 @@ void load_matrix(const std::string &path, int8_t out[A * A]) {
             if (!(ss >> v)) break;
             if (row < 0 || cols[c] < 0) continue;
             // 48 keeps (S3 + SA + gap_open) inside the biased-byte query profile of the DP kernel, and five letters' row maxima (-240 .. 240) inside the
-            // 10-bit fields, biased by 256, of the similar-k-mer search's pruning bound (uc_prefilter.hip, restpack)
+            // 10-bit fields, biased by 256, of the similar-k-mer search's pruning bound (uc_kmer_match.hip, restpack)
             if (v < -48 || v > 48) fail(UC_ERR_ARGS, "matrix %s: value %ld outside [-48,48]", path.c_str(), v);
             out[row * A + cols[c]] = (int8_t)v;
         }

@@ -166,13 +166,14 @@ void launch_ungapped(const DeviceDb &db, uint64_t n, const uint32_t *q, const ui
 // used - tens of milliseconds each for the SW classes, paid in the middle of the first pass.  A helper thread touches one kernel per module while the main
 // thread builds the engine, uploads the database and runs the prefilter.
 void preload_sw_pk_m0(); void preload_sw_pk_m1(); void preload_sw_pk_m4(); void preload_sw_pk_m6();
-void preload_prefilter_module(); void preload_linclust_module();
+void preload_kmer_match_module(); void preload_kmer_filter_module(); void preload_diag_select_module(); void preload_hit_lists_module();
+void preload_linclust_module();
 void preload_sw_plan_module(); void preload_align_module(); void preload_traceback_module(); void preload_cluster_graph_module();
 void preload_modules(int device, bool linclust) {
     if (hipSetDevice(device) != hipSuccess) return;
     hipFuncAttributes fa;
     (void)hipFuncGetAttributes(&fa, (const void *)db_pad_kernel);
-    preload_prefilter_module();
+    preload_kmer_match_module(); preload_kmer_filter_module(); preload_diag_select_module(); preload_hit_lists_module();      // in the order the prefilter runs them
     if (linclust) preload_linclust_module();
     preload_sw_plan_module(); preload_align_module(); preload_traceback_module(); preload_cluster_graph_module();
     preload_sw_pk_m0(); preload_sw_pk_m1(); preload_sw_pk_m6(); preload_sw_pk_m4();

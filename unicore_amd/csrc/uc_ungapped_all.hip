@@ -1,7 +1,7 @@
 // uc_ungapped_all.hip — rule UC-1/X (--prefilter-mode 1): the exhaustive ungapped prefilter.  Every query of a batch against every target of a
 // chunk, all diagonals: the pair's score is the best E3 score over the diagonals -(Lt-1) .. Lq-1 (capped at 255), its diagonal the smallest one
 // that reaches it.  One kernel fills a (query batch x target chunk) tile of scores (one byte per pair) and diagonals; a second one turns the
-// pairs that pass --min-ungapped-score into the candidate arrays the E4 selection of the k-mer path takes (uc_prefilter.hip).
+// pairs that pass --min-ungapped-score into the candidate arrays the E4 selection of the k-mer path takes (uc_hit_lists.hip; the tile loop: uc_prefilter.hip).
 //
 // The scan.  A LANE OWNS A DIAGONAL: lane l of a wave works on d = d0 + l, and the wave walks the target columns j, so that at every step
 //   * the target letter t[j] is wave-uniform (sixteen letters per load, handed to the scalar unit),
