@@ -461,6 +461,37 @@ typedef struct uc_nj_boot_stats {
 int uc_tree_infer_boot(const char *msa_fasta, const char *out_nwk, const char *model, uint32_t n_rep, uint64_t seed, const uc_opts *o,
                        uc_nj_boot_stats *stats_out);
 
+/* ---- transfer bootstrap support for `nj` (rule UC-N/T; TBE, Lemoine et al., Nature 2018): for a branch of the main tree and a
+ * replicate tree, the fewest leaves that would have to move for the branch to appear, averaged over the replicates.  Integers throughout; the _dev
+ * sibling runs the HIP kernels of uc_nj_transfer.hip.  Limits, all UC_ERR_ARGS before the device is touched: those of UC-N and UC-N/B, and join records
+ * that do not form a tree (a node joined twice or before it exists), the main tree's or a replicate's.
+ * Join s of a tree on n leaves creates node n + s with leaf set L_s; light[s] = min(|L_s|, n - |L_s|) >= 2.  For a main split x and a replicate split y,
+ *   h = popcount(x xor y) over the n-bit sets and delta = min(h, n - h).  phi[b][s] = min(light[s] - 1, min over replicate b's n - 3 joins of delta): the
+ *   cap is what the replicate's terminal branches would give.  phi[b][s] == 0 exactly when replicate b holds the split (uc_nj_support counts those).
+ * uc_nj_transfer: phi [n_rep][n - 3] and light [n - 3]; threads: host threads of the twin (0 = 1), replicates spread over them.  n <= 3 writes
+ *   nothing.  The device side works under UC_TREE_BUDGET_BYTES in batches of replicates; no result depends on it.
+ * Labelled Newick: phi_sum[s] = the sum of phi[b][s] over the replicates (64 bits), den = n_rep (light[s] - 1), the label of node n + s is the
+ *   percentage of 1 - phi_sum[s] / den rounded half up, (200 (den - phi_sum[s]) + den) div (2 den); phi_sum[s] > den is UC_ERR_ARGS; n_rep == 0 (light and
+ *   phi_sum may be NULL) gives the unlabelled line.
+ * uc_nj_transfer_geometry: the splits of a tile of the comparison kernel, the 32-bit words of a split staged through LDS at a time, and the largest
+ *   tree for which uc_tree_infer_support runs the twin also on a device run (the device call's fixed cost is above the twin's whole time there). */
+#define UC_NJ_SUPPORT_FBP 0
+#define UC_NJ_SUPPORT_TBE 1
+int uc_nj_transfer(uint32_t n, const uint32_t *join_a, const uint32_t *join_b, uint32_t n_rep, const uint32_t *rep_join_a, const uint32_t *rep_join_b,
+                   uint32_t threads, uint32_t *phi, uint32_t *light);
+int uc_nj_transfer_dev(int32_t device, uint32_t n, const uint32_t *join_a, const uint32_t *join_b, uint32_t n_rep, const uint32_t *rep_join_a,
+                       const uint32_t *rep_join_b, uint32_t threads, uint32_t *phi, uint32_t *light);
+int uc_nj_newick_transfer(const char *const *names, uint32_t n, const uint32_t *join_a, const uint32_t *join_b, const double *len_a, const double *len_b,
+                          const uint32_t *root_node, const double *root_len, const uint32_t *light, const uint64_t *phi_sum, uint32_t n_rep, char *buf,
+                          uint64_t cap, uint64_t *need);
+int uc_nj_transfer_geometry(uint32_t *tile_splits, uint32_t *chunk_words, uint32_t *host_leaves);
+/* == `unicore tree -t nj -p "--bootstrap B --support fbp|tbe"`: uc_tree_infer_boot with the support rule as an argument.  UC_NJ_SUPPORT_FBP is that
+ * call, byte for byte; UC_NJ_SUPPORT_TBE labels the same main tree with UC-N/T's percentages, reports the transfer time in seconds[5], keeps
+ * support_min / support_sum as the counts of replicates that hold a split (the zeros of phi), and a dump's <out_nwk>.boot.tsv reads
+ * `s\tsupport\tlight\tphi_sum\tlabel`.  Any other mode is UC_ERR_ARGS before a file is read. */
+int uc_tree_infer_support(const char *msa_fasta, const char *out_nwk, const char *model, uint32_t n_rep, uint64_t seed, uint32_t support_mode,
+                          const uc_opts *o, uc_nj_boot_stats *stats_out);
+
 /* ---- kernel-level entry points (parity tests call the HIP kernels through these) -------------- */
 /* ungapped diagonal score (E3) for n candidates (q[i], t[i], diag[i]) of the engine's DB */
 int uc_engine_ungapped_batch(uc_engine *e, uint64_t n, const uint32_t *q, const uint32_t *t,

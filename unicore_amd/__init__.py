@@ -57,6 +57,7 @@ class UcNjStats(C.Structure):
 
 NJ_PHASES = ("read", "counts", "transform", "join", "write")
 NJ_MODELS = {"kimura": 0, "p": 1}
+NJ_SUPPORT_MODES = {"fbp": 0, "tbe": 1}      # UC_NJ_SUPPORT_FBP / UC_NJ_SUPPORT_TBE
 NJ_NO_NODE = 0xFFFFFFFF  # == UC_NJ_NO_NODE: the third root entry of a two-leaf tree
 
 
@@ -95,6 +96,7 @@ SYMBOLS = (
     "uc_nj_counts", "uc_nj_counts_dev", "uc_nj_distances", "uc_nj_join", "uc_nj_join_dev", "uc_nj_newick", "uc_nj_geometry", "uc_tree_infer",
     "uc_nj_boot_columns", "uc_nj_boot_counts", "uc_nj_boot_counts_dev", "uc_nj_join_batch", "uc_nj_join_batch_dev", "uc_nj_support", "uc_nj_newick_support",
     "uc_nj_boot_geometry", "uc_tree_infer_boot",
+    "uc_nj_transfer", "uc_nj_transfer_dev", "uc_nj_newick_transfer", "uc_nj_transfer_geometry", "uc_tree_infer_support",
 )
 NO_GENE = 0xFFFFFFFF  # == UC_NO_GENE: a TSV row whose gene name is not in the map
 ABI_VERSION = 9      # == UC_ABI_VERSION of include/unicore_cluster.h this binding mirrors
@@ -199,6 +201,11 @@ def lib():
     L.uc_nj_newick_support.argtypes = [C.POINTER(C.c_char_p), u32] + [vp] * 6 + [vp, u32, vp, u64, C.POINTER(u64)]
     L.uc_nj_boot_geometry.argtypes = [C.POINTER(u32)]
     L.uc_tree_infer_boot.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, u32, u64, C.POINTER(UcOpts), C.POINTER(UcNjBootStats)]
+    L.uc_nj_transfer.argtypes = [u32, vp, vp, u32, vp, vp, u32, vp, vp]
+    L.uc_nj_transfer_dev.argtypes = [i32] + L.uc_nj_transfer.argtypes
+    L.uc_nj_newick_transfer.argtypes = [C.POINTER(C.c_char_p), u32] + [vp] * 6 + [vp, vp, u32, vp, u64, C.POINTER(u64)]
+    L.uc_nj_transfer_geometry.argtypes = [C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]
+    L.uc_tree_infer_support.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, u32, u64, u32, C.POINTER(UcOpts), C.POINTER(UcNjBootStats)]
     L.uc_engine_ungapped_batch.argtypes = [vp, u64, vp, vp, vp, vp]
     L.uc_engine_ungapped_select.argtypes = [vp, u64, vp, vp, vp, C.c_int32, vp, vp, vp]
     L.uc_engine_ungapped_all.argtypes = [vp, u32, u32, u32, u32, u64, vp, vp]
@@ -497,16 +504,24 @@ def nj_join(D, device=None):
     return {"join_a": ja[:steps], "join_b": jb[:steps], "len_a": la[:steps], "len_b": lb[:steps], "root_node": rn, "root_len": rl}
 
 
-def nj_newick(names, joins, support=None, n_rep=0):
-    """uc_nj_newick / uc_nj_newick_support (host only): the tree of nj_join's dict over the leaf names (str or bytes) as one Newick line with its
-    newline (str).  With support (nj_support's array) and n_rep > 0 every internal node but the root carries its percentage, rounded half up."""
+def nj_newick(names, joins, support=None, n_rep=0, light=None, phi_sum=None):
+    """uc_nj_newick / uc_nj_newick_support / uc_nj_newick_transfer (host only): the tree of nj_join's dict over the leaf names (str or bytes) as one
+    Newick line with its newline (str).  With support (nj_support's array) and n_rep > 0 every internal node but the root carries its percentage,
+    rounded half up.  With light and phi_sum (nj_transfer's light and the sum of its phi over the replicates) instead of support, the labels are
+    UC-N/T's: the percentage of 1 - phi_sum / (n_rep (light - 1)), rounded half up."""
     nm = [x if isinstance(x, bytes) else x.encode() for x in names]
     arr = (C.c_char_p * max(len(nm), 1))(*nm)
     a = [np.ascontiguousarray(joins[k], t) for k, t in (("join_a", np.uint32), ("join_b", np.uint32), ("len_a", np.float64), ("len_b", np.float64),
                                                         ("root_node", np.uint32), ("root_len", np.float64))]
     need = C.c_uint64()
     ptrs = [_ptr(x) for x in a]
-    if support is None and not n_rep:
+    if light is not None or phi_sum is not None:
+        if support is not None:
+            raise ValueError("support or (light, phi_sum), not both")
+        li = None if light is None else np.ascontiguousarray(light, np.uint32)
+        ps = None if phi_sum is None else np.ascontiguousarray(phi_sum, np.uint64)
+        call = lambda buf, cap: lib().uc_nj_newick_transfer(arr, len(nm), *ptrs, None if li is None else _ptr(li), None if ps is None else _ptr(ps), n_rep, buf, cap, C.byref(need))
+    elif support is None and not n_rep:
         call = lambda buf, cap: lib().uc_nj_newick(arr, len(nm), *ptrs, buf, cap, C.byref(need))
     else:
         su = None if support is None else np.ascontiguousarray(support, np.uint32)
@@ -579,15 +594,48 @@ def nj_support(n, joins, rep_join_a, rep_join_b):
     return out[:steps]
 
 
-def tree_infer(fasta, out, model="kimura", verbosity=1, device=-1, threads=1, bootstrap=0, seed=1):
+def nj_transfer_geometry():
+    """The comparison kernel's geometry (uc_nj_transfer_geometry): {"tile": splits of a tile, "chunk": 32-bit words staged through LDS at a time,
+    "host_leaves": the largest tree whose transfer phase tree_infer runs on the host twin also on a device run}."""
+    t, c, h = C.c_uint32(), C.c_uint32(), C.c_uint32()
+    _check(lib().uc_nj_transfer_geometry(C.byref(t), C.byref(c), C.byref(h)))
+    return {"tile": t.value, "chunk": c.value, "host_leaves": h.value}
+
+
+def nj_transfer(n, joins, rep_join_a, rep_join_b, device=None, threads=1):
+    """UC-N/T (uc_nj_transfer / uc_nj_transfer_dev): joins is the main tree's nj_join dict over n leaves, rep_join_a / rep_join_b [n_rep][n - 3] the
+    replicates' (nj_join_batch's arrays).  Returns (phi, light): phi uint32 [n_rep][n - 3], the transfer index of every main-tree join in every
+    replicate (0 exactly where the replicate holds the split), and light uint32 [n - 3], the smaller side of every main-tree split.  device as in
+    msa_center; threads: the host twin's."""
+    steps = max(n - 3, 0)
+    ja, jb = np.ascontiguousarray(joins["join_a"], np.uint32), np.ascontiguousarray(joins["join_b"], np.uint32)
+    ra, rb = np.ascontiguousarray(rep_join_a, np.uint32).reshape(-1, max(steps, 1)), np.ascontiguousarray(rep_join_b, np.uint32).reshape(-1, max(steps, 1))
+    if len(ja) != steps or len(jb) != steps or ra.shape != rb.shape or (steps and ra.shape[1] != steps):
+        raise ValueError("join arrays hold n - 3 entries per tree")
+    B = ra.shape[0] if steps else 0
+    phi, light = np.zeros((max(B, 1), max(steps, 1)), np.uint32), np.zeros(max(steps, 1), np.uint32)
+    args = [n, _ptr(ja), _ptr(jb), B, _ptr(ra), _ptr(rb), threads, phi.ctypes.data, light.ctypes.data]
+    _check(lib().uc_nj_transfer(*args) if device is None else lib().uc_nj_transfer_dev(device, *args))
+    return phi[:B, :steps], light[:steps]
+
+
+def tree_infer(fasta, out, model="kimura", verbosity=1, device=-1, threads=1, bootstrap=0, seed=1, support="fbp"):
     """== the inference step of `unicore tree -t nj` (uc_tree_infer): reads the aligned FASTA `fasta`, counts on the device, transforms under
     `model`, joins and writes the Newick line to `out`.  UC_TREE_HOST=1 in the environment runs the host twins (no GPU needed); UC_TREE_DUMP=1
     also writes <out>.dist.tsv.  Returns the stats dict (counts and seconds per phase).  bootstrap > 0 (uc_tree_infer_boot): `bootstrap`
     replicate trees drawn under `seed` label every internal branch of the same tree with its support; the stats dict is then the bootstrap's
-    (replicates, batches, smallest and summed support, seconds per phase) and a dump also writes <out>.boot.tsv and <out>.boottrees."""
+    (replicates, batches, smallest and summed support, seconds per phase) and a dump also writes <out>.boot.tsv and <out>.boottrees.
+    support: "fbp" (the share of replicates that hold the split) or "tbe" (uc_tree_infer_support: the transfer bootstrap expectation, UC-N/T);
+    anything else is UC_ERR_ARGS, with or without replicates; without replicates it is unused."""
+    if support not in NJ_SUPPORT_MODES:
+        raise UcError(UC_ERR_ARGS, "nj: unknown support mode '%s' (fbp, tbe)" % (support,))
     if bootstrap:
         o, st = make_opts("", threads, verbosity, device), UcNjBootStats()
-        _check(lib().uc_tree_infer_boot(fasta.encode(), out.encode(), None if model is None else model.encode(), bootstrap, seed & (2 ** 64 - 1), C.byref(o), C.byref(st)))
+        if support == "fbp":
+            _check(lib().uc_tree_infer_boot(fasta.encode(), out.encode(), None if model is None else model.encode(), bootstrap, seed & (2 ** 64 - 1), C.byref(o), C.byref(st)))
+        else:
+            _check(lib().uc_tree_infer_support(fasta.encode(), out.encode(), None if model is None else model.encode(), bootstrap, seed & (2 ** 64 - 1),
+                                               NJ_SUPPORT_MODES[support], C.byref(o), C.byref(st)))
         d = {k: int(getattr(st, k)) for k, _ in UcNjBootStats._fields_ if k != "seconds"}
         d["seconds"] = dict(zip(NJ_BOOT_PHASES, st.seconds))
         return d

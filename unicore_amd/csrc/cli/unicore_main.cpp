@@ -242,7 +242,8 @@ void usage_tree(FILE *to) {
          "  -n, --no-inference                       Stop the tree module after alignment (before tree inference); required unless the builder is nj\n"
          "  -p, --tree-options <TREE_OPTIONS>        Options for tree builder; nj: \"--model kimura|p\" [default: kimura], \"--bootstrap B\" replicates label\n"
          "                                           every internal branch with its support in percent [default: 0], \"--seed S\" of their draws\n"
-         "                                           [default: 1]; parsed, not used for the others\n"
+         "                                           [default: 1], \"--support fbp|tbe\" the share of replicates with the same branch or the\n"
+         "                                           transfer bootstrap expectation [default: fbp]; parsed, not used for the others\n"
          "  -d, --threshold <THRESHOLD>              Gap threshold for multiple sequence alignment [0 - 100] [default: 50]\n"
          "  -c, --threads <THREADS>                  Number of threads to use; 0 to use all [default: 0]\n"
          "  -v, --verbosity <VERBOSITY>              Verbosity (0: quiet, 1: +errors, 2: +warnings, 3: +info, 4: +debug) [default: 3]\n"
@@ -254,9 +255,9 @@ void usage_tree(FILE *to) {
     exit(CLAP_USAGE);
 }
 
-// the options of the built-in builder: "--model kimura|p", "--bootstrap B" (0 .. 100000) and "--seed S" (64 bits), each also as --word=value; any other
-// word is refused by name, a value that is no number in range too
-struct NjOptions { std::string model = "kimura"; uint32_t bootstrap = 0; uint64_t seed = 1; };
+// the options of the built-in builder: "--model kimura|p", "--bootstrap B" (0 .. 100000), "--seed S" (64 bits) and "--support fbp|tbe", each also as
+// --word=value; any other word is refused by name, a value that is no number in range or no name of a rule too
+struct NjOptions { std::string model = "kimura"; uint32_t bootstrap = 0; uint64_t seed = 1; std::string support = "fbp"; };
 
 uint64_t nj_number_of(const std::string &word, const std::string &v, uint64_t most) {
     bool ok = !v.empty() && v.size() <= 20 && v.find_first_not_of("0123456789") == std::string::npos;
@@ -290,8 +291,10 @@ NjOptions nj_options_of(const std::string &tree_options) {
         if (value("--model", "kimura, p", v)) o.model = v;
         else if (value("--bootstrap", "replicates, 0 .. 100000", v)) o.bootstrap = (uint32_t)nj_number_of("--bootstrap", v, 100000);
         else if (value("--seed", "a 64-bit number", v)) o.seed = nj_number_of("--seed", v, UINT64_MAX);
-        else error(ERR_GENERAL, "tree builder nj does not know the option '" + words[k] + "' (--model kimura|p, --bootstrap B, --seed S)");
+        else if (value("--support", "fbp, tbe", v)) o.support = v;
+        else error(ERR_GENERAL, "tree builder nj does not know the option '" + words[k] + "' (--model kimura|p, --bootstrap B, --seed S, --support fbp|tbe)");
     }
+    if (o.support != "fbp" && o.support != "tbe") error(ERR_GENERAL, "tree builder nj: '" + o.support + "' is not a value for --support (fbp, tbe)");
     if (o.model != "kimura" && o.model != "p") error(ERR_GENERAL, "tree builder nj does not know the model '" + o.model + "' (kimura, p)");
     return o;
 }
@@ -302,6 +305,7 @@ int nj_infer(const std::string &msa, const std::string &out, const NjOptions &nj
     if (!nj.bootstrap) return uc_tree_infer(msa.c_str(), out.c_str(), nj.model.c_str(), &o, nullptr);
     uc_opts ob = o;
     ob.threads = threads > 0 ? threads : (int)std::min(16u, std::max(1u, std::thread::hardware_concurrency()));      // n^2 logs a replicate: more do not pay
+    if (nj.support == "tbe") return uc_tree_infer_support(msa.c_str(), out.c_str(), nj.model.c_str(), nj.bootstrap, nj.seed, UC_NJ_SUPPORT_TBE, &ob, nullptr);
     return uc_tree_infer_boot(msa.c_str(), out.c_str(), nj.model.c_str(), nj.bootstrap, nj.seed, &ob, nullptr);
 }
 
@@ -386,7 +390,8 @@ void usage_gene_tree(FILE *to) {
          "                                           fasta/<gene>/nj.nwk; the others are external programs and are refused [default: iqtree]\n"
          "  -p, --tree-options <TREE_OPTIONS>        Options for tree builder; nj: \"--model kimura|p\" [default: kimura], \"--bootstrap B\" replicates label\n"
          "                                           every internal branch with its support in percent [default: 0], \"--seed S\" of their draws\n"
-         "                                           [default: 1], the same for every gene\n"
+         "                                           [default: 1], \"--support fbp|tbe\" the share of replicates with the same branch or the\n"
+         "                                           transfer bootstrap expectation [default: fbp], the same for every gene\n"
          "  -f, --realign                            Refused: re-aligning single genes is not built in\n"
          "  -c, --threads <THREADS>                  Number of threads to use; 0 to use all [default: 0]\n"
          "  -v, --verbosity <VERBOSITY>              Verbosity (0: quiet, 1: +errors, 2: +warnings, 3: +info, 4: +debug) [default: 3]\n"

@@ -81,9 +81,10 @@ void nj_join_device(int device, const NjJoinArgs &a);
 // ---- the pieces of uc_nj_host.cpp that the bootstrap (uc_nj_boot_host.cpp) builds on
 // comp / diff of every row pair over n rows of `words` 64-bit words of codes (eight columns a word, padding 0), spread over `threads`
 void nj_count_codes(const uint64_t *code, uint64_t n, uint64_t words, uint32_t threads, uint32_t *comp, uint32_t *diff);
-// the Newick line; support (nullable) [n - 3] with n_rep > 0 labels node n + s with the percentage (200 support[s] + n_rep) div (2 n_rep)
+// the Newick line; support (nullable) [n - 3] with n_rep > 0 labels node n + s with the percentage (200 support[s] + n_rep) div (2 n_rep); labels
+// (nullable) [n - 3] with n_rep > 0 are written as they are instead (UC-N/T works its percentages out itself) and support is not read
 std::string nj_newick_line(const char *const *names, uint32_t n, const uint32_t *ja, const uint32_t *jb, const double *la, const double *lb, const uint32_t *root,
-                           const double *rlen, const uint32_t *support, uint32_t n_rep);
+                           const double *rlen, const uint32_t *support, uint32_t n_rep, const uint64_t *labels = nullptr);
 // the tree of the alignment itself, as uc_tree_infer computes it (phases 0 .. 3 of st.seconds), and the files uc_tree_infer writes for it
 struct NjMainTree {
     std::vector<std::string> names;
@@ -98,7 +99,7 @@ struct NjMainTree {
     double rlen[3];
 };
 void nj_main_tree(const char *msa_fasta, const char *model_name, const uc_opts *o, NjMainTree &T, uc_nj_stats &st);
-void nj_write_main_tree(const char *out_nwk, const NjMainTree &T, const uint32_t *support, uint32_t n_rep);
+void nj_write_main_tree(const char *out_nwk, const NjMainTree &T, const uint32_t *support, uint32_t n_rep, const uint64_t *labels = nullptr);
 
 // ---- UC-N/B: bootstrap support.  Draws: SplitMix64's finaliser over (seed, replicate, draw); a draw depends on nothing else
 constexpr uint32_t NJ_BOOT_MAX_REPS = 100000;
@@ -146,5 +147,38 @@ void nj_join_batch_host(const NjJoinBatchArgs &a);
 void nj_join_batch_device(int device, const NjJoinBatchArgs &a);
 // UC_TREE_BUDGET_BYTES, as nj_counts_device reads it (default 512 MiB, at least 1)
 uint64_t nj_tree_budget();
+
+// the bootstrap driver behind uc_tree_infer_boot.  rule == nullptr is that entry point, bit for bit and call for call; a rule (UC-N/T's lives in
+// uc_nj_transfer_host.cpp, which uc_nj_boot_host.cpp names nowhere: it links without it) takes the place of the split count: it sees the main tree once,
+// then every batch's join records (its time is phase [5]), and at the end gives the count of replicates that hold each split, the labels and the dump's columns
+struct NjBootRule {
+    virtual ~NjBootRule() = default;
+    virtual void begin(const NjMainTree &T, uint32_t n_rep) = 0;                                                     // n > 3 and n_rep > 0
+    virtual void batch(const NjMainTree &T, uint32_t nb, const uint32_t *ja, const uint32_t *jb) = 0;               // [nb][n - 3] each
+    virtual void finish(uint32_t *support, std::vector<uint64_t> &labels, std::vector<std::string> &tsv_columns) = 0;   // [n - 3] each
+};
+void nj_tree_infer_boot(const char *msa_fasta, const char *out_nwk, const char *model_name, uint32_t n_rep, uint64_t seed, const uc_opts *o, uc_nj_boot_stats *st_out,
+                        NjBootRule *rule);
+
+// ---- UC-N/T: transfer bootstrap support (uc_nj_transfer_host.cpp, uc_nj_transfer.hip)
+constexpr uint32_t NJ_T_TILE = 64;                             // splits of a tile of the comparison kernel, both ways
+constexpr uint32_t NJ_T_CHUNK = 16;                            // 32-bit words of both tiles staged through LDS at a time
+constexpr uint32_t NJ_T_HOST_LEAVES = 128;                     // up to here the driver runs the twin: the device call's allocations and transfers take
+                                                               // longer than the twin's comparison (profiles/nj_transfer); the _dev entry point never does
+struct NjTransferArgs {
+    uint32_t n;
+    const uint32_t *join_a, *join_b;          // the main tree, n - 3
+    uint32_t n_rep;
+    const uint32_t *rep_join_a, *rep_join_b;  // [n_rep][n - 3]
+    uint32_t threads;                         // host twin only (0 = 1)
+    uint32_t *phi;                            // [n_rep][n - 3]
+    uint32_t *light;                          // n - 3
+};
+// the limits, the pointers and that every tree's records form a tree; fills light.  n <= 3 checks the limits alone
+void nj_transfer_validate(const NjTransferArgs &a);
+void nj_transfer_host(const NjTransferArgs &a);              // after nj_transfer_validate: a.light is read
+void nj_transfer_device(int device, const NjTransferArgs &a);
+std::string nj_newick_transfer_line(const char *const *names, uint32_t n, const uint32_t *ja, const uint32_t *jb, const double *la, const double *lb, const uint32_t *root,
+                                    const double *rlen, const uint32_t *light, const uint64_t *phi_sum, uint32_t n_rep);
 
 }  // namespace uc

@@ -173,7 +173,10 @@ void support_args(uint32_t n, const uint32_t *ja, const uint32_t *jb, uint32_t n
     if (n_rep) { need(rja, "the replicates' join_a"); need(rjb, "the replicates' join_b"); }
 }
 
-void tree_infer_boot(const char *msa_fasta, const char *out_nwk, const char *model_name, uint32_t n_rep, uint64_t seed, const uc_opts *o, uc_nj_boot_stats *st_out) {
+}  // namespace
+
+void nj_tree_infer_boot(const char *msa_fasta, const char *out_nwk, const char *model_name, uint32_t n_rep, uint64_t seed, const uc_opts *o, uc_nj_boot_stats *st_out,
+                        NjBootRule *rule) {
     check_reps(n_rep);
     uc_nj_boot_stats st;
     memset(&st, 0, sizeof st);
@@ -189,9 +192,12 @@ void tree_infer_boot(const char *msa_fasta, const char *out_nwk, const char *mod
     const uint64_t tri = (uint64_t)n * (n - 1) / 2, nn = (uint64_t)n * n;
     std::vector<uint32_t> support(std::max<uint32_t>(steps, 1), 0);
     std::string boot_trees;
+    std::vector<uint64_t> labels;                  // a rule's own; empty: the percentages of support
+    std::vector<std::string> tsv_columns;          // a rule's columns of the dump, behind the support
     if (n_rep && (steps || T.dump)) {      // n <= 3 has no internal branch: its replicates are computed for the dump alone
         std::unique_ptr<SupportCounter> counter;
-        if (steps) counter.reset(new SupportCounter(n, T.ja.data(), T.jb.data()));
+        if (steps && !rule) counter.reset(new SupportCounter(n, T.ja.data(), T.jb.data()));
+        if (steps && rule) rule->begin(T, n_rep);
         // a batch holds the counts, D and the join records of its replicates
         const uint64_t per_rep = tri * 8 + nn * 8 + (uint64_t)steps * 24 + 36;
         const uint32_t batch = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(n_rep, nj_tree_budget() / per_rep));
@@ -211,7 +217,8 @@ void tree_infer_boot(const char *msa_fasta, const char *out_nwk, const char *mod
             const NjJoinBatchArgs ja_args{n, nb, D.data(), ja.data(), jb.data(), la.data(), lb.data(), root.data(), rlen.data(), (uint32_t)T.threads};
             if (T.on_host) nj_join_batch_host(ja_args); else nj_join_batch_device(T.device, ja_args);
             lap(4);
-            if (steps) parallel_for(nb, (uint32_t)T.threads, [&](uint64_t b) { counter->add(ja.data() + b * steps, jb.data() + b * steps); });
+            if (steps && rule) rule->batch(T, nb, ja.data(), jb.data());
+            else if (steps) parallel_for(nb, (uint32_t)T.threads, [&](uint64_t b) { counter->add(ja.data() + b * steps, jb.data() + b * steps); });
             lap(5);
             if (T.dump)
                 for (uint64_t b = 0; b < nb; b++)
@@ -220,17 +227,18 @@ void tree_infer_boot(const char *msa_fasta, const char *out_nwk, const char *mod
             lap(6);
         }
         st.support_min = steps ? n_rep : 0;
+        if (steps && rule) rule->finish(support.data(), labels, tsv_columns);
         for (uint32_t s = 0; s < steps; s++) {
-            support[s] = counter->support[s];
+            if (!rule) support[s] = counter->support[s];
             st.support_min = std::min<uint64_t>(st.support_min, support[s]);
             st.support_sum += support[s];
         }
         lap(5);
     }
-    nj_write_main_tree(out_nwk, T, support.data(), steps ? n_rep : 0);
+    nj_write_main_tree(out_nwk, T, support.data(), steps ? n_rep : 0, labels.empty() ? nullptr : labels.data());
     if (T.dump && n_rep) {
         std::string txt;
-        for (uint32_t s = 0; s < steps; s++) txt += std::to_string(s) + "\t" + std::to_string(support[s]) + "\n";
+        for (uint32_t s = 0; s < steps; s++) txt += std::to_string(s) + "\t" + std::to_string(support[s]) + (tsv_columns.empty() ? std::string() : tsv_columns[s]) + "\n";
         write_file(std::string(out_nwk) + ".boot.tsv", txt);
         write_file(std::string(out_nwk) + ".boottrees", boot_trees);
     }
@@ -241,8 +249,6 @@ void tree_infer_boot(const char *msa_fasta, const char *out_nwk, const char *mod
                 st.seconds[0], st.seconds[1], st.seconds[2], st.seconds[3], st.seconds[4], st.seconds[5], st.seconds[6]);
     if (st_out) *st_out = st;
 }
-
-}  // namespace
 
 }  // namespace uc
 
@@ -321,6 +327,6 @@ int uc_nj_boot_geometry(uint32_t *lds_rows) {
 int uc_tree_infer_boot(const char *msa_fasta, const char *out_nwk, const char *model, uint32_t n_rep, uint64_t seed, const uc_opts *o, uc_nj_boot_stats *stats_out) {
     return guard([&] {
         if (!msa_fasta || !out_nwk) fail(UC_ERR_ARGS, "tree_infer_boot: msa_fasta and out_nwk must not be NULL");
-        tree_infer_boot(msa_fasta, out_nwk, model, n_rep, seed, o, stats_out);
+        nj_tree_infer_boot(msa_fasta, out_nwk, model, n_rep, seed, o, stats_out, nullptr);
     });
 }

@@ -179,13 +179,13 @@ void append_len(std::string &out, double v) {
 }  // namespace
 
 std::string nj_newick_line(const char *const *names, uint32_t n, const uint32_t *ja, const uint32_t *jb, const double *la, const double *lb, const uint32_t *root,
-                           const double *rlen, const uint32_t *support, uint32_t n_rep) {
+                           const double *rlen, const uint32_t *support, uint32_t n_rep, const uint64_t *label_of) {
     check_rows(n);
     need(names, "names"); need(root, "root_node"); need(rlen, "root_len");
     const uint32_t steps = n > 3 ? n - 3 : 0, kids = n == 2 ? 2 : 3;
     if (steps) { need(ja, "join_a"); need(jb, "join_b"); need(la, "len_a"); need(lb, "len_b"); }
     const bool labels = steps && n_rep > 0;      // UC-N/B: the root carries none
-    if (labels) {
+    if (labels && !label_of) {
         need(support, "support");
         if (n_rep > NJ_BOOT_MAX_REPS) fail(UC_ERR_ARGS, "nj: %u replicates; 0 .. %u", n_rep, NJ_BOOT_MAX_REPS);
         for (uint32_t s = 0; s < steps; s++) if (support[s] > n_rep) fail(UC_ERR_ARGS, "nj: support %u of %u replicates at join %u", support[s], n_rep, s);
@@ -214,7 +214,7 @@ std::string nj_newick_line(const char *const *names, uint32_t n, const uint32_t 
             else if (f.st == 1) { append_len(out, la[s]); out += ','; st.back().st = 2; st.push_back(Frame{jb[s], 0}); }
             else {
                 append_len(out, lb[s]); out += ')'; st.pop_back();
-                if (labels) out += std::to_string((200ull * support[s] + n_rep) / (2ull * n_rep));      // the percentage, rounded half up
+                if (labels) out += std::to_string(label_of ? label_of[s] : (200ull * support[s] + n_rep) / (2ull * n_rep));      // the percentage, rounded half up
             }
         }
         append_len(out, rlen[t]);
@@ -301,11 +301,11 @@ void nj_main_tree(const char *msa_fasta, const char *model_name, const uc_opts *
     lap(3);
 }
 
-void nj_write_main_tree(const char *out_nwk, const NjMainTree &T, const uint32_t *support, uint32_t n_rep) {
+void nj_write_main_tree(const char *out_nwk, const NjMainTree &T, const uint32_t *support, uint32_t n_rep, const uint64_t *labels) {
     const uint32_t n = T.n;
     std::vector<const char *> names(n);
     for (uint32_t i = 0; i < n; i++) names[i] = T.names[i].c_str();
-    write_file(out_nwk, nj_newick_line(names.data(), n, T.ja.data(), T.jb.data(), T.la.data(), T.lb.data(), T.root, T.rlen, support, n_rep));
+    write_file(out_nwk, nj_newick_line(names.data(), n, T.ja.data(), T.jb.data(), T.la.data(), T.lb.data(), T.root, T.rlen, support, n_rep, labels));
     if (T.dump) {
         std::string txt;
         char b[128];
