@@ -54,10 +54,11 @@ def classify(ins):
     if op.startswith("s_waitcnt") or op == "s_nop" or op.startswith("s_delay"): return "waits / nops"
     if op.startswith("s_"): return "SALU"
     if dpp: return "VALU: lane shifts (DPP) — H, F, letters from the neighbour lane"
-    if op == "v_pk_maximum3_f16": return "VALU: v_pk_maximum3_f16 — H = max3(x, e, f); row / column maxima"
+    if op == "v_pk_maximum3_f16": return "VALU: v_pk_maximum3_f16 — H = max3(x, e, f); E' = max3(e - ext, h - open, bias); row / column maxima"
     if op == "v_perm_b32": return "VALU: v_perm_b32 — byte r of the two profile words -> packed u16 score"
-    if op in ("v_pk_add_u16", "v_pk_sub_u16"): return "VALU: v_pk_add/sub_u16 clamp — x = max(Hdiag + s, 0); h - open; e - ext; f - ext"
-    if op in ("v_pk_max_u16", "v_pk_max_i16", "v_pk_min_u16"): return "VALU: v_pk_max_u16 — E', F', best"
+    if op == "v_add3_u32": return "VALU: v_add3_u32 — x' = diag' + (s + 128) - 128 on the packed register (biased domain)"
+    if op in ("v_pk_add_u16", "v_pk_sub_u16"): return "VALU: v_pk_add/sub_u16 clamp — h - open; e - ext; f - ext (MODE 7 also x = max(Hdiag + s, 0))"
+    if op in ("v_pk_max_u16", "v_pk_max_i16", "v_pk_min_u16"): return "VALU: v_pk_max_u16 — F', best, the bias for lane 0's diagonal"
     if op.startswith("v_add") or op.startswith("v_and") or op.startswith("v_lshl") or op.startswith("v_mad") or op.startswith("v_mul") or op.startswith("v_or") or op.startswith("v_lshr") or op.startswith("v_bfe") or op.startswith("v_sub"):
         return "VALU: integer add / and / shift — profile word sums, LDS addresses"
     if op.startswith("v_cmp") or op.startswith("v_cndmask"): return "VALU: compare / select — first column of a new maximum"
@@ -95,10 +96,15 @@ def main():
         print("## sw_pk_kernel<%d, %d, %d, %d>: longest branch-free run = %d DP step(s), %d instructions, %d VALU; %d cells per lane -> %.3f VALU instructions per cell" % (G, R, a.mode, NW, steps, len(run), valu, cells, valu / cells))
         for k, v in sorted(cnt.items(), key=lambda kv: (not kv[0].startswith("VALU"), -kv[1])):
             print("  %5d  %6.3f / cell   %s" % (v, v / cells, k))
-        rec = (10 if a.mode == 0 else 9.5) * R * steps                      # per step and row: perm + add + sub + max3 + 3 sub + 2 max = 9, + colmax max3 every second row = 0.5, + rowbest max3 every second step = 0.5
-        print("  source-level count of the recurrence (uc_sw_pk_impl.hpp:284-300): per row and step 1 perm + 2 (x) + 1 max3 (h) + 3 sat-sub + 2 max = 9, "
+        x_ops = 2 if a.mode == 7 else 1                                         # MODE 7 keeps the unbiased domain: sat-add + sat-sub
+        rec = ((9 if a.mode == 0 else 8.5) + (x_ops - 1)) * R * steps         # per step and row: perm + add3 + max3 + 3 sub + max3 + max = 8, + colmax max3 every second row = 0.5, + rowbest max3 every second step = 0.5
+        ops = collections.Counter(i.split()[0] for i in run)
+        found = ops["v_perm_b32"] + ops["v_add3_u32"] + ops["v_pk_add_u16"] + ops["v_pk_sub_u16"] + ops["v_pk_maximum3_f16"] + ops["v_pk_max_u16"]
+        print("  source-level count of the recurrence (uc_sw_pk_impl.hpp:do_step): per row and step 1 perm + %d (x) + 1 max3 (h) + 3 sat-sub + 1 max3 (E') + 1 max (F') = %d, "
               "+ 0.5 column max3 + 0.5 row max3 (MODE 0 only) -> %d per run = %.3f per cell; the rest of the VALU count (%d = %.3f per cell) is per-STEP work "
-              "that R rows amortise: profile sums, LDS addressing, DPP shifts, first-column select, best" % (rec, rec / cells, valu - rec, (valu - rec) / cells))
+              "that R rows amortise: profile sums, LDS addressing, DPP shifts, first-column select, best" % (x_ops, 7 + x_ops, rec, rec / cells, valu - rec, (valu - rec) / cells))
+        print("  found in the run: %d perm, %d add3, %d pk_add, %d pk_sub, %d max3, %d pk_max = %d, i.e. %.2f per row and step (the per-step best / lane-0 bias maxima included)"
+              % (ops["v_perm_b32"], ops["v_add3_u32"], ops["v_pk_add_u16"], ops["v_pk_sub_u16"], ops["v_pk_maximum3_f16"], ops["v_pk_max_u16"], found, found / (R * steps)))
         print()
 
 

@@ -30,6 +30,42 @@ __global__ void check(unsigned long long *bad, unsigned long long *nan_small) {
     if (nb) atomicAdd(bad, nb);
     if (ns) atomicAdd(nan_small, ns);
 }
+// The biased score domain of uc_sw_pk_impl.hpp rests on two more properties (its header comment, "overflow"):
+//  claim 3: an operand in [0x7C00, 0x7FFF] (+inf, NaN with a clear sign bit) gives a result in [0x7C00, 0x7FFF], whatever the other two are - positive
+//           numbers, the negative patterns 0x8000 .. 0x807E an unfloored x' can take, or NaN themselves - and in whichever operand slot it stands:
+//           a stored H', E' never has its sign bit set, so the plain 32-bit add of the next x' cannot carry into the neighbouring half;
+//  claim 4: x' in [0x8000, 0x807E] loses against e' >= 0x0080: max3(x', e', f') = max(e', f') as unsigned integers (e', f' < 0x7C00).
+__global__ void check_biased(unsigned long long *bad_nan, unsigned long long *bad_neg) {
+    const uint32_t n = 0x7C00u + blockIdx.x;            // 1024 blocks: every pattern of [0x7C00, 0x7FFF]
+    unsigned long long b3 = 0, b4 = 0;
+    for (uint32_t o = threadIdx.x; o <= 0x807Eu; o += blockDim.x) {
+        const uint32_t others[6] = {0x0080u, 0u, 0x7BFFu, 0x8000u, 0x807Eu, 0x7E00u};
+        for (int k = 0; k < 6; k++) {
+            const uint32_t p = others[k];
+            // low half: (n, o, p) in the three rotations; high half: the same with o and p exchanged
+            const uint32_t r0 = pkmax3(n | (n << 16), o | (p << 16), p | (o << 16));
+            const uint32_t r1 = pkmax3(o | (p << 16), n | (n << 16), p | (o << 16));
+            const uint32_t r2 = pkmax3(o | (p << 16), p | (o << 16), n | (n << 16));
+            const uint32_t rs[3] = {r0, r1, r2};
+            for (int j = 0; j < 3; j++) {
+                const uint32_t lo = rs[j] & 0xFFFFu, hi = rs[j] >> 16;
+                if (lo < 0x7C00u || lo > 0x7FFFu) b3++;
+                if (hi < 0x7C00u || hi > 0x7FFFu) b3++;
+            }
+        }
+    }
+    // claim 4: x' = 0x8000 + (block % 127), e' over [0x0080, 0x7BFF], f' spread over [0, 0x7BFF]
+    const uint32_t x = 0x8000u + blockIdx.x % 127u;
+    for (uint32_t e = 0x0080u + threadIdx.x; e < 0x7C00u; e += blockDim.x)
+        for (uint32_t k = 0; k < 16; k++) {
+            const uint32_t f = (k * 0x7C1u + e * 13u + blockIdx.x) % 0x7C00u, e2 = 0x0080u + (e * 7u + k) % (0x7C00u - 0x0080u), f2 = (f * 5u + 1u) % 0x7C00u;
+            const uint32_t r = pkmax3(x | (x << 16), e | (e2 << 16), f | (f2 << 16));
+            if ((r & 0xFFFFu) != max(e, f)) b4++;
+            if ((r >> 16) != max(e2, f2)) b4++;
+        }
+    if (b3) atomicAdd(bad_nan, b3);
+    if (b4) atomicAdd(bad_neg, b4);
+}
 __global__ void __launch_bounds__(256) rate(uint32_t *out, int iters, uint32_t seed) {
     uint32_t a[8];
     for (int i = 0; i < 8; i++) a[i] = (seed * (threadIdx.x + 1) + i * 77) & 0x3FFF3FFFu;
@@ -49,6 +85,11 @@ int main() {
     hipLaunchKernelGGL(check, dim3(0x8000), dim3(256), 0, 0, d, d + 1);
     hipMemcpy(h, d, 16, hipMemcpyDeviceToHost);
     printf("mismatches below 0x7C00: %llu   lost overflows: %llu   (of %.3g packed triples)\n", h[0], h[1], 32768.0 * 32768.0 * 64);
+    unsigned long long h2[2] = {0, 0};
+    hipMemset(d, 0, 16);
+    hipLaunchKernelGGL(check_biased, dim3(1024), dim3(256), 0, 0, d, d + 1);
+    hipMemcpy(h2, d, 16, hipMemcpyDeviceToHost);
+    printf("biased domain: results outside [0x7C00, 0x7FFF] with an operand inside it: %llu   negative x' winning against e' >= 0x0080: %llu\n", h2[0], h2[1]);
     uint32_t *o; hipMalloc(&o, 256 * 8 * 256 * 4);
     hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
     const int iters = 20000, blocks = 256 * 8;

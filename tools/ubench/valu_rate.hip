@@ -14,6 +14,7 @@ __global__ void __launch_bounds__(256) k(uint32_t *out, int iters, uint32_t seed
     uint32_t a[8];
     for (int i = 0; i < 8; i++) a[i] = seed * (threadIdx.x + 1) + i * 77;
     uint32_t b = seed | 3;
+    [[maybe_unused]] const uint32_t bv = (seed | 3) + (threadIdx.x & 1);   // a per-lane (VGPR) second operand for the inline-asm kinds
     for (int it = 0; it < iters; it++) {
 #pragma unroll
         for (int u = 0; u < 4; u++)
@@ -29,6 +30,8 @@ __global__ void __launch_bounds__(256) k(uint32_t *out, int iters, uint32_t seed
                 if (KIND == 7) a[i] = (uint32_t)max(max((int)a[i], (int)(b + it)), (int)(b + i + u)) ^ 1u; // v_max3_i32 + v_xor
                 if (KIND == 9) a[i] = (a[i] + b) ^ 1u;                                   // v_add + v_xor (baseline pair)
                 if (KIND == 8) a[i] = (a[i] << 5) | (b & 31);                             // v_lshl_or_b32
+                if (KIND == 10) asm volatile("v_add3_u32 %0, %1, %2, %3" : "=v"(a[i]) : "v"(a[i]), "v"(bv), "s"(0xFF7FFF80u));   // v_add3_u32, third operand an SGPR (the biased x')
+                if (KIND == 11) asm volatile("v_pk_maximum3_f16 %0, %1, %2, %3" : "=v"(a[i]) : "v"(a[i]), "v"(bv), "s"(0x00800080u)); // max3 with an SGPR operand (the biased E')
             }
     }
     uint32_t s = 0;
@@ -55,5 +58,6 @@ int main() {
     uint32_t *d; hipMalloc(&d, 256 * 8 * 256 * 4);
     run<9>("v_add+v_xor", d); run<0>("v_max_i32+v_xor", d); run<7>("v_max3_i32+v_xor", d); run<6>("v_sub_u32 clamp", d); run<8>("v_lshl_or_b32", d); run<5>("v_dot4_i32_i8", d);
     run<1>("v_pk_max_u16+v_xor", d); run<2>("v_pk_sub_u16 clamp", d); run<3>("v_pk_add_u16 clamp", d); run<4>("v_perm_b32", d);
+    run<10>("v_add3_u32 v,v,s", d); run<11>("v_pk_maximum3_f16 v,v,s", d);
     return 0;
 }

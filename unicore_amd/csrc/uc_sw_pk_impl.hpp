@@ -2,11 +2,31 @@
 // systolic-group design it shares).  The int32 kernel is integer-VALU-bound (every int32 VALU instruction
 // occupies its SIMD for 4 cycles, profiles/round1/r1b_pmc_sw.txt), so the only lever left is instructions per cell:
 // here every DP register holds TWO alignments of the same query (target A in the low, target B in the high
-// 16 bits) and the recurrence runs on v_pk_{add,sub,max}_u16, i.e. ~6.3 VALU ops per cell instead of ~9.7.
+// 16 bits) and the recurrence runs on packed 16-bit VALU instructions, 8 per row and step (4 per cell) + 1 for the column and row maxima.
 //
-//  * unsigned floored domain: H >= 0, E/F/T floored at 0 by saturating subtraction (exact for local
-//    alignment); x = sat_sub(sat_add(Hdiag, s + 128), 128) = max(Hdiag + s, 0); H = max3(x, e, f) in one
-//    v_pk_maximum3_f16 (see SW_PK_OVF).
+//  * biased domain (every MODE but 7): registers hold H' = H + 128 and E' = E + 128 in either half; F' = F + 128 too, but floored at a true -128 only.
+//      x' = diag' + ub - 128   ONE plain 32-bit v_add3_u32 on the packed register, ub = s + 128 the profile byte sum and 0xFF7FFF80 (= -0x00800080) the
+//                              third addend.  Per half diag' >= 128 and 0 <= ub <= 255, so the two-operand sum carries out of no half and the subtraction
+//                              borrows from none.  (Written per half the constant would be 0xFF80FF80 - and wrong by one in the high half: the low half's sum
+//                              with 0xFF80 ALWAYS carries.)  x' is not floored: it stands for Hdiag + s >= -128.
+//      h'  = max3(x', e', f')  one v_pk_maximum3_f16 (see SW_PK_OVF).  e' >= 128 always, which is H's floor at a true 0.
+//      E'' = max3(e' - ext, h' - open, 128)   saturating subtracts; the third operand floors E at a true 0, exactly what the saturating subtract does in
+//                              the unbiased domain.  f'' = max(f' - ext, h' - open) needs no floor: a negative F never wins against e'.
+//    That is perm + add3 + max3 + 3 subtracts + max3 + max = 8, where the unbiased domain needs 9 (x = sat_sub(sat_add(Hdiag, ub), 128) is two).  H and
+//    E have the unbiased domain's value in every cell (tests/test_sw_bias_model.py: both recurrences cell by cell, the packed sums as 32-bit integers).
+//    Resets: H, E, Hlast, prevHup, best, rowbest = 0x00800080; f enters lane 0 as 0; the diagonal that lane 0 receives (0 from the DPP shift) is raised
+//    to the bias by one v_pk_max_u16 per step.  The three constants are SGPR operands of their instructions (pk_max3_s, pk_max_s, add3_s): no class
+//    holds a wave per SIMD less than before (profiles/biased_domain/kernel_resources.txt).  Out of the kernel go best - 128 and the unbiased known score.
+//  * overflow in the biased domain.  SW_PK_OVF stays 0x7C00 - 256 on the REPORTED (unbiased) score.  A reported score below it means every
+//    h' stayed below 0x7C00 - 128: only patterns the f16 maximum orders like integers took part, the result is exact.  A true score of 0x7C00 - 128 or more
+//    makes some h' >= 0x7C00, which every later max3 keeps (colmax) and the integer maximum `best` records: reported >= 0x7C00 - 128 > SW_PK_OVF.  So the
+//    flagged pairs are exactly those of the unbiased domain.  The add no longer saturates, yet a half never carries into its neighbour - which belongs
+//    to ANOTHER pair, whose result must stay exact: a stored value never exceeds 0x7FFF, because max3 returns one of its inputs or, if an input is a NaN
+//    pattern (0x7C01 .. 0x7FFF), a NaN with a clear sign bit, and the subtracts and the integer max only lower a value or pick one; so x' <= 0x7FFF + 127.
+//    An x' of 0x8000 .. 0x807E reads as a negative f16 and loses against e' >= 0x0080.  Both properties are checked exhaustively on the device by
+//    tools/ubench/pk_max3_f16.hip (check_biased); v_add3_u32 and the SGPR forms issue at the rate of the instructions they replace (valu_rate.hip).
+//  * MODE 7 keeps the unsigned floored domain (it stores H mod 256 for the walk): H >= 0, E/F/T floored at 0 by saturating subtraction (exact for
+//    local alignment); x = sat_sub(sat_add(Hdiag, s + 128), 128) = max(Hdiag + s, 0); H = max3(x, e, f).
 //  * profile bytes are (S3+64) and (SA+64) so the packed byte sum is s+128 (PAD = 0 => s = -128); one
 //    v_perm_b32 per row interleaves byte r of target A's and target B's word into two zero-extended u16.
 //  * end tracking: per lane the running maximum gives (score, first column) per half; per-row maxima
@@ -53,6 +73,25 @@ __device__ __forceinline__ uint32_t pk_max3(uint32_t a, uint32_t b, uint32_t c) 
     asm("v_pk_maximum3_f16 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
     return r;
 }
+// The constants of the biased domain are uniform: they reach their instruction as its one SGPR operand and cost no vector register.
+__device__ __forceinline__ uint32_t pk_max3_s(uint32_t a, uint32_t b, uint32_t c) {
+    uint32_t r;
+    asm("v_pk_maximum3_f16 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "s"(c));
+    return r;
+}
+__device__ __forceinline__ uint32_t pk_max_s(uint32_t a, uint32_t c) {
+    uint32_t r;
+    asm("v_pk_max_u16 %0, %1, %2" : "=v"(r) : "v"(a), "s"(c));
+    return r;
+}
+__device__ __forceinline__ uint32_t add3_s(uint32_t a, uint32_t b, uint32_t c) {   // a plain 32-bit sum of three
+    uint32_t r;
+    asm("v_add3_u32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "s"(c));
+    return r;
+}
+constexpr uint32_t SW_PK_BIAS = 128u * 0x10001u;       // H' = H + 128, E' = E + 128 in either half (every MODE but 7)
+constexpr uint32_t SW_PK_UNBIAS = 0u - SW_PK_BIAS;     // -128 in either half as ONE 32-bit addend: 0xFF7FFF80 (not 0xFF80FF80: see the header comment)
+static_assert(SW_PK_UNBIAS == 0xFF7FFF80u, "the packed -128");
 
 // K > 1: slots of the K tasks one workgroup serves (K * tcap / 2 at most: the launcher checks) and how a table entry names one: task << 6 | slot
 constexpr int SW_MQ_SLOTS = 128;
@@ -77,6 +116,7 @@ __global__ void __launch_bounds__(NW * 64) sw_pk_kernel(const SwArgs a) {
     // score): neighbouring cells differ by less than 128, so every H it needs is exact again, and every decision of the
     // traceback (diagonal / F / E, gap opened or extended) is a comparison of H values: alignment length, identities, gaps.
     constexpr bool TBB = MODE == 7;
+    constexpr uint32_t HB = TBB ? 0u : SW_PK_BIAS;   // what a true 0 of H and E looks like in a register
     constexpr bool KNOWN = MODE == 4 || MODE == 6;
     constexpr int BASE = KNOWN ? MODE - 4 : (TBB ? 0 : MODE);
     constexpr bool TRACK = BASE != 1 && !TBB, MASK = BASE == 2 || TBB, REVQ = BASE != 0, REVT = BASE == 2;
@@ -187,7 +227,7 @@ __global__ void __launch_bounds__(NW * 64) sw_pk_kernel(const SwArgs a) {
     // ---- per-group state (all group-uniform scalars live replicated in the group's lanes) ----
     uint32_t H[R], E[R], rowbest[(TRACK && !KNOWN) ? R : 1];   // E[r] holds the gap state ENTERING the next column (no separate H - open array)
     uint32_t mskA[MASK ? RW : 1], mskB[MASK ? RW : 1];
-    uint32_t best = 0, Hlast = 0, prevHup = 0, fout = 0;
+    uint32_t best = HB, Hlast = HB, prevHup = HB, fout = 0;
     // KNOWN: colA / colB hold the lane's whole first-answer state in one register, so that the second key below costs no occupancy step:
     // -1 = no optimal cell yet, else first optimal column << 6 | its first row (of this lane's R) << 1 | this lane saw the optimum in more than one of its rows
     int colA = -1, colB = -1;
@@ -329,17 +369,17 @@ __global__ void __launch_bounds__(NW * 64) sw_pk_kernel(const SwArgs a) {
             ltB = vB ? a.db.lt + toffB - (REVT ? 1 : 0) : a.db.lt + toffA - 1;
         }
 #pragma unroll
-        for (int r = 0; r < R; r++) { H[r] = 0; E[r] = 0; }
+        for (int r = 0; r < R; r++) { H[r] = HB; E[r] = HB; }
         if constexpr (TRACK && !KNOWN) {
 #pragma unroll
-            for (int r = 0; r < R; r++) rowbest[r] = 0;
+            for (int r = 0; r < R; r++) rowbest[r] = HB;
         }
-        if constexpr (KNOWN) {
-            knownA = (uint32_t)a.pscore[gA];
-            knownB = vB ? (uint32_t)a.pscore[gB] : 0u;
+        if constexpr (KNOWN) {   // compared with the biased column maximum: known + 128 (128 = no known score: the guard of the event test)
+            knownA = (uint32_t)a.pscore[gA] + 128u;
+            knownB = vB ? (uint32_t)a.pscore[gB] + 128u : 128u;
             key2A = 0x7fffffff; key2B = 0x7fffffff;
         }
-        best = 0; colA = -1; colB = -1; Hlast = 0; prevHup = 0; fout = 0;
+        best = HB; colA = -1; colB = -1; Hlast = HB; prevHup = HB; fout = 0;   // f enters as 0 = true -128: it never wins against e' >= 128
         lst = 0;
         nst = (max(tlenA, tlenB) + G) & ~1;      // Lt + G - 1 steps, rounded up to the 2-step loop trip
         c1 = pack_letters(issue_letters(1), 1);
@@ -368,14 +408,20 @@ __global__ void __launch_bounds__(NW * 64) sw_pk_kernel(const SwArgs a) {
         fetch_profile();
         const uint32_t Hup = (uint32_t)shift_from_prev_lane_zero<G>((int)Hlast, g);
         uint32_t f = (uint32_t)shift_from_prev_lane_zero<G>((int)fout, g);
+        // lane g = 0 received 0 from the shift: its diagonal is the bias (a true 0); every other lane's value is >= the bias already.  Raised here, at its
+        // use, and not on Hup: that keeps one register less alive across the row loop (profiles/biased_domain/README.md, 3)
         uint32_t diag = prevHup;
+        if constexpr (!TBB) diag = pk_max_s(prevHup, HB);
         uint32_t colmax = 0;
         [[maybe_unused]] uint32_t code[TBB ? R : 1];
 #pragma unroll
         for (int r = 0; r < R; r++) {
             // {byte r of A's word, 0, byte r of B's word, 0}
             const uint32_t ub = __builtin_amdgcn_perm(sB[r >> 2], sA[r >> 2], 0x0c000c00u | ((4u + (r & 3)) << 16) | (uint32_t)(r & 3));
-            const uint32_t x = pk_sub_sat(pk_add_sat(diag, ub), bias2);
+            // biased: x' = diag' + ub - 128 per half in one 32-bit add; not floored (it stands for Hdiag + s >= -128), e' >= 128 is H's floor
+            uint32_t x;
+            if constexpr (TBB) x = pk_sub_sat(pk_add_sat(diag, ub), bias2);
+            else x = add3_s(diag, ub, SW_PK_UNBIAS);
             const uint32_t e = E[r];                          // max(E - ext, H - open) of the previous column
             const uint32_t h = pk_max3(x, e, f);
             const uint32_t hprev = H[r];                      // this row one column earlier
@@ -384,7 +430,8 @@ __global__ void __launch_bounds__(NW * 64) sw_pk_kernel(const SwArgs a) {
             const uint32_t t = pk_sub_sat(h, open2);
             const uint32_t esub = pk_sub_sat(e, ext2), fsub = pk_sub_sat(f, ext2);
             if constexpr (TBB) code[r] = h;   // the cell's byte = H mod 256 of either half (packed into byte streams below)
-            E[r] = pk_max(esub, t);
+            if constexpr (TBB) E[r] = pk_max(esub, t);
+            else E[r] = pk_max3_s(esub, t, HB);           // the third operand floors E at a true 0, as the saturating subtract does in the unbiased domain
             f = pk_max(fsub, t);
             if constexpr (TRACK && !KNOWN) { if (ODD) rowbest[r] = pk_max3(rowbest[r], hprev, h); }
             if (r & 1) colmax = pk_max3(colmax, H[r - 1], h);   // two rows per instruction (R is even)
@@ -431,8 +478,8 @@ __global__ void __launch_bounds__(NW * 64) sw_pk_kernel(const SwArgs a) {
         if constexpr (KNOWN) {
             // every column of this lane that holds the optimum is an event (a handful per alignment: wave-level branch);
             // the first one gives (column, row); all of them together tell whether ONE row holds every optimal cell
-            const bool evA = knownA != 0 && (colmax & 0xffffu) == knownA;
-            const bool evB = knownB != 0 && (colmax >> 16) == knownB;
+            const bool evA = knownA != 128u && (colmax & 0xffffu) == knownA;
+            const bool evB = knownB != 128u && (colmax >> 16) == knownB;
             if (__builtin_amdgcn_ballot_w64(evA || evB) != 0) {
                 if (evA) {
                     int first = 0, cnt = 0;
@@ -462,6 +509,7 @@ __global__ void __launch_bounds__(NW * 64) sw_pk_kernel(const SwArgs a) {
     auto finish_slot = [&]() {
         if constexpr (TBB) return;
         if constexpr (KNOWN) {
+            knownA -= 128u; knownB -= 128u;   // unbiased for the output, in place: start_slot sets both anew
 #pragma unroll
             for (int half = 0; half < 2; half++) {
                 const int st1 = half ? colB : colA, col = st1 >> 6, row = (st1 >> 1) & 31;
@@ -519,11 +567,12 @@ __global__ void __launch_bounds__(NW * 64) sw_pk_kernel(const SwArgs a) {
             const bool valid = half ? vB : true;
             const uint32_t gp = half ? gB : gA;
             if (g == 0 && valid) {
-                a.oscore[gp] = score;
+                const int sc = score - 128;   // the reductions above compare biased values with biased values; what leaves the kernel is unbiased
+                a.oscore[gp] = sc;
                 if constexpr (TRACK) {
                     const int rowoff = half ? rowoffB : rowoffA;
                     int qe = -1, te = -1;
-                    if (score > 0) { te = col; qe = (cnt == 1 && score < SW_PK_OVF) ? minrow - rowoff : -2; }
+                    if (sc > 0) { te = col; qe = (cnt == 1 && sc < SW_PK_OVF) ? minrow - rowoff : -2; }
                     a.oqe[gp] = qe;
                     a.ote[gp] = te;
                 }
