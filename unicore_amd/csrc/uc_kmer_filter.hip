@@ -1,5 +1,7 @@
 // uc_kmer_filter.hip - prefilter stage E2 from the run lists to the surviving hit keys.
-// Consumes a query batch's runs per query position (cut_batch, uc_kmer_match.hip) and the chunk's index entries.
+// Consumes the plan of the batch's super-batch (plan_superbatch, uc_kmer_match.hip: the sorted run lists of the distinct k-mers, per query position where
+// its list starts and the running sum of the list lengths, per query its hits and runs) and the chunk's index entries.  There is no per-position copy
+// of the runs: run r of a query belongs to the last position whose run prefix is <= r and is read from that position's list (FILTER_PW below).
 // Produces the batch's (query, target, diagonal) keys, dense and sorted (QueryBatch::sorted / n_sort).  With min_diag_hits >= 2 (expand_keys_filtered) one
 // workgroup per query expands the query's runs through the double-hit filter in LDS (filter_kernel: two Bloom bitmaps, two levels) and only the keys that
 // share (target, diagonal) with another hit survive; queries of at most td_cap survivors are then sorted and evaluated on chip at once (launch_td_select,
@@ -36,9 +38,9 @@ __device__ __forceinline__ void ent_decode(const void *ent, uint32_t idx, const 
 // A workgroup takes 256 runs, scans their lengths, reserves the tile's key range with one atomic and then lets
 // thread k write key k of the tile (binary search in the LDS prefix): loads of index entries touch a handful of
 // lines per wave and the key stores are fully coalesced.
-__global__ void __launch_bounds__(256) expand_kernel(const DeviceDb db, uint32_t qbegin, uint32_t qend, uint32_t p0, RunList runs,
-                                                     uint64_t n_runs, const void *ent, KeyFmt fmt,
-                                                     unsigned long long *key_cursor, uint64_t *keys, uint64_t key_cap) {
+__global__ void __launch_bounds__(256) expand_kernel(const DeviceDb db, uint32_t qbegin, uint32_t qend, uint32_t P0, uint32_t b0, uint32_t b1,
+                                                     const uint32_t *src, const uint64_t *cumr, const uint64_t *drv, uint64_t n_runs, const void *ent,
+                                                     KeyFmt fmt, unsigned long long *key_cursor, uint64_t *keys, uint64_t key_cap) {
     __shared__ uint64_t s_pref[257];
     __shared__ uint64_t s_qb[256];
     __shared__ uint32_t s_e0[256];
@@ -46,13 +48,21 @@ __global__ void __launch_bounds__(256) expand_kernel(const DeviceDb db, uint32_t
     __shared__ uint64_t s_wsum[4];
     __shared__ unsigned long long s_base;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const uint64_t rbase = cumr[b0];
     for (uint64_t tile = blockIdx.x; tile * 256 < n_runs; tile += gridDim.x) {
         const uint64_t r = tile * 256 + tid;
         uint64_t c = 0;
         if (r < n_runs) {
-            const uint64_t rv = runs.val[r];
+            // the run's position: the last one of the batch [b0, b1) whose run prefix is <= r (a position without runs shares its prefix with the next
+            // one and is never the last); the run itself lies where the plan left it, in the list of the position's k-mer
+            uint32_t lo = b0, hi = b1;
+            while (hi - lo > 1) {
+                const uint32_t mid = lo + ((hi - lo) >> 1);
+                if (cumr[mid] - rbase <= r) lo = mid; else hi = mid;
+            }
+            const uint64_t rv = drv[src[lo] + (uint32_t)(r - (cumr[lo] - rbase))];
             c = rv >> 32;
-            const uint32_t p = p0 + runs.pidx[r];
+            const uint32_t p = P0 + lo;
             const uint32_t s = find_seq(db.off, qbegin, qend, p);
             s_e0[tid] = (uint32_t)rv;
             s_i[tid] = (int32_t)(p - db.off[s]) + fmt.dbias;
@@ -110,26 +120,24 @@ constexpr int KPT = 4;                 // consecutive keys per thread and binary
 // runs per tile = RPT x FT.  RPT = 2 (r4): half as many tile hand-overs (three workgroup barriers and the drain of 16 waves each) per
 // query; the prefix search takes 11 probes instead of 10
 constexpr int FILTER_RPT = 2;
-constexpr size_t filter_lds(int rpt) { return 2 * ((size_t)1 << FB_LOG2) / 8 + ((size_t)rpt * FT + 1) * 4 + (size_t)rpt * FT * 8 + 16 * 4 + 64; }
-
-// first run of every query of the batch (runs are sorted by query position): qr[i] = lower_bound(rpidx, off[qbegin + i] - p0),
-// i = 0..nq.  One thread per query here instead of two serial ~25-step searches at the head of every filter workgroup
-// (those cost ~20 us of the ~100 us a query spends in the filter kernel).
-__global__ void __launch_bounds__(256) run_range_kernel(const DeviceDb db, uint32_t qbegin, uint32_t nq, uint32_t p0, const uint32_t *rpidx,
-                                                        uint64_t n_runs, uint64_t *qr) {
-    for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i <= nq; i += gridDim.x * 256) {
-        const uint32_t want = db.off[qbegin + i] - p0;
-        uint64_t lo = 0, hi = n_runs;
-        while (lo < hi) { const uint64_t m = (lo + hi) >> 1; if (rpidx[m] < want) lo = m + 1; else hi = m; }
-        qr[i] = lo;
-    }
+// The filter reads a query's runs where the plan left them (plan_superbatch, uc_kmer_match.hip): run r of the query belongs to the last position whose run
+// prefix (d_cumr, relative to the query's first position) is <= r, and is entry r - prefix of the list of that position's k-mer (d_src into d_drv2).  The
+// prefix is staged in LDS once per workgroup so that finding a position costs no global load: FILTER_PW entries of prefix and list start are what fits
+// beside the bitmaps and the tile (160 KiB - filter_lds(RPT) < 100 B).  A query of at most FILTER_PW positions - nearly every protein - holds all of them and
+// a tile's runs cost one dependent global load, as they did when they were read from a copy.  A longer query keeps every 2^sh-th prefix entry, and a run
+// then takes sh probes of d_cumr and one load of d_src on top (L2 hits: a tile spans few positions): these queries have tens of tiles of ~40 us each,
+// behind whose expansion the next tile's fetch runs, and searching d_cumr alone would put ~10-16 such probes before every tile of EVERY query.
+constexpr int FILTER_PW = 1000;
+constexpr size_t filter_lds(int rpt) {
+    return 2 * ((size_t)1 << FB_LOG2) / 8 + ((size_t)rpt * FT + 1) * 4 + (size_t)rpt * FT * 8 + 16 * 4 + 64 + ((size_t)FILTER_PW + 1) * 4 + (size_t)FILTER_PW * 4;
 }
+static_assert(filter_lds(FILTER_RPT) <= 160 * 1024, "filter_kernel: one workgroup must fit the CU's LDS");
 
 // launch order of the filter workgroups: queries with the most runs first (longest-processing-time-first: a batch then ends
-// with many short queries instead of a few long ones; the tail was ~20 % of the kernel)
-__global__ void __launch_bounds__(256) run_order_key_kernel(uint32_t nq, const uint64_t *qr, uint32_t *key, uint32_t *idx) {
+// with many short queries instead of a few long ones; the tail was ~20 % of the kernel).  qrn: the plan's runs per query, from the batch's first query on
+__global__ void __launch_bounds__(256) run_order_key_kernel(uint32_t nq, const uint64_t *qrn, uint32_t *key, uint32_t *idx) {
     for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < nq; i += gridDim.x * 256) {
-        const uint64_t c = qr[i + 1] - qr[i];
+        const uint64_t c = qrn[i];
         key[i] = 0xFFFFFFFFu - (uint32_t)min<uint64_t>(c, 0xFFFFFFFFull);
         idx[i] = i;
     }
@@ -141,8 +149,8 @@ template <> struct TdType<true> { using type = uint32_t; };
 // (Measured and removed, profiles/r03_filter_ab.log: 1024-run tiles — 2.5 % slower; a blocked Bloom filter with both hash positions of a key in one
 // 64-bit LDS word, one ds_or_rtn_b64 instead of two dependent 32-bit atomic pairs — no gain: the kernel is not bound by its LDS atomics.)
 template <bool C>
-__global__ void __launch_bounds__(FT) filter_kernel(const DeviceDb db, uint32_t qbegin, uint32_t p0, const uint32_t *rpidx,
-                                                    const uint64_t *rval, const uint64_t *qr, const uint32_t *order, const void *ent, KeyFmt fmt,
+__global__ void __launch_bounds__(FT) filter_kernel(const DeviceDb db, uint32_t qbegin, uint32_t P0, const uint32_t *psrc, const uint64_t *cumr,
+                                                    const uint64_t *drv, const uint64_t *qh, const uint32_t *order, const void *ent, KeyFmt fmt,
                                                     unsigned long long *region_cursor, void *region_v, uint64_t region_cap,
                                                     uint64_t *qbase, uint32_t *qsurv) {
     using TD = typename TdType<C>::type;
@@ -156,17 +164,28 @@ __global__ void __launch_bounds__(FT) filter_kernel(const DeviceDb db, uint32_t 
     uint2 *s_run = (uint2 *)(f_lds + 2 * BW);                   // TR: {first index entry - prefix, query position + bias}: ONE 8-byte read per key
     uint32_t *s_pref = (uint32_t *)(s_run + TR);                // TR + 1 (hits of one query < 2^32: checked by the host)
     uint32_t *s_wsum = s_pref + TR + 1;                         // 16
-    uint64_t *s_misc = (uint64_t *)(((uintptr_t)(s_wsum + 16) + 7) & ~(uintptr_t)7);   // [0] r0, [1] r1, [2] region base, [3] cursors (2 x u32)
+    uint64_t *s_misc = (uint64_t *)(((uintptr_t)(s_wsum + 16) + 7) & ~(uintptr_t)7);   // [2] region base, [3] cursors (2 x u32)
+    uint32_t *s_pp = (uint32_t *)(s_misc + 4);                  // FILTER_PW + 1: run prefix of every 2^sh-th position of the query (runs of one query < 2^32)
+    uint32_t *s_src = s_pp + FILTER_PW + 1;                     // FILTER_PW: where the run list of position i starts in drv (sh == 0 only)
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const uint32_t qi = order[blockIdx.x];                      // query of this workgroup (index inside the batch)
     const uint32_t q = qbegin + qi;
-    const uint32_t plo = db.off[q] - p0;
-    const uint64_t r0 = qr[qi], r1 = qr[qi + 1];
+    const uint32_t pq = db.off[q] - P0, L = db.off[q + 1] - db.off[q];     // the query's positions in the plan: [pq, pq + L)
+    const uint64_t c0 = cumr[pq];
+    const uint64_t r0 = 0, r1 = cumr[pq + L] - c0;              // its runs, counted from its first one
     TD *surv = region + region_cap;                             // second area of the same size: survivors of sweep 2
     for (int w = tid; w < 2 * BW; w += FT) f_lds[w] = 0;
     if (r0 == r1) {
         if (tid == 0) { qbase[qi] = 0; qsurv[qi] = 0; }
         return;
+    }
+    // the position prefix (comment at FILTER_PW): ns samples, one per 2^sh positions
+    int sh = 0;
+    while (((L + (1u << sh) - 1) >> sh) > (uint32_t)FILTER_PW) sh++;
+    const int ns = (int)((L + (1u << sh) - 1) >> sh);
+    for (int i = tid; i < ns; i += FT) {
+        s_pp[i] = (uint32_t)(cumr[pq + ((uint32_t)i << sh)] - c0);
+        if (sh == 0) s_src[i] = psrc[pq + i];
     }
 
     // loads one tile of runs, leaves the exclusive prefix of their lengths in s_pref[0..FT] (s_pref[FT] = total)
@@ -175,10 +194,31 @@ __global__ void __launch_bounds__(FT) filter_kernel(const DeviceDb db, uint32_t 
     uint64_t pf_rv[RPT] = {};
     uint32_t pf_pi[RPT] = {};
     auto prefetch_tile = [&](uint64_t tile) {      // thread tid owns runs tile + RPT * tid .. + RPT - 1 (consecutive: the prefix stays a plain scan)
+        // the last sample whose prefix is <= r: a position without runs has the prefix of the one behind it and is never the last.  One search for the
+        // thread's first run; the following ones are in the same sample or a few further on
+        int lo = 0, hi = ns;
+        if (tile + (uint64_t)RPT * tid < r1)
+            while (hi - lo > 1) {
+                const int mid = (lo + hi) >> 1;
+                if (s_pp[mid] <= (uint32_t)(tile + (uint64_t)RPT * tid)) lo = mid; else hi = mid;
+            }
 #pragma unroll
         for (int j = 0; j < RPT; j++) {
             const uint64_t r = tile + (uint64_t)RPT * tid + j;
-            if (r < r1) { pf_rv[j] = rval[r]; pf_pi[j] = rpidx[r]; }
+            if (r < r1) {
+                if (j) while (lo + 1 < ns && s_pp[lo + 1] <= (uint32_t)r) lo++;
+                uint32_t pos = (uint32_t)lo << sh, pre = s_pp[lo], first;
+                if (sh) {                          // ... and the last position of that sample's 2^sh
+                    uint32_t phi = min(pos + (1u << sh), L);
+                    while (phi - pos > 1) {
+                        const uint32_t mid = pos + ((phi - pos) >> 1), v = (uint32_t)(cumr[pq + mid] - c0);
+                        if (v <= (uint32_t)r) { pos = mid; pre = v; } else phi = mid;
+                    }
+                    first = psrc[pq + pos];
+                } else first = s_src[pos];
+                pf_rv[j] = drv[first + ((uint32_t)r - pre)];
+                pf_pi[j] = pos;                    // position inside the query
+            }
         }
     };
     auto load_tile = [&](uint64_t tile) {
@@ -202,7 +242,7 @@ __global__ void __launch_bounds__(FT) filter_kernel(const DeviceDb db, uint32_t 
 #pragma unroll
         for (int j = 0; j < RPT; j++) {
             s_pref[RPT * tid + j] = pre;
-            s_run[RPT * tid + j] = make_uint2((uint32_t)pf_rv[j] - pre, (uint32_t)((int32_t)(pf_pi[j] - plo) + fmt.dbias));
+            s_run[RPT * tid + j] = make_uint2((uint32_t)pf_rv[j] - pre, (uint32_t)((int32_t)pf_pi[j] + fmt.dbias));
             pre += c[j];
         }
         if (tid == FT - 1) s_pref[TR] = pre;
@@ -265,30 +305,22 @@ __global__ void __launch_bounds__(FT) filter_kernel(const DeviceDb db, uint32_t 
         return ((B2[h >> 5] >> (h & 31)) & (B2[g >> 5] >> (g & 31))) & 1u;
     };
 
-    // the query's region: its exact hit total is the sum of its run lengths; reserve it first (rounded up to KPT keys)
-    {
-        uint64_t part = 0;
-        for (uint64_t r = r0 + tid; r < r1; r += FT) part += rval[r] >> 32;
-        for (int o = 32; o > 0; o >>= 1) part += __shfl_down(part, o, 64);
-        uint64_t *s_part = (uint64_t *)s_pref;      // not in use yet
-        if (lane == 0) s_part[wv] = part;
-        __syncthreads();
-        if (tid == 0) {
-            uint64_t tot = 0;
-            for (int w = 0; w < FT / 64; w++) tot += s_part[w];
-            s_misc[2] = atomicAdd(region_cursor, (unsigned long long)((tot + KPT - 1) / KPT * KPT));
-            ((uint32_t *)&s_misc[3])[0] = 0;
-            ((uint32_t *)&s_misc[3])[1] = 0;
-        }
-        __syncthreads();
+    // the query's region: its exact hit total is the plan's (d_qh); reserve it first (rounded up to KPT keys).  The barrier also publishes the prefix
+    if (tid == 0) {
+        s_misc[2] = atomicAdd(region_cursor, (unsigned long long)((qh[qi] + KPT - 1) / KPT * KPT));
+        ((uint32_t *)&s_misc[3])[0] = 0;
+        ((uint32_t *)&s_misc[3])[1] = 0;
     }
+    __syncthreads();
     const uint64_t base = s_misc[2];
     uint32_t *cur = (uint32_t *)&s_misc[3];
     uint32_t total = 0;
     prefetch_tile(r0);
     for (uint64_t tile = r0; tile < r1; tile += TR) {
         load_tile(tile);
-        prefetch_tile(tile + TR);
+        // the next tile's fetch starts behind the first gathers of this one: its search in the LDS prefix (~10 dependent reads) then runs while the
+        // index entries are on their way, instead of between the barrier and the first gather
+        bool fetched = false;
         const uint32_t T = s_pref[TR];
         using ET = typename std::conditional<C, uint32_t, uint64_t>::type;
         auto mark_store = [&](TD4 &td, int n, uint32_t k4) {
@@ -315,12 +347,14 @@ __global__ void __launch_bounds__(FT) filter_kernel(const DeviceDb db, uint32_t 
             ET ea[KPT], eb[KPT];
             gather(ia, ea);
             gather(ib, eb);
+            if (!fetched) { prefetch_tile(tile + TR); fetched = true; }
             TD4 ta, tb;
             to_td(ea, sa, ta.v);
             mark_store(ta, na, k4);
             to_td(eb, sb, tb.v);
             mark_store(tb, k4b < T ? nb : 0, k4b);
         }
+        if (!fetched) prefetch_tile(tile + TR);      // (a thread without a key in this tile)
         total += T;
         __syncthreads();
     }
@@ -454,21 +488,19 @@ uint64_t compact_u64(Engine &E, DevBuf<char> &tmp, uint32_t *cnt, uint64_t *pos,
 void expand_keys_filtered(Engine &E, PrefilterPass &PP, QueryBatch &B) {
     PrefilterScratch &S = *E.pre;
     const KeyFmt &fmt = PP.fmt;
-    const uint32_t qa = B.qa, qp0 = B.qp0, nq = B.qb - B.qa;
+    const uint32_t qa = B.qa, nq = B.qb - B.qa;
     S.batch.d_qbase.reserve(nq); S.batch.d_qsurv.reserve(nq); S.batch.d_soff.reserve((size_t)nq + 1);
     // the query regions hold (target, diagonal) keys: u32 in compact mode (half of the u64 buffer stays unused),
     // every region rounded up to KPT keys
     const uint64_t region_cap = B.total_hits + (uint64_t)KPT * nq;
     S.batch.d_keys.reserve(fmt.compact ? region_cap : 2 * region_cap);       // regions + survivor area of the same size
-    S.batch.d_qr.reserve((size_t)nq + 1);
-    hipLaunchKernelGGL(run_range_kernel, grid_for((uint64_t)nq + 1), dim3(256), 0, E.stream, E.ddb, qa, nq, qp0, S.batch.d_rpidx2.p, B.n_runs, S.batch.d_qr.p);
     S.batch.d_okey.reserve(nq); S.batch.d_okey2.reserve(nq); S.batch.d_oidx.reserve(nq); S.batch.d_order.reserve(nq);
-    hipLaunchKernelGGL(run_order_key_kernel, grid_for(nq), dim3(256), 0, E.stream, nq, S.batch.d_qr.p, S.batch.d_okey.p, S.batch.d_oidx.p);
+    hipLaunchKernelGGL(run_order_key_kernel, grid_for(nq), dim3(256), 0, E.stream, nq, S.plan.d_qrn.p + (qa - B.plan_q0), S.batch.d_okey.p, S.batch.d_oidx.p);
     rocprim_call(S.shared.d_temp, [&](void *t, size_t &b) { return rocprim::radix_sort_pairs(t, b, S.batch.d_okey.p, S.batch.d_okey2.p, S.batch.d_oidx.p, S.batch.d_order.p, (size_t)nq, 0u, 32u, E.stream); });
     auto launch = [&](auto kern) {
         static PerDeviceOnce once[2];
         once[fmt.compact ? 1 : 0]([&] { UC_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)filter_lds(FILTER_RPT))); });
-        hipLaunchKernelGGL(kern, dim3(nq), dim3(FT), filter_lds(FILTER_RPT), E.stream, E.ddb, qa, qp0, S.batch.d_rpidx2.p, S.batch.d_rval2.p, S.batch.d_qr.p, S.batch.d_order.p, PP.ent_p, fmt,
+        hipLaunchKernelGGL(kern, dim3(nq), dim3(FT), filter_lds(FILTER_RPT), E.stream, E.ddb, qa, B.plan_p0, S.plan.d_src.p, S.plan.d_cumr.p, S.plan.d_drv2.p, S.plan.d_qh.p + (qa - B.plan_q0), S.batch.d_order.p, PP.ent_p, fmt,
                            S.shared.d_counters.p + 5, (void *)S.batch.d_keys.p, region_cap, S.batch.d_qbase.p, S.batch.d_qsurv.p);
     };
     if (fmt.compact) launch(filter_kernel<true>);
@@ -506,13 +538,13 @@ void expand_keys_filtered(Engine &E, PrefilterPass &PP, QueryBatch &B) {
 void expand_keys_plain(Engine &E, PrefilterPass &PP, QueryBatch &B) {
     PrefilterScratch &S = *E.pre;
     S.batch.d_keys.reserve(B.total_hits); S.batch.d_keys2.reserve(B.total_hits);
-    const RunList rl{S.batch.d_rpidx2.p, S.batch.d_rval2.p, PP.run_cap};
-    hipLaunchKernelGGL(expand_kernel, grid_for(B.n_runs), dim3(256), 0, E.stream, E.ddb, B.qa, B.qb, B.qp0, rl, B.n_runs, PP.ent_p, PP.fmt,
+    hipLaunchKernelGGL(expand_kernel, grid_for(B.n_runs), dim3(256), 0, E.stream, E.ddb, B.qa, B.qb, B.plan_p0, B.qp0 - B.plan_p0, B.qp1 - B.plan_p0,
+                       S.plan.d_src.p, S.plan.d_cumr.p, S.plan.d_drv2.p, B.n_runs, PP.ent_p, PP.fmt,
                        S.shared.d_counters.p + 5, S.batch.d_keys.p, B.total_hits);
     rocprim_call(S.shared.d_temp, [&](void *t, size_t &b) { return rocprim::radix_sort_keys(t, b, S.batch.d_keys.p, S.batch.d_keys2.p, (size_t)B.total_hits, 0u, B.kbits, E.stream); });
     B.sorted = S.batch.d_keys2.p; B.n_sort = B.total_hits;
     E.stats.n_filtered_hits += B.n_sort;
 }
 
-void preload_kmer_filter_module() { hipFuncAttributes fa; (void)hipFuncGetAttributes(&fa, (const void *)run_range_kernel); }
+void preload_kmer_filter_module() { hipFuncAttributes fa; (void)hipFuncGetAttributes(&fa, (const void *)run_order_key_kernel); }
 }  // namespace uc

@@ -4,7 +4,8 @@
 // (20^6 + 1 u32) and an 8 MB presence bitmap of the k-mers that occur; (b) the plan of a query super-batch (plan_superbatch): the DISTINCT k-mers of its
 // queries, the similar k-mers of each (sim_runs_kernel: sorted-letter DFS with a score bound as a per-lane state machine, the bitmap in front of the
 // offset table) as index ranges ("runs") sorted by k-mer rank, and per query position the length and source of its run list and its k-mer hits;
-// (c) an exact query batch with its runs laid out per query position (cut_batch), which uc_kmer_filter.hip expands.
+// with the running sums of both and the totals per query; (c) an exact query batch (cut_batch): the queries whose hits and runs fit the key buffers, cut
+// on the plan's per-query totals.  Nothing is copied for it: uc_kmer_filter.hip reads a batch's runs where the plan left them.
 // Sort and scan primitives come from rocPRIM; every kernel below is hand-written for wave64 (spec UC-1 E1-E2).
 #include <hip/hip_runtime.h>
 
@@ -462,32 +463,6 @@ __global__ void __launch_bounds__(256) query_totals_kernel(const uint32_t *off, 
     }
 }
 
-// a wave lays out the run lists of 64 consecutive positions of the batch [b0, b1): position order, runs of one position contiguous
-__global__ void __launch_bounds__(256) position_expand_kernel(uint32_t b0, uint32_t b1, const uint32_t *nr, const uint32_t *src, const uint64_t *cumr,
-                                                              const uint64_t *val, uint32_t *opidx, uint64_t *oval) {
-    const int lane = threadIdx.x & 63;
-    const uint64_t nwaves = (uint64_t)gridDim.x * 4, w0 = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    const uint64_t rbase = cumr[b0];
-    for (uint64_t base = b0 + w0 * 64; base < b1; base += nwaves * 64) {
-        const uint64_t idx = base + lane;
-        uint32_t n = 0, s = 0, dst = 0;
-        if (idx < b1) {
-            n = nr[idx];
-            if (n) { s = src[idx]; dst = (uint32_t)(cumr[idx] - rbase); }
-        }
-        uint64_t m = __builtin_amdgcn_ballot_w64(n != 0);
-        while (m) {
-            const int j = __builtin_ctzll(m);
-            m &= m - 1;
-            const uint32_t nj = (uint32_t)__shfl((int)n, j, 64), sj = (uint32_t)__shfl((int)s, j, 64), dj = (uint32_t)__shfl((int)dst, j, 64);
-            for (uint32_t i = lane; i < nj; i += 64) {
-                oval[dj + i] = val[sj + i];
-                opidx[dj + i] = (uint32_t)(base + j - b0);
-            }
-        }
-    }
-}
-
 // consumes max_len, the sequence count and the chunk's target range; produces the layout of the (query, target, diagonal) keys
 KeyFmt key_format(const Engine &E, uint32_t tbegin, uint32_t tend) {
     KeyFmt fmt;
@@ -589,7 +564,7 @@ uint64_t distinct_runs(Engine &E, PrefilterPass &PP, const SuperBatch &SB, uint3
 //      of its distinct k-mers exceed DRUN_MAX, i.e. at high sensitivity): similar k-mers and index ranges of every
 //      DISTINCT query k-mer, then per query position the length and source of its run list and its k-mer hits; exact
 //      per-query totals for the batch plan ----
-// consumes the index and queries [sa, sb); produces SB and the sorted runs (d_drv2) with d_nr / d_src / d_cumr per position, which cut_batch expands
+// consumes the index and queries [sa, sb); produces SB and the sorted runs (d_drv2) with d_nr / d_src / d_cumr per position and d_qh / d_qrn per query, which the filter reads
 PlanResult plan_superbatch(Engine &E, PrefilterPass &PP, SuperBatch &SB, uint32_t sa, uint32_t sb) {
     PrefilterScratch &S = *E.pre;
     uint64_t plan_hits = 0;
@@ -676,7 +651,7 @@ bool choose_superbatch(Engine &E, PrefilterPass &PP, SuperBatch &SB, uint32_t qa
     }
 }
 
-// consumes the plan of SB and the first query qa; produces the exact batch [qa, qb) and its runs per query position (d_rpidx2 / d_rval2)
+// consumes the plan of SB and the first query qa; produces the exact batch [qa, qb).  It launches nothing: the batch's runs stay where the plan left them
 QueryBatch cut_batch(Engine &E, PrefilterPass &PP, const SuperBatch &SB, uint32_t qa) {
     PrefilterScratch &S = *E.pre;
     QueryBatch B;
@@ -692,12 +667,8 @@ QueryBatch cut_batch(Engine &E, PrefilterPass &PP, const SuperBatch &SB, uint32_
     }
     if (B.n_runs >= (1ull << 32)) fail(UC_ERR_GENERIC, "query %u alone produces %llu index ranges", qa, (unsigned long long)B.n_runs);
     B.qp0 = E.h_poff[qa]; B.qp1 = E.h_poff[B.qb]; B.nq_res = B.qp1 - B.qp0;
-    PP.run_cap = std::max<uint64_t>(PP.run_cap, B.n_runs);
-    S.batch.d_rpidx2.reserve(PP.run_cap); S.batch.d_rval2.reserve(PP.run_cap);
+    B.plan_p0 = SB.P0; B.plan_q0 = SB.begin;
     UC_HIP(hipMemsetAsync(S.shared.d_counters.p + 3, 0, 32, E.stream));   // run cursor, batch hits, key cursor, candidate cursor
-    if (B.n_runs)
-        hipLaunchKernelGGL(position_expand_kernel, grid_for(B.nq_res), dim3(256), 0, E.stream, B.qp0 - SB.P0, B.qp1 - SB.P0, S.plan.d_nr.p, S.plan.d_src.p, S.plan.d_cumr.p, S.plan.d_drv2.p,
-                           S.batch.d_rpidx2.p, S.batch.d_rval2.p);
     if (B.total_hits > (1ull << 34)) fail(UC_ERR_GENERIC, "query %u alone produces %llu k-mer hits", qa, (unsigned long long)B.total_hits);
     PP.n_hits_total += B.total_hits + mirror_hits;
     unsigned qbits = 1;

@@ -4,8 +4,9 @@
 //   E1  build_index (uc_kmer_match.hip): (k-mer, sequence, position) per target residue -> radix sort by k-mer -> offsets per k-mer slot (20^6 + 1 u32 =
 //       256 MB) and an 8 MB presence bitmap of the k-mers that occur, which answers most lookups at high sensitivity without touching the offset table.
 //   E2  plan_superbatch: the similar k-mers (sorted-letter DFS with score bound) and their non-empty index ranges ("runs") are enumerated once per DISTINCT
-//       k-mer of a query super-batch, sorted by k-mer rank, and laid out per query position - already in position order - for every exact batch that
-//       cut_batch fits into the key and run buffers.  A super-batch whose run lists would exceed DRUN_MAX is cut (choose_superbatch).
+//       k-mer of a query super-batch and sorted by k-mer rank; per query position the plan keeps where its k-mer's list starts and the running sum of
+//       the list lengths.  cut_batch cuts exact batches that fit the key buffers on the plan's per-query totals and copies nothing: the filter reads a
+//       query's runs from the lists.  A super-batch whose run lists would exceed DRUN_MAX is cut (choose_superbatch).
 //       expand_keys_filtered (uc_kmer_filter.hip): one workgroup per query expands its runs through the same-diagonal double-hit filter in LDS and keeps
 //       the (target, diagonal) keys seen twice; min_diag_hits 1 uses a plain expansion (expand_keys_plain).
 //       select_diagonals (uc_diag_select.hip): per (query, target) the diagonal with the most hits.  Queries of at most TDS_CAP surviving keys are sorted and

@@ -89,19 +89,17 @@ struct IndexScratch {
     template <class F> void each(F &f) { f(d_koff); f(k_in); f(k_out); f(d_ent32); f(v_in32); f(d_ent); f(v_in); f(d_kbits); }
 };
 UC_LISTS_EVERY_BUFFER(IndexScratch, 8);
-// cut_batch: the runs of a batch per query position (d_rpidx2 / d_rval2); expand_keys_filtered / expand_keys_plain: the launch order of the filter's
-// workgroups (d_okey .. d_order), the first run of every query (d_qr), the key regions (d_keys), where a query's survivors lie and how many they are
-// (d_qbase / d_qsurv / d_soff), the dense keys and the sort's output (d_keys2).  td_select_kernel sorts inside d_keys and zeroes d_qsurv of the
-// queries it took; cand_gather_kernel reads the records it left in d_keys
+// expand_keys_filtered / expand_keys_plain: the launch order of the filter's workgroups (d_okey .. d_order), the key regions (d_keys), where a query's
+// survivors lie and how many they are (d_qbase / d_qsurv / d_soff), the dense keys and the sort's output (d_keys2).  td_select_kernel sorts inside d_keys
+// and zeroes d_qsurv of the queries it took; cand_gather_kernel reads the records it left in d_keys.  cut_batch fills nothing here: a batch's runs are
+// read where the plan left them (PlanScratch)
 struct BatchScratch {
     DevBuf<uint32_t> d_okey, d_okey2, d_oidx, d_order;
-    DevBuf<uint32_t> d_rpidx2, d_qsurv;
-    DevBuf<uint64_t> d_keys, d_keys2, d_rval2, d_qbase, d_soff, d_qr;
-    template <class F> void each(F &f) {
-        f(d_okey); f(d_okey2); f(d_oidx); f(d_order); f(d_rpidx2); f(d_qsurv); f(d_keys); f(d_keys2); f(d_rval2); f(d_qbase); f(d_soff); f(d_qr);
-    }
+    DevBuf<uint32_t> d_qsurv;
+    DevBuf<uint64_t> d_keys, d_keys2, d_qbase, d_soff;
+    template <class F> void each(F &f) { f(d_okey); f(d_okey2); f(d_oidx); f(d_order); f(d_qsurv); f(d_keys); f(d_keys2); f(d_qbase); f(d_soff); }
 };
-UC_LISTS_EVERY_BUFFER(BatchScratch, 12);
+UC_LISTS_EVERY_BUFFER(BatchScratch, 9);
 // rescore_ungapped (E3): d_score, which prefilter_exhaustive fills from its tiles instead; select_and_append (E4) and merge_hits_dev, which run the same
 // sort / rank / truncate / scatter: sort keys and the sorted diagonals (d_skey / d_skey2 / d_cd2), the rank flags and their positions (d_flag / d_pos);
 // finish_hit_lists: d_cnt.  partition_hits_by_owner borrows d_flag and d_cnt as its index arrays
@@ -126,7 +124,8 @@ struct CandScratch {
 UC_LISTS_EVERY_BUFFER(CandScratch, 8);
 // plan_superbatch / distinct_runs: the distinct k-mers of a super-batch (d_kflag, d_kid: rank of every k-mer, d_dk: the list, d_nsimk), their runs unsorted
 // (d_drk / d_drv) and sorted by rank (d_drk2 / d_drv2), per rank d_roff / d_rec, per query position d_qk / d_nr / d_src / d_ph and the running sums d_cumh /
-// d_cumr, per query d_qh / d_qrn.  cut_batch reads d_nr, d_src, d_cumr and d_drv2
+// d_cumr, per query d_qh / d_qrn.  filter_kernel and expand_kernel read the runs of an exact batch from here (d_src, d_cumr, d_drv2, d_qh), the launch
+// order of the filter's workgroups comes from d_qrn
 struct PlanScratch {
     DevBuf<uint8_t> d_kflag;
     DevBuf<uint32_t> d_qk, d_kid, d_dk, d_nsimk, d_drk, d_drk2, d_roff, d_nr, d_src, d_ph;
@@ -199,7 +198,7 @@ struct PrefilterScratch {
 };
 
 // ---- E1-E4 for ONE target chunk (prefilter_one): a short driver over passes that share this state ----------
-constexpr uint64_t RUN_MAX = 1ull << 29;       // runs per batch (6 GiB + 6 GiB sort double buffer)
+constexpr uint64_t RUN_MAX = 1ull << 29;       // runs per batch (the bound of the batches since they had run buffers of their own; kept: it decides the cuts)
 struct PrefilterPass {
     KmerCfg cfg;
     KeyFmt fmt;
@@ -213,7 +212,7 @@ struct PrefilterPass {
     uint64_t HIT_CAP = 0, HIT_CAP_BIG = 0, DRUN_MAX = 0;
     uint64_t td_queries = 0, td_keys = 0, filt_queries = 0, filt_keys = 0;   // what td_select_kernel took of the filter's queries and survivors (UC_TIMING)
     uint32_t td_cap = 0;                       // td_select_kernel takes the queries with at most this many survivors (0: none, UC_TD_ONCHIP=0)
-    uint64_t n_hits_total = 0, n_cand_total = 0, cand_cap = 0, run_cap = 1ull << 20;
+    uint64_t n_hits_total = 0, n_cand_total = 0, cand_cap = 0;
     double t_kmer = 0, t_ung = 0, t_sel = 0, gpu_ms = 0;   // host seconds of E2 / E3 / E4 and the event time of everything
 };
 // a query "super-batch" [begin, end) of the chunk with what its plan leaves for the exact batches
@@ -229,6 +228,8 @@ struct QueryBatch {
     uint32_t qa = 0, qb = 0;
     uint64_t total_hits = 0, n_runs = 0;
     uint32_t qp0 = 0, qp1 = 0, nq_res = 0;     // its residue positions
+    uint32_t plan_p0 = 0, plan_q0 = 0;         // first position and first query of its super-batch: the plan's per-position arrays are indexed by position -
+                                               // plan_p0, the per-query ones by query - plan_q0
     unsigned kbits = 0;                        // significant bits of its keys [query - qa | target | diagonal]
     const uint64_t *sorted = nullptr;          // the n_sort keys in that order
     uint64_t n_sort = 0;
