@@ -208,6 +208,23 @@ def count_cases_small():
     return out
 
 
+@functools.lru_cache(maxsize=None)
+def route_cases(L):
+    """name -> D for the single entry point on both sides of the batch's LDS route (L rows and L + 1), at the smallest trees (4 has one step) and at 257, the
+    first n where a row of pairs takes a second stride of 256 threads and the row sums a second workgroup.  Per size a tree metric, the all-zero
+    matrix (every Q equal: the index tie-break alone decides, across waves and across partials) and a matrix with duplicated rows"""
+    cases = {}
+    for n in (4, 5, L, L + 1, 257):
+        cases["tree_%d" % n] = tree_metric(random_tree(random.Random(1100 + n), n), n)
+        cases["zero_%d" % n] = np.zeros((n, n))
+        dup = random_matrix(random.Random(1200 + n), n)
+        for a, b in ((1, n - 1), (n // 2, n - 2), (0, n // 3 + 1)):      # n = 4: rows 1 and 3, rows 0 and 2
+            if a != b:
+                dup[a, :] = dup[b, :]; dup[:, a] = dup[:, b]; dup[a, a] = dup[b, b] = dup[a, b] = dup[b, a] = 0.0
+        cases["duplicate_rows_%d" % n] = dup
+    return cases
+
+
 NEWICK_NAMES = ["plain", "with space", "a:b", "it's", "(paren)", "semi;colon", "comma,", "[brack]", "tab\there", "Homo_sapiens.1"]
 
 

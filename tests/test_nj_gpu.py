@@ -69,6 +69,22 @@ def test_joins(U):
         assert np.array_equal(NC.tree_metric(NC.edges_of_joins(len(D), U.nj_join(D, device=-1)), len(D)), D), name
 
 
+def test_single_entry_across_the_route_boundary_and_on_ties(U):
+    """uc_nj_join_dev is a batch of one replicate: the workgroup minimum by shuffles and the per-replicate partials of the three launches per step
+    serve the main tree.  Equal to the host twin by bits, and to replicate 0 of a batch of two (the LDS kernel up to lds_rows, the same three
+    launches above)"""
+    L = U.nj_boot_geometry()["lds_rows"]
+    cases = NC.route_cases(L)
+    assert sorted({len(D) for D in cases.values()}) == [4, 5, L, L + 1, 257] and len(cases) == 15
+    for name, D in cases.items():
+        before = D.copy()
+        got = U.nj_join(D, device=-1)
+        NC.same_joins(got, U.nj_join(D), name)
+        pair = U.nj_join_batch(np.stack([D, D]), device=-1)
+        NC.same_joins(got, {k: v[0] for k, v in pair.items()}, name + ", replicate 0 of two")
+        assert np.array_equal(bits(D), bits(before)), name
+
+
 def test_refusals_come_before_the_device(U):
     refusals(U, -1)
     refusals(U, 1 << 20)      # an ordinal no machine has: UC_ERR_ARGS all the same, the device is not asked for

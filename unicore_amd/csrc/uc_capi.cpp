@@ -32,13 +32,7 @@ void require(const void *p, const char *what) {
 }
 
 // ---- the encoder's kernel-level entry points: one call = one device, buffers freed on every exit path
-void t5_use_device(int32_t device) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) fail(UC_ERR_DEVICE, "no HIP device available; the ProstT5 kernels have no CPU fallback");
-    if (device < 0) UC_HIP(hipGetDevice(&device));
-    if (device >= ndev) fail(UC_ERR_DEVICE, "device %d requested but only %d visible", device, ndev);
-    UC_HIP(hipSetDevice(device));
-}
+constexpr const char *T5_NO_FALLBACK = "the ProstT5 kernels have no CPU fallback";
 
 struct DevBufs {
     std::vector<void *> p;
@@ -748,7 +742,7 @@ int uc_t5_kernel_gemm(int32_t device, int32_t variant, int32_t epi, int32_t M, i
         if (!t5_gemm_admits(0, M, N, K)) fail(UC_ERR_ARGS, "t5 gemm: %d x %d x %d: needs M, N >= 1, N %% 4 == 0, K %% 64 == 0", M, N, K);
         const int v = variant < 0 ? t5_gemm_pick(M, N, K) : variant;
         if (!t5_gemm_admits(v, M, N, K)) fail(UC_ERR_ARGS, "t5 gemm: variant %d cannot run %d x %d x %d", v, M, N, K);
-        t5_use_device(device);
+        use_device(device, T5_NO_FALLBACK);
         DevBufs b;
         const size_t mn = (size_t)M * N, ob = mn * (epi == 2 ? 4 : 2);
         const uint16_t *dA = b.up(A, (size_t)M * K), *dW = b.up(W, (size_t)N * K);
@@ -763,7 +757,7 @@ int uc_t5_kernel_rmsnorm(int32_t device, int32_t T, int32_t D, float eps, const 
     return guard([&] {
         require(x, "x"); require(w, "w"); require(y, "y");
         if (T < 1 || D < 4 || D % 4) fail(UC_ERR_ARGS, "t5 rmsnorm: needs T >= 1 and D a positive multiple of 4 (T %d, D %d)", T, D);
-        t5_use_device(device);
+        use_device(device, T5_NO_FALLBACK);
         DevBufs b;
         const size_t n = (size_t)T * D;
         const float *dx = b.up(x, n), *dw = b.up(w, (size_t)D);
@@ -785,7 +779,7 @@ int uc_t5_kernel_attention(int32_t device, int32_t H, int32_t n_seqs, const int3
         if (bias_span > (1 << 24)) fail(UC_ERR_ARGS, "t5 attention: bias_span %d too large", bias_span);
         std::vector<T5AttnTile> tiles;
         t5_attn_tiles(off.data(), (size_t)n_seqs, tiles);
-        t5_use_device(device);
+        use_device(device, T5_NO_FALLBACK);
         DevBufs b;
         const size_t T = (size_t)off[(size_t)n_seqs], HD = (size_t)H * 128;
         const uint16_t *dq = b.up(qkv, T * 3 * HD);
@@ -811,7 +805,7 @@ int uc_t5_kernel_cnn_head(int32_t device, int32_t n_seqs, const int32_t *seq_len
         std::vector<int32_t> seq_of((size_t)T);
         for (int32_t s = 0; s < n_seqs; s++) std::fill(seq_of.begin() + off[(size_t)s], seq_of.begin() + off[(size_t)s + 1], s);
         const std::vector<float> w1r = t5_conv1_rearrange(w1, C1, D, KW);
-        t5_use_device(device);
+        use_device(device, T5_NO_FALLBACK);
         DevBufs b;
         const uint16_t *dx = b.up(x, (size_t)T * D);
         const float *dw1f = b.up(w1r.data(), w1r.size());

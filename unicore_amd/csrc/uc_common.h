@@ -2,10 +2,12 @@
 // Error model mirrors the reference: the only signal that crosses the boundary is a status code
 // (/root/reference/src/util/command.rs:10-14); the message is kept thread-local for uc_last_error().
 #pragma once
+#include <algorithm>
 #include <chrono>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <stdexcept>
 #include <string>
 
@@ -45,6 +47,12 @@ struct Timer {
     double seconds() const { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); }
 };
 inline const Timer g_library_loaded;      // started when the shared library's initialisers run: UC_TIMING stamps are relative to it
+
+// UC_TREE_BUDGET_BYTES: the bytes a call of the tree tools (star MSA, nj and its replicates) keeps on the device at a time; default 512 MiB, at least 1
+inline uint64_t tree_budget_bytes() {
+    const char *b = getenv("UC_TREE_BUDGET_BYTES");
+    return b ? std::max<uint64_t>(strtoull(b, nullptr, 10), 1) : 512ull << 20;
+}
 
 }  // namespace uc
 

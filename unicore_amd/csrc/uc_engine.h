@@ -138,6 +138,16 @@ inline dim3 grid_for(uint64_t n, uint32_t cap = 16384) {
     return dim3((uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(b, cap)));
 }
 
+// makes `device` (below 0: the one that is current) the calling thread's device.  A missing kernel path is an error, never a quiet fall-back:
+// no_fallback is the caller's sentence on what does not run without a device
+inline void use_device(int device, const char *no_fallback) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) fail(UC_ERR_DEVICE, "no HIP device available; %s", no_fallback);
+    if (device < 0) UC_HIP(hipGetDevice(&device));
+    if (device >= ndev) fail(UC_ERR_DEVICE, "device %d requested but only %d visible", device, ndev);
+    UC_HIP(hipSetDevice(device));
+}
+
 // one rocPRIM device call: size query (host only, launches nothing), temporary storage reserved with 256 B to spare, the run.
 // `call` is (void *tmp, size_t &bytes) -> hipError_t and holds the argument list, so that it is written once and its iterator types are deduced once
 template <class F>

@@ -183,13 +183,7 @@ __global__ void __launch_bounds__(256) msa_compact_kernel(uint64_t n_cells, uint
     }
 }
 
-void msa_use_device(int device) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) fail(UC_ERR_DEVICE, "no HIP device available; the device side of the star MSA has no CPU fallback (the host twins are separate entry points)");
-    if (device < 0) UC_HIP(hipGetDevice(&device));
-    if (device >= ndev) fail(UC_ERR_DEVICE, "device %d requested but only %d visible", device, ndev);
-    UC_HIP(hipSetDevice(device));
-}
+constexpr const char *MSA_NO_FALLBACK = "the device side of the star MSA has no CPU fallback (the host twins are separate entry points)";
 
 template <typename T>
 void up(DevBuf<T> &d, const T *src, size_t n) {
@@ -206,7 +200,7 @@ void launch_count(uint64_t n_cols, uint32_t ng, const uint64_t *d_grp, const uin
 }  // namespace
 
 void msa_center_device(int device, const MsaCenterArgs &a, const std::vector<uint64_t> &tri_off) {
-    msa_use_device(device);
+    use_device(device, MSA_NO_FALLBACK);
     const uint32_t ng = a.n_groups;
     if (!ng) return;
     const uint64_t n_rows = a.grp_off[ng], n_sc = tri_off[ng];
@@ -225,7 +219,7 @@ void msa_center_device(int device, const MsaCenterArgs &a, const std::vector<uin
 }
 
 void msa_star_device(int device, const MsaStarArgs &a, const MsaStarPlan &plan) {
-    msa_use_device(device);
+    use_device(device, MSA_NO_FALLBACK);
     const uint32_t ng = a.n_groups;
     if (a.need) a.need[0] = a.need[1] = 0;
     if (!ng) return;
@@ -294,7 +288,7 @@ void msa_star_device(int device, const MsaStarArgs &a, const MsaStarPlan &plan) 
 }
 
 void msa_filter_device(int device, const MsaFilterArgs &a, const MsaFilterPlan &plan) {
-    msa_use_device(device);
+    use_device(device, MSA_NO_FALLBACK);
     const uint32_t ng = a.n_groups;
     if (!ng) return;
     const uint64_t n_cols = plan.col_off[ng], n_cells = plan.cell_off[ng];

@@ -355,8 +355,7 @@ void tree_files(const char *db_prefix, const char *profile_dir, const char *out_
     for (uint32_t k = 0; k < ng; k++) std::copy(genes[live[k]].seq.begin(), genes[live[k]].seq.end(), row_seq.begin() + grp_off[k]);
     st.n_groups = ng_all; st.n_rows = n_rows;
     const bool on_host = env_is_one("UC_TREE_HOST"), dump = env_is_one("UC_TREE_DUMP");
-    uint64_t budget = 512ull << 20;
-    if (const char *b = getenv("UC_TREE_BUDGET_BYTES")) budget = std::max<uint64_t>(strtoull(b, nullptr, 10), 1);
+    const uint64_t budget = tree_budget_bytes();
     lap(0);
 
     // ---- UC-T/C: all pairs of every group, scores only, batched over whole groups under the byte budget; then the centres

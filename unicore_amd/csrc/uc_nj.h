@@ -1,9 +1,13 @@
 // uc_nj.h — the built-in tree builder `nj` of `unicore tree` / `unicore gene-tree` (rule UC-N): argument blocks, the checks both
-// sides share, the host twins (uc_nj_host.cpp) and the device side (uc_nj.hip).  Host and device take the same arrays and give the same outputs:
+// sides share, the host twins (uc_nj_host.cpp) and the device side (uc_nj.hip, uc_nj_join.hip).  Host and device take the same arrays and give the same outputs:
 // integers as integers, fp64 values by their bits.
 #pragma once
+#include <algorithm>
+#include <atomic>
 #include <cstdint>
+#include <functional>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "uc_common.h"
@@ -27,6 +31,23 @@ constexpr uint32_t NJ_TILE = 64;                               // rows of a pair
 constexpr uint32_t NJ_CHUNK = 256;                             // columns of both row tiles staged through LDS at a time
 constexpr double NJ_CAP = 5.0;                                 // the largest distance (UC-N/D)
 constexpr uint32_t NJ_NO_NODE = 0xffffffffu;                   // root_node[2] of a two-leaf tree
+constexpr const char *NJ_NO_FALLBACK = "the device side of nj has no CPU fallback (the host twins are separate entry points)";      // use_device's sentence
+
+// ---- what every validate of the host files starts with, and their thread pool
+inline void need(const void *p, const char *what) { if (!p) fail(UC_ERR_ARGS, "nj: %s must not be NULL", what); }
+inline void check_rows(uint32_t n) {
+    if (n < NJ_MIN_ROWS || n > NJ_MAX_ROWS) fail(UC_ERR_ARGS, "nj: %u rows; a tree needs %u .. %u", n, NJ_MIN_ROWS, NJ_MAX_ROWS);
+}
+// items 0 .. count - 1 over up to `threads` host threads (the caller is one of them); an item goes to the thread that draws its ticket
+inline void parallel_for(uint64_t count, uint32_t threads, const std::function<void(uint64_t)> &fn) {
+    std::atomic<uint64_t> next{0};
+    auto work = [&] { for (uint64_t i; (i = next.fetch_add(1)) < count;) fn(i); };
+    const uint32_t nt = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(threads, count));
+    std::vector<std::thread> pool;
+    for (uint32_t t = 1; t < nt; t++) pool.emplace_back(work);
+    work();
+    for (std::thread &t : pool) t.join();
+}
 
 // ---- UC-N/D: comp / diff of every row pair
 struct NjCountArgs {
@@ -145,8 +166,6 @@ struct NjJoinBatchArgs {
 void nj_join_batch_validate(const NjJoinBatchArgs &a);
 void nj_join_batch_host(const NjJoinBatchArgs &a);
 void nj_join_batch_device(int device, const NjJoinBatchArgs &a);
-// UC_TREE_BUDGET_BYTES, as nj_counts_device reads it (default 512 MiB, at least 1)
-uint64_t nj_tree_budget();
 
 // the bootstrap driver behind uc_tree_infer_boot.  rule == nullptr is that entry point, bit for bit and call for call; a rule (UC-N/T's lives in
 // uc_nj_transfer_host.cpp, which uc_nj_boot_host.cpp names nowhere: it links without it) takes the place of the split count: it sees the main tree once,

@@ -6,10 +6,8 @@
 #include <atomic>
 #include <cstdlib>
 #include <cstring>
-#include <functional>
 #include <memory>
 #include <string>
-#include <thread>
 #include <unordered_map>
 #include <vector>
 
@@ -20,32 +18,11 @@ namespace uc {
 
 namespace {
 
-void need(const void *p, const char *what) { if (!p) fail(UC_ERR_ARGS, "nj: %s must not be NULL", what); }
-void check_rows(uint32_t n) {
-    if (n < NJ_MIN_ROWS || n > NJ_MAX_ROWS) fail(UC_ERR_ARGS, "nj: %u rows; a tree needs %u .. %u", n, NJ_MIN_ROWS, NJ_MAX_ROWS);
-}
 void check_reps(uint64_t n_rep) {
     if (n_rep > NJ_BOOT_MAX_REPS) fail(UC_ERR_ARGS, "nj: %llu bootstrap replicates; 0 .. %u", (unsigned long long)n_rep, NJ_BOOT_MAX_REPS);
 }
 
-// items 0 .. count - 1 over up to `threads` host threads
-void parallel_for(uint64_t count, uint32_t threads, const std::function<void(uint64_t)> &fn) {
-    std::atomic<uint64_t> next{0};
-    auto work = [&] { for (uint64_t i; (i = next.fetch_add(1)) < count;) fn(i); };
-    const uint32_t nt = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(threads, count));
-    std::vector<std::thread> pool;
-    for (uint32_t t = 1; t < nt; t++) pool.emplace_back(work);
-    work();
-    for (std::thread &t : pool) t.join();
-}
-
 }  // namespace
-
-uint64_t nj_tree_budget() {
-    uint64_t budget = 512ull << 20;
-    if (const char *b = getenv("UC_TREE_BUDGET_BYTES")) budget = std::max<uint64_t>(strtoull(b, nullptr, 10), 1);
-    return budget;
-}
 
 void nj_boot_counts_validate(const NjBootCountArgs &a) {
     const NjCountArgs c{a.n, a.w, a.cells, a.threads, a.comp, a.diff};
@@ -200,7 +177,7 @@ void nj_tree_infer_boot(const char *msa_fasta, const char *out_nwk, const char *
         if (steps && rule) rule->begin(T, n_rep);
         // a batch holds the counts, D and the join records of its replicates
         const uint64_t per_rep = tri * 8 + nn * 8 + (uint64_t)steps * 24 + 36;
-        const uint32_t batch = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(n_rep, nj_tree_budget() / per_rep));
+        const uint32_t batch = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(n_rep, tree_budget_bytes() / per_rep));
         const size_t rec = std::max<size_t>((size_t)batch * steps, 1);
         std::vector<uint32_t> comp(batch * tri), diff(batch * tri), ja(rec), jb(rec), root((size_t)batch * 3);
         std::vector<double> D(batch * nn), la(rec), lb(rec), rlen((size_t)batch * 3);

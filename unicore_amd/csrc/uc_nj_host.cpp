@@ -2,12 +2,10 @@
 // the distance transform and the Newick writer (host only), the C entry points and the file level (uc_tree_infer).
 // The reference hands inference to iqtree, fasttree or raxml-ng (tree.rs:139-161, genetree.rs); `nj` is a builder of this project's own.
 // No FMA: uc_nj.h turns contraction off for this file too, and the host build names no -march, so a * b + c is two roundings here as on the device.
-#include <atomic>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <string>
-#include <thread>
 #include <unordered_set>
 #include <vector>
 
@@ -19,10 +17,6 @@ namespace uc {
 
 namespace {
 
-void need(const void *p, const char *what) { if (!p) fail(UC_ERR_ARGS, "nj: %s must not be NULL", what); }
-void check_rows(uint32_t n) {
-    if (n < NJ_MIN_ROWS || n > NJ_MAX_ROWS) fail(UC_ERR_ARGS, "nj: %u rows; a tree needs %u .. %u", n, NJ_MIN_ROWS, NJ_MAX_ROWS);
-}
 bool env_is_one(const char *name) { const char *v = getenv(name); return v && !strcmp(v, "1"); }
 
 constexpr uint64_t K7F = 0x7f7f7f7f7f7f7f7full, K80 = 0x8080808080808080ull;
@@ -49,28 +43,20 @@ void nj_counts_host(const NjCountArgs &a) {
 }
 
 void nj_count_codes(const uint64_t *code, uint64_t n, uint64_t words, uint32_t threads, uint32_t *comp_out, uint32_t *diff_out) {
-    std::atomic<uint64_t> next{0};
-    auto work = [&] {
-        for (uint64_t i; (i = next.fetch_add(1)) + 1 < n;) {
-            const uint64_t *x = code + i * words;
-            uint64_t k = i * n - i * (i + 1) / 2;
-            for (uint64_t j = i + 1; j < n; j++, k++) {
-                const uint64_t *y = code + j * words;
-                uint64_t comp = 0, diff = 0;
-                for (uint64_t t = 0; t < words; t++) {
-                    const uint64_t m = (x[t] + K7F) & (y[t] + K7F) & K80;
-                    comp += (uint64_t)__builtin_popcountll(m);
-                    diff += (uint64_t)__builtin_popcountll(m & ((x[t] ^ y[t]) + K7F));
-                }
-                comp_out[k] = (uint32_t)comp; diff_out[k] = (uint32_t)diff;
+    parallel_for(n ? n - 1 : 0, threads, [&](uint64_t i) {      // a ticket is a row and its pairs (i, j > i)
+        const uint64_t *x = code + i * words;
+        uint64_t k = i * n - i * (i + 1) / 2;
+        for (uint64_t j = i + 1; j < n; j++, k++) {
+            const uint64_t *y = code + j * words;
+            uint64_t comp = 0, diff = 0;
+            for (uint64_t t = 0; t < words; t++) {
+                const uint64_t m = (x[t] + K7F) & (y[t] + K7F) & K80;
+                comp += (uint64_t)__builtin_popcountll(m);
+                diff += (uint64_t)__builtin_popcountll(m & ((x[t] ^ y[t]) + K7F));
             }
+            comp_out[k] = (uint32_t)comp; diff_out[k] = (uint32_t)diff;
         }
-    };
-    const uint32_t nt = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(threads, n));
-    std::vector<std::thread> pool;
-    for (uint32_t t = 1; t < nt; t++) pool.emplace_back(work);
-    work();
-    for (std::thread &t : pool) t.join();
+    });
 }
 
 void nj_distances_host(const uint32_t *comp, const uint32_t *diff, uint32_t n, uint32_t model, double *D, uint64_t *counts) {

@@ -117,22 +117,14 @@ __global__ void __launch_bounds__(256) nj_transfer_kernel(const uint32_t *A, con
     }
 }
 
-void transfer_use_device(int device) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) fail(UC_ERR_DEVICE, "no HIP device available; the device side of nj has no CPU fallback (the host twins are separate entry points)");
-    if (device < 0) UC_HIP(hipGetDevice(&device));
-    if (device >= ndev) fail(UC_ERR_DEVICE, "device %d requested but only %d visible", device, ndev);
-    UC_HIP(hipSetDevice(device));
-}
-
 }  // namespace
 
 void nj_transfer_device(int device, const NjTransferArgs &a) {
     if (a.n <= 3 || !a.n_rep) return;
-    transfer_use_device(device);
+    use_device(device, NJ_NO_FALLBACK);
     const uint32_t n = a.n, steps = n - 3, words = (n + 31) / 32, n_chunks = (words + NJ_T_CHUNK - 1) / NJ_T_CHUNK, wp = n_chunks * NJ_T_CHUNK;
     const uint32_t sp = (steps + NJ_T_TILE - 1) / NJ_T_TILE * NJ_T_TILE, nt = sp / NJ_T_TILE;
-    const uint64_t stride = (uint64_t)wp * sp, per_tree = stride * 4 + (uint64_t)steps * 12, budget = nj_tree_budget();      // bit sets, join records and phi
+    const uint64_t stride = (uint64_t)wp * sp, per_tree = stride * 4 + (uint64_t)steps * 12, budget = tree_budget_bytes();      // bit sets, join records and phi
     const uint32_t batch = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint32_t>(a.n_rep, T_BATCH_MAX), (budget - std::min(budget, per_tree)) / per_tree));
     hipStream_t s = nullptr;
     DevBuf<uint32_t> d_bits, d_ja, d_jb, d_cap, d_phi;

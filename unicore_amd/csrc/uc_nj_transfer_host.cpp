@@ -3,12 +3,9 @@
 // bootstrap driver of uc_nj_boot_host.cpp behind uc_tree_infer_support.  Integers throughout: host, device and the Python reference agree bit for bit.
 // Builds without HIP, like uc_nj_host.cpp.
 #include <algorithm>
-#include <atomic>
 #include <cstdlib>
 #include <cstring>
-#include <functional>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "uc_files.h"
@@ -17,19 +14,6 @@
 namespace uc {
 
 namespace {
-
-void need(const void *p, const char *what) { if (!p) fail(UC_ERR_ARGS, "nj: %s must not be NULL", what); }
-
-// items 0 .. count - 1 over up to `threads` host threads
-void parallel_for(uint64_t count, uint32_t threads, const std::function<void(uint64_t)> &fn) {
-    std::atomic<uint64_t> next{0};
-    auto work = [&] { for (uint64_t i; (i = next.fetch_add(1)) < count;) fn(i); };
-    const uint32_t nt = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(threads, count));
-    std::vector<std::thread> pool;
-    for (uint32_t t = 1; t < nt; t++) pool.emplace_back(work);
-    work();
-    for (std::thread &t : pool) t.join();
-}
 
 // the joins must describe a forest inside the tree: a step joins two nodes that exist before it and hang from no earlier step.  size (nullable)
 // [n - 3] receives |L_s|; used and below are the caller's, so that a thousand replicates allocate once

@@ -111,14 +111,6 @@ __global__ void __launch_bounds__(256) pf_emit_kernel(uint32_t n_runs, const uin
     }
 }
 
-void pf_use_device(int device) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) fail(UC_ERR_DEVICE, "no HIP device available; the profile counter's device path has no CPU fallback (UC_PROFILE_HOST=1 selects the host counter)");
-    if (device < 0) UC_HIP(hipGetDevice(&device));
-    if (device >= ndev) fail(UC_ERR_DEVICE, "device %d requested but only %d visible", device, ndev);
-    UC_HIP(hipSetDevice(device));
-}
-
 struct PfEvents {      // stage boundaries on the null stream, only when the caller asked for times
     hipEvent_t e[6] = {};
     int n = 0;
@@ -131,7 +123,7 @@ struct PfEvents {      // stage boundaries on the null stream, only when the cal
 }  // namespace
 
 void profile_count_device(int device, const ProfileArgs &a, uint64_t n_pairs, float *ms) {
-    pf_use_device(device);
+    use_device(device, "the profile counter's device path has no CPU fallback (UC_PROFILE_HOST=1 selects the host counter)");
     const uint32_t ng = a.n_groups, ns = a.n_species;
     const uint64_t thr_s = (uint64_t)a.threshold * ns;
     if (ms) std::fill(ms, ms + 6, 0.f);
