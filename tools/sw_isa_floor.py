@@ -57,6 +57,7 @@ def classify(ins):
     if op == "v_pk_maximum3_f16": return "VALU: v_pk_maximum3_f16 — H = max3(x, e, f); E' = max3(e - ext, h - open, bias); row / column maxima"
     if op == "v_perm_b32": return "VALU: v_perm_b32 — byte r of the two profile words -> packed u16 score"
     if op == "v_add3_u32": return "VALU: v_add3_u32 — x' = diag' + (s + 128) - 128 on the packed register (biased domain)"
+    if op == "v_pk_mad_u16": return "VALU: v_pk_mad_u16 — first-column age of the maximum (its two v_pk_sub_u16 count with the clamped subtracts below)"
     if op in ("v_pk_add_u16", "v_pk_sub_u16"): return "VALU: v_pk_add/sub_u16 clamp — h - open; e - ext; f - ext (MODE 7 also x = max(Hdiag + s, 0))"
     if op in ("v_pk_max_u16", "v_pk_max_i16", "v_pk_min_u16"): return "VALU: v_pk_max_u16 — F', best, the bias for lane 0's diagonal"
     if op.startswith("v_add") or op.startswith("v_and") or op.startswith("v_lshl") or op.startswith("v_mad") or op.startswith("v_mul") or op.startswith("v_or") or op.startswith("v_lshr") or op.startswith("v_bfe") or op.startswith("v_sub"):
@@ -102,8 +103,9 @@ def main():
         found = ops["v_perm_b32"] + ops["v_add3_u32"] + ops["v_pk_add_u16"] + ops["v_pk_sub_u16"] + ops["v_pk_maximum3_f16"] + ops["v_pk_max_u16"]
         print("  source-level count of the recurrence (uc_sw_pk_impl.hpp:do_step): per row and step 1 perm + %d (x) + 1 max3 (h) + 3 sat-sub + 1 max3 (E') + 1 max (F') = %d, "
               "+ 0.5 column max3 + 0.5 row max3 (MODE 0 only) -> %d per run = %.3f per cell; the rest of the VALU count (%d = %.3f per cell) is per-STEP work "
-              "that R rows amortise: profile sums, LDS addressing, DPP shifts, first-column select, best" % (x_ops, 7 + x_ops, rec, rec / cells, valu - rec, (valu - rec) / cells))
-        print("  found in the run: %d perm, %d add3, %d pk_add, %d pk_sub, %d max3, %d pk_max = %d, i.e. %.2f per row and step (the per-step best / lane-0 bias maxima included)"
+              "that R rows amortise: profile sums, LDS addressing, DPP shifts, the target letters (G < 64: per trip 1 add, 2 min, 2 64-bit shift-adds, 1 move, "
+              "2 global_load_dword, and 1 v_perm_b32 per step), the first-column age (MODE 0 / 2: 2 v_pk_sub_u16 + 1 v_pk_mad_u16 per step), best" % (x_ops, 7 + x_ops, rec, rec / cells, valu - rec, (valu - rec) / cells))
+        print("  found in the run: %d perm, %d add3, %d pk_add, %d pk_sub, %d max3, %d pk_max = %d, i.e. %.2f per row and step (the per-step best / lane-0 bias maxima, the letters' perm and the age's two subtracts included)"
               % (ops["v_perm_b32"], ops["v_add3_u32"], ops["v_pk_add_u16"], ops["v_pk_sub_u16"], ops["v_pk_maximum3_f16"], ops["v_pk_max_u16"], found, found / (R * steps)))
         print()
 

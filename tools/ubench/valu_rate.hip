@@ -32,6 +32,8 @@ __global__ void __launch_bounds__(256) k(uint32_t *out, int iters, uint32_t seed
                 if (KIND == 8) a[i] = (a[i] << 5) | (b & 31);                             // v_lshl_or_b32
                 if (KIND == 10) asm volatile("v_add3_u32 %0, %1, %2, %3" : "=v"(a[i]) : "v"(a[i]), "v"(bv), "s"(0xFF7FFF80u));   // v_add3_u32, third operand an SGPR (the biased x')
                 if (KIND == 11) asm volatile("v_pk_maximum3_f16 %0, %1, %2, %3" : "=v"(a[i]) : "v"(a[i]), "v"(bv), "s"(0x00800080u)); // max3 with an SGPR operand (the biased E')
+                if (KIND == 12) asm volatile("v_pk_mad_u16 %0, %1, %2, %3" : "=v"(a[i]) : "v"(a[i]), "v"(bv), "v"(bv));   // per half a * b + b, VGPR operands (the first-column age)
+                if (KIND == 13) asm volatile("v_pk_sub_u16 %0, %1, %2" : "=v"(a[i]) : "v"(a[i]), "v"(bv));               // its yardstick: the same form without the clamp
             }
     }
     uint32_t s = 0;
@@ -59,5 +61,6 @@ int main() {
     run<9>("v_add+v_xor", d); run<0>("v_max_i32+v_xor", d); run<7>("v_max3_i32+v_xor", d); run<6>("v_sub_u32 clamp", d); run<8>("v_lshl_or_b32", d); run<5>("v_dot4_i32_i8", d);
     run<1>("v_pk_max_u16+v_xor", d); run<2>("v_pk_sub_u16 clamp", d); run<3>("v_pk_add_u16 clamp", d); run<4>("v_perm_b32", d);
     run<10>("v_add3_u32 v,v,s", d); run<11>("v_pk_maximum3_f16 v,v,s", d);
+    run<13>("v_pk_sub_u16 v,v", d); run<12>("v_pk_mad_u16 v,v,v", d);
     return 0;
 }

@@ -29,6 +29,15 @@
 //    local alignment); x = sat_sub(sat_add(Hdiag, s + 128), 128) = max(Hdiag + s, 0); H = max3(x, e, f).
 //  * profile bytes are (S3+64) and (SA+64) so the packed byte sum is s+128 (PAD = 0 => s = -128); one
 //    v_perm_b32 per row interleaves byte r of target A's and target B's word into two zero-extended u16.
+//  * first column of the maximum (MODE 0 / 2): ONE packed register age2 holds, per half, the steps since this lane's column maximum last exceeded its
+//    running best.  Per step d = sat_sub(colmax, best) is non-zero exactly where the maximum rose (strictly: the FIRST column), nm = sat_sub(1, d) is
+//    1 where it did not, and age2 = age2 * nm + nm (v_pk_mad_u16, mod 2^16, the rate of v_pk_sub_u16: valu_rate.hip) counts on or starts again at 0: three
+//    packed instructions where two int32 column registers took an unpacking compare and a select each (-2 per step, one register less).  finish_slot
+//    rebuilds the column as (nst - 1 - g) - age mod 2^16: exact, a column is below 65,535, even where nst or the age wrapped
+//    (tests/test_sw_firstcol_model.py).  Integer operations only: a NaN pattern in colmax needs no special case.
+//  * target letters, G < 64, every MODE but 7: one 32-bit load per target and 2-step trip brings the letters of two columns from the interleaved stream
+//    a.db.lt (see LT2 in the kernel); one v_perm_b32 per step packs A's and B's half into c1.  -3 VALU and -1 VMEM instruction per step against one
+//    16-bit load per target and step.  G = 64 reads its letters through the scalar cache, MODE 7 keeps the 16-bit loads.
 //  * end tracking: per lane the running maximum gives (score, first column) per half; per-row maxima
 //    (rowbest) identify the row: if exactly one row of the alignment ever reaches the optimum it must be the
 //    row of the first column too, so (qEnd, tEnd) is exact.  Otherwise — or if a value came within 256 of the
@@ -87,6 +96,12 @@ __device__ __forceinline__ uint32_t pk_max_s(uint32_t a, uint32_t c) {
 __device__ __forceinline__ uint32_t add3_s(uint32_t a, uint32_t b, uint32_t c) {   // a plain 32-bit sum of three
     uint32_t r;
     asm("v_add3_u32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "s"(c));
+    return r;
+}
+// per half a * b + c mod 2^16 (the first-column age of MODE 0: do_step)
+__device__ __forceinline__ uint32_t pk_mad(uint32_t a, uint32_t b, uint32_t c) {
+    uint32_t r;
+    asm("v_pk_mad_u16 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
     return r;
 }
 constexpr uint32_t SW_PK_BIAS = 128u * 0x10001u;       // H' = H + 128, E' = E + 128 in either half (every MODE but 7)
@@ -231,6 +246,9 @@ __global__ void __launch_bounds__(NW * 64) sw_pk_kernel(const SwArgs a) {
     // KNOWN: colA / colB hold the lane's whole first-answer state in one register, so that the second key below costs no occupancy step:
     // -1 = no optimal cell yet, else first optimal column << 6 | its first row (of this lane's R) << 1 | this lane saw the optimum in more than one of its rows
     int colA = -1, colB = -1;
+    // MODE 0 / 2 keep the first column of the maximum on ONE packed register instead: per half the steps since this lane's column maximum last exceeded
+    // its running best (mod 2^16); finish_slot turns it back into the column
+    [[maybe_unused]] uint32_t age2 = 0;
     [[maybe_unused]] uint32_t knownA = 0, knownB = 0;
     // KNOWN: the other tie-break order over this lane's optimal cells, (first optimal row, then first column) = row << 16 | col: the answer of the
     // transposed DP, i.e. of the mirror (t,q) of a mutual hit.  Only touched inside the event branch.
@@ -246,10 +264,29 @@ __global__ void __launch_bounds__(NW * 64) sw_pk_kernel(const SwArgs a) {
     struct RawLetters { uint32_t a3, aa, b3, ba; } r2 = {0, 0, 0, 0};   // G < 64: a3 / b3 hold the whole 16-bit letter pair
     uint32_t nA3[RW], nAa[RW], nB3[RW], nBa[RW];
     // G < 64: both letters of a residue come from the interleaved stream a.db.lt (3Di | AA << 8, PAD pairs between the
-    // sequences): one 16-bit load per target and step, the index clamped onto the PAD entry behind (REVT: before) the
-    // sequence, so neither a second byte load nor a "past the end" select is needed.  ltA / ltB point at element 0
-    // (REVT: at the PAD entry before it, so that the index stays unsigned).
+    // sequences): MODE 7 one 16-bit load per target and step, the index clamped onto the PAD entry behind the
+    // sequence, so neither a second byte load nor a "past the end" select is needed.  ltA / ltB point at element 0.
     [[maybe_unused]] const uint16_t *ltA = nullptr, *ltB = nullptr;
+    // G < 64, every MODE but 7 (LT2): ONE 32-bit load per target and 2-step trip brings the letters of two columns.  A sequence starts at a multiple of 16
+    // entries and at least 16 PAD entries follow it (Engine::plan_db_layout; 16 more stand in front of the first), so:
+    //  * forward targets: word (c, c + 1), c even, is ltA[min(c, clA)], clA = (tlen + 1) & ~1: even, hence 4-byte aligned; the clamp lands on
+    //    (last, PAD) or (PAD, PAD), never on the sequence behind.  The low half is the first column of the two.
+    //  * REVT: column c is element tlen - 1 - c.  ltA points two entries in front of the sequence and the word is ltA[max(tlen - c, 0)]: (c + 1, c) in
+    //    its (low, high) half, (PAD, PAD) from the entries in front once c >= tlen, never the sequence in front.  An odd tlen makes these words
+    //    2-byte aligned only (one global_load_dword all the same).
+    // wA / wB hold the word whose columns enter c1 in this trip; the ODD step issues the next one right after it took the second half, one step before
+    // its first use - the distance the 16-bit loads had.
+    constexpr bool LT2 = G != 64 && !TBB;
+    constexpr uint32_t LT2_FIRST = REVT ? 0x07060302u : 0x05040100u, LT2_SECOND = REVT ? 0x05040100u : 0x07060302u;   // v_perm_b32: [A's half | B's half << 16]
+    [[maybe_unused]] uint32_t wA = 0, wB = 0;
+    [[maybe_unused]] int clA = 0, clB = 0;
+    typedef uint32_t __attribute__((aligned(2))) lt2_word;
+    auto issue_words = [&](int c) __attribute__((always_inline)) {
+        const uint32_t ia = REVT ? (uint32_t)max(clA - c, 0) : (uint32_t)min(c, clA);
+        const uint32_t ib = REVT ? (uint32_t)max(clB - c, 0) : (uint32_t)min(c, clB);
+        if constexpr (REVT) { wA = *(const lt2_word *)(ltA + ia); wB = *(const lt2_word *)(ltB + ib); }
+        else { wA = *(const uint32_t *)(ltA + ia); wB = *(const uint32_t *)(ltB + ib); }
+    };
 
     // letters of both targets travel as one dword: [c3A | caA << 8 | c3B << 16 | caB << 24].  The loads are
     // branch-free (clamped index, every lane of the group reads the same address) and are only combined a full
@@ -266,9 +303,8 @@ __global__ void __launch_bounds__(NW * 64) sw_pk_kernel(const SwArgs a) {
                 return (*w >> (8u * (p & 3u))) & 0xffu;
             };
             r.a3 = ld(a.db.s3, pa); r.aa = ld(a.db.sa, pa); r.b3 = ld(a.db.s3, pb_); r.ba = ld(a.db.sa, pb_);
-        } else {
-            const uint32_t ia = REVT ? (uint32_t)max(tlenA - st, 0) : (uint32_t)min(st, tlenA);
-            const uint32_t ib = REVT ? (uint32_t)max(tlenB - st, 0) : (uint32_t)min(st, tlenB);
+        } else {   // MODE 7 only (LT2 otherwise)
+            const uint32_t ia = (uint32_t)min(st, tlenA), ib = (uint32_t)min(st, tlenB);
             r.a3 = ltA[ia]; r.b3 = ltB[ib];
             r.aa = 0; r.ba = 0;
         }
@@ -363,10 +399,16 @@ __global__ void __launch_bounds__(NW * 64) sw_pk_kernel(const SwArgs a) {
                 mskA[k] = ma; mskB[k] = mb;
             }
         }
-        if constexpr (G != 64) {
-            ltA = a.db.lt + toffA - (REVT ? 1 : 0);
+        if constexpr (LT2) {
+            ltA = a.db.lt + toffA - (REVT ? 2 : 0);
+            // no second pair (tlenB = 0): every word is the two PAD entries in front of A's first residue
+            ltB = vB ? a.db.lt + toffB - (REVT ? 2 : 0) : a.db.lt + toffA - 2;
+            clA = REVT ? tlenA : (tlenA + 1) & ~1;
+            clB = REVT ? tlenB : (tlenB + 1) & ~1;
+        } else if constexpr (G != 64) {
+            ltA = a.db.lt + toffA;
             // no second pair: every index lands on a PAD entry (the one before A's first residue)
-            ltB = vB ? a.db.lt + toffB - (REVT ? 1 : 0) : a.db.lt + toffA - 1;
+            ltB = vB ? a.db.lt + toffB : a.db.lt + toffA - 1;
         }
 #pragma unroll
         for (int r = 0; r < R; r++) { H[r] = HB; E[r] = HB; }
@@ -379,9 +421,18 @@ __global__ void __launch_bounds__(NW * 64) sw_pk_kernel(const SwArgs a) {
             knownB = vB ? (uint32_t)a.pscore[gB] + 128u : 128u;
             key2A = 0x7fffffff; key2B = 0x7fffffff;
         }
-        best = HB; colA = -1; colB = -1; Hlast = HB; prevHup = HB; fout = 0;   // f enters as 0 = true -128: it never wins against e' >= 128
+        best = HB; colA = -1; colB = -1; age2 = 0; Hlast = HB; prevHup = HB; fout = 0;   // f enters as 0 = true -128: it never wins against e' >= 128
         lst = 0;
         nst = (max(tlenA, tlenB) + G) & ~1;      // Lt + G - 1 steps, rounded up to the 2-step loop trip
+        if constexpr (LT2) {   // columns 0 and 1 from the first word, the word of columns 2 and 3 in flight
+            issue_words(0);
+            const uint32_t c0 = __builtin_amdgcn_perm(wB, wA, LT2_FIRST);
+            c1 = __builtin_amdgcn_perm(wB, wA, LT2_SECOND);
+            issue_words(2);
+            cin = (uint32_t)shift_from_prev_lane<G>((int)(SW_PADPACK * 0x10001u), (int)c0, g);
+            fetch_profile();
+            return;
+        }
         c1 = pack_letters(issue_letters(1), 1);
         r2 = issue_letters(2);
         if constexpr (G == 64) {   // keep the letter pipeline in SGPRs across the loop back edge
@@ -403,8 +454,13 @@ __global__ void __launch_bounds__(NW * 64) sw_pk_kernel(const SwArgs a) {
             if constexpr (MASK) { sA[k] &= mskA[k]; sB[k] &= mskB[k]; }
         }
         cin = (uint32_t)shift_from_prev_lane<G>((int)cin, (int)c1, g);
-        c1 = pack_letters(r2, st + 2);
-        r2 = issue_letters(st + 3);
+        if constexpr (LT2) {   // column st + 2: the first half of the trip's word in the even step, the second in the odd one, which then issues the next word
+            c1 = __builtin_amdgcn_perm(wB, wA, ODD ? LT2_SECOND : LT2_FIRST);
+            if (ODD) issue_words(st + 3);
+        } else {
+            c1 = pack_letters(r2, st + 2);
+            r2 = issue_letters(st + 3);
+        }
         fetch_profile();
         const uint32_t Hup = (uint32_t)shift_from_prev_lane_zero<G>((int)Hlast, g);
         uint32_t f = (uint32_t)shift_from_prev_lane_zero<G>((int)fout, g);
@@ -471,9 +527,11 @@ __global__ void __launch_bounds__(NW * 64) sw_pk_kernel(const SwArgs a) {
             if (vB && st >= tsaB && st <= tsbB) put(dB, wb);
         }
         if constexpr (TRACK && !KNOWN) {
-            const uint32_t cmA = colmax & 0xffffu, cmB = colmax >> 16;
-            colA = cmA > (best & 0xffffu) ? st - g : colA;
-            colB = cmB > (best >> 16) ? st - g : colB;
+            // strictly above best = the FIRST column of the maximum: d != 0 there, nm = 1 - min(d, 1), age = improved ? 0 : age + 1 in one multiply-add.
+            // Integer operations throughout: a NaN pattern in colmax (an overflowed pair, re-run anyway) is a large number like any other.
+            const uint32_t d = pk_sub_sat(colmax, best);
+            const uint32_t nm = pk_sub_sat(0x00010001u, d);
+            age2 = pk_mad(age2, nm, nm);
         }
         if constexpr (KNOWN) {
             // every column of this lane that holds the optimum is an event (a handful per alignment: wave-level branch);
@@ -543,7 +601,11 @@ __global__ void __launch_bounds__(NW * 64) sw_pk_kernel(const SwArgs a) {
 #pragma unroll
         for (int half = 0; half < 2; half++) {
             int score = half ? (int)(best >> 16) : (int)(best & 0xffffu);
-            int col = half ? colB : colA;
+            // the last step is nst - 1 and a lane's column in step st is st - g: the column of the last improvement is (nst - 1 - g) - age.  Exact mod 2^16
+            // (a column is < 65,535) even where nst or the age wrapped.  A lane that never improved holds no column: its score is the bias, and it can
+            // tie only where every lane's is, i.e. where te = -1 goes out.
+            int col = -1;   // (MODE 1 reports no column)
+            if constexpr (TRACK) col = (int)(((uint32_t)(nst - 1 - g) - (half ? age2 >> 16 : age2)) & 0xffffu);
 #pragma unroll
             for (int m = 1; m < G; m <<= 1) {
                 const int os = __shfl_xor(score, m, 64), oc = __shfl_xor(col, m, 64);
