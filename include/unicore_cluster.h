@@ -374,6 +374,59 @@ typedef struct uc_tree_stats {
 int uc_tree(const char *db_prefix, const char *profile_dir, const char *out_dir, uint32_t threshold, const char *aligner_options, const uc_opts *o,
             uc_tree_stats *stats_out);
 
+/* ---- `unicore tree -a profile` (rule UC-T/P): profile refinement of the star MSA.  One round realigns every row of a group against the
+ * leave-one-out column profile of the group's current MSA (one local affine DP over the full matrix, one walk), lays the rows out again by UC-T/L with a
+ * virtual centre of the MSA's width and drops the columns without an amino acid.  Host functions need no device; the _dev siblings run the HIP kernels of
+ * uc_msa_profile.hip and give the same bytes.  Track 0 is the amino acids, track 1 the 3Di letters, as in uc_msa_star.
+ * uc_msa_profile_align: width[g] and cells0 / cells1 are the current MSA as uc_msa_star lays it out (group g: m_g x width[g] bytes); a cell is `-` or an
+ *   ASCII letter (coded as the database loader codes it: ACDEFGHIKLMNPQRSTVWY -> 0 .. 19, any other letter 20), and both tracks hold their gaps in the
+ *   same cells.  res_off / res0 / res1: the full rows as letters.  S3, SA: 21 x 21, [column letter][row letter].  Per row: aligned (score > 0), score,
+ *   the first cell (qs = column, ts = residue), the end cell (qe, te; smallest te, then smallest qe) and the runs `length << 2 | op` (0 M, 1 I = column
+ *   only, 2 D = residue only) at run_off[r] .. run_off[r + 1].  need_out (nullable) receives the run count; runs_capacity below it is UC_ERR_ARGS with
+ *   run_off filled in.  width[g] + L_r words per row always suffice.  A group of one row is left alone: no DP runs, its row reports
+ *   aligned = 0 without runs, and uc_msa_profile_layout keeps such a group's cells as they are.
+ *   threads: host threads of the twin (0 = 1); the answer does not depend on it.
+ * UC_ERR_ARGS: gap_open < gap_ext, gap_ext < 0 or gap_open > 2^20 (scores stay in 32 bits), a cell that is neither a letter nor `-`, tracks that
+ *   disagree on a gap, width[g] * L_r >= 2^31, ceil(width[g] / chunk) * (L_r + chunk - 1) * chunk >= 2^31 (the decision bytes of the row as the kernel
+ *   lays them out; both sides refuse it), more than 65534 rows in a group, malformed offsets.
+ * uc_msa_profile_layout: the new MSA from the rows' alignments: ins[s], s = 0 .. width[g], = the longest D run after s columns, col[c] = c + sum of
+ *   ins[0 .. c], M writes at col[c], D runs left-justified into their slot's block, I writes nothing, an unaligned row is all gaps; then every column
+ *   without a residue on track 0 is dropped.  new_width [n_groups]; need_out[0] = cell bytes per track.  A group of one row keeps cells_in's row.
+ * uc_msa_profile_geometry: chunk = columns of the MSA a wave stages in LDS at a time (wider tasks are served chunk after chunk: there is no cap on the
+ *   width, *cap receives 0); task_bytes_per_cell = bytes of the decision buffer per DP cell. */
+int uc_msa_profile_align(uint32_t n_groups, const uint64_t *grp_off, const uint32_t *width, const uint8_t *cells0, const uint8_t *cells1, const uint64_t *res_off,
+                         const uint8_t *res0, const uint8_t *res1, const int8_t *S3, const int8_t *SA, int32_t gap_open, int32_t gap_ext, uint8_t *aligned,
+                         int32_t *score, int32_t *qs, int32_t *ts, int32_t *qe, int32_t *te, uint64_t *run_off, uint32_t *runs, uint64_t runs_capacity,
+                         uint64_t *need_out, uint32_t threads);
+int uc_msa_profile_align_dev(int32_t device, uint32_t n_groups, const uint64_t *grp_off, const uint32_t *width, const uint8_t *cells0, const uint8_t *cells1,
+                             const uint64_t *res_off, const uint8_t *res0, const uint8_t *res1, const int8_t *S3, const int8_t *SA, int32_t gap_open,
+                             int32_t gap_ext, uint8_t *aligned, int32_t *score, int32_t *qs, int32_t *ts, int32_t *qe, int32_t *te, uint64_t *run_off,
+                             uint32_t *runs, uint64_t runs_capacity, uint64_t *need_out);
+int uc_msa_profile_layout(uint32_t n_groups, const uint64_t *grp_off, const uint32_t *width, const uint8_t *cells0_in, const uint8_t *cells1_in,
+                          const uint64_t *res_off, const uint8_t *res0, const uint8_t *res1, const uint8_t *aligned, const int32_t *qs, const int32_t *ts,
+                          const uint64_t *run_off, const uint32_t *runs, uint32_t *new_width, uint8_t *cells0, uint8_t *cells1, uint64_t cells_capacity,
+                          uint64_t *need_out);
+int uc_msa_profile_layout_dev(int32_t device, uint32_t n_groups, const uint64_t *grp_off, const uint32_t *width, const uint8_t *cells0_in,
+                              const uint8_t *cells1_in, const uint64_t *res_off, const uint8_t *res0, const uint8_t *res1, const uint8_t *aligned, const int32_t *qs,
+                              const int32_t *ts, const uint64_t *run_off, const uint32_t *runs, uint32_t *new_width, uint8_t *cells0, uint8_t *cells1,
+                              uint64_t cells_capacity, uint64_t *need_out);
+int uc_msa_profile_geometry(uint32_t *chunk, uint32_t *cap, uint32_t *task_bytes_per_cell);
+/* == `unicore tree --no-inference -a profile --refine-iters refine_iters`: uc_tree, with refine_iters (0 .. UC_TREE_MAX_REFINE) rounds of UC-T/P between
+ * the star MSA and the filter.  refine_iters = 0 writes exactly what uc_tree writes.  The rounds take the matrices and gaps of aligner_options, run on
+ * o->device (UC_TREE_HOST=1: the host twins) in batches of tasks under UC_TREE_BUDGET_BYTES (no result depends on it); UC_TREE_DUMP=1 also writes
+ * fasta/<gene>/refine.tsv (round, row, score, qs, ts). */
+#define UC_TREE_MAX_REFINE 8
+#define UC_TREE_REFINED_NPHASE 3
+typedef struct uc_tree_refined_stats {
+    uc_tree_stats tree;                  /* of the whole call; n_rows_unaligned counts the rows that are all gaps in the final MSA */
+    uint64_t n_rounds, n_tasks, n_cells; /* rounds run; DPs (rows of groups with two rows or more, summed over the rounds); their cells, width x length */
+    uint64_t n_rows_became_aligned, n_rows_became_unaligned;      /* against the MSA the round started from, summed over the rounds */
+    uint64_t width_before[UC_TREE_MAX_REFINE], width_after[UC_TREE_MAX_REFINE];      /* per round, summed over the genes */
+    double seconds[UC_TREE_REFINED_NPHASE];      /* host wall: [0] profile DP + walk, [1] layout + compaction, [2] both */
+} uc_tree_refined_stats;
+int uc_tree_refined(const char *db_prefix, const char *profile_dir, const char *out_dir, uint32_t threshold, const char *aligner_options, uint32_t refine_iters,
+                    const uc_opts *o, uc_tree_refined_stats *stats_out);
+
 /* ---- the built-in tree builder `nj` (rule UC-N): pairwise protein distances over an aligned FASTA and neighbour joining (Saitou-Nei
  * with the Studier-Keppler criterion), the inference step of `unicore tree -t nj` and `unicore gene-tree -t nj` (tree.rs:139-161 and genetree.rs hand it
  * to an external program).  Every output is defined bit for bit; every host function (no device needed) has a _dev sibling that runs the HIP kernels

@@ -49,6 +49,15 @@ class UcTreeStats(C.Structure):
 
 
 TREE_PHASES = ("read", "pair_scores", "centres", "centre_alignments", "layout_render_filter", "write", "total")
+TREE_MAX_REFINE = 8      # == UC_TREE_MAX_REFINE
+
+
+class UcTreeRefinedStats(C.Structure):
+    _fields_ = [("tree", UcTreeStats)] + [(n, C.c_uint64) for n in ("n_rounds", "n_tasks", "n_cells", "n_rows_became_aligned", "n_rows_became_unaligned")] + [
+        ("width_before", C.c_uint64 * TREE_MAX_REFINE), ("width_after", C.c_uint64 * TREE_MAX_REFINE), ("seconds", C.c_double * 3)]
+
+
+TREE_REFINED_PHASES = ("profile_dp_walk", "layout_compaction", "total")
 
 
 class UcNjStats(C.Structure):
@@ -93,6 +102,7 @@ SYMBOLS = (
     "uc_cluster_graph", "uc_engine_cluster_graph", "uc_engine_reassign", "uc_engine_td_onchip", "uc_engine_sw_task_queries", "uc_engine_linclust_pairs",
     "uc_profile_count", "uc_profile_count_dev", "uc_profile",
     "uc_msa_center", "uc_msa_center_dev", "uc_msa_star", "uc_msa_star_dev", "uc_msa_filter", "uc_msa_filter_dev", "uc_tree",
+    "uc_msa_profile_align", "uc_msa_profile_align_dev", "uc_msa_profile_layout", "uc_msa_profile_layout_dev", "uc_msa_profile_geometry", "uc_tree_refined",
     "uc_nj_counts", "uc_nj_counts_dev", "uc_nj_distances", "uc_nj_join", "uc_nj_join_dev", "uc_nj_newick", "uc_nj_geometry", "uc_tree_infer",
     "uc_nj_boot_columns", "uc_nj_boot_counts", "uc_nj_boot_counts_dev", "uc_nj_join_batch", "uc_nj_join_batch_dev", "uc_nj_support", "uc_nj_newick_support",
     "uc_nj_boot_geometry", "uc_tree_infer_boot",
@@ -184,6 +194,13 @@ def lib():
     L.uc_msa_filter.argtypes = [u32, vp, vp, vp, u32, vp, vp, vp]
     L.uc_msa_filter_dev.argtypes = [i32] + L.uc_msa_filter.argtypes
     L.uc_tree.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, u32, C.c_char_p, C.POINTER(UcOpts), C.POINTER(UcTreeStats)]
+    L.uc_msa_profile_align.argtypes = [u32] + [vp] * 9 + [i32, i32] + [vp] * 8 + [u64, vp]
+    L.uc_msa_profile_align_dev.argtypes = [i32] + L.uc_msa_profile_align.argtypes
+    L.uc_msa_profile_align.argtypes = L.uc_msa_profile_align.argtypes + [u32]
+    L.uc_msa_profile_layout.argtypes = [u32] + [vp] * 15 + [u64, vp]
+    L.uc_msa_profile_layout_dev.argtypes = [i32] + L.uc_msa_profile_layout.argtypes
+    L.uc_msa_profile_geometry.argtypes = [vp, vp, vp]
+    L.uc_tree_refined.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, u32, C.c_char_p, u32, C.POINTER(UcOpts), C.POINTER(UcTreeRefinedStats)]
     L.uc_nj_counts.argtypes = [u32, u64, vp, u32, vp, vp]
     L.uc_nj_counts_dev.argtypes = [i32] + L.uc_nj_counts.argtypes
     L.uc_nj_distances.argtypes = [vp, vp, u32, u32, vp]
@@ -436,15 +453,99 @@ def msa_filter(grp_off, width, cells, threshold, device=None):
     return {"keep": keep[:ncols], "fwidth": fwidth[:ng], "fcells": fcells[:nf].copy()}
 
 
-def tree(db, profile_dir, out_dir, threshold=50, aligner_options="", verbosity=1, device=-1):
+def msa_profile_geometry():
+    """The profile DP kernel's geometry (uc_msa_profile_geometry): {"chunk": columns of the MSA a wave holds at a time, "cap": the widest MSA the kernel
+    serves (0: no cap, wider tasks run chunk after chunk), "task_bytes_per_cell": bytes of the decision buffer per DP cell}."""
+    a, b, c = C.c_uint32(), C.c_uint32(), C.c_uint32()
+    _check(lib().uc_msa_profile_geometry(C.byref(a), C.byref(b), C.byref(c)))
+    return {"chunk": a.value, "cap": b.value, "task_bytes_per_cell": c.value}
+
+
+def _profile_shape(grp_off, width, cells, res_off, res):
+    go, w, ro = np.ascontiguousarray(grp_off, np.uint64), np.ascontiguousarray(width, np.uint32), np.ascontiguousarray(res_off, np.uint64)
+    ce, tr = [np.ascontiguousarray(c, np.uint8) for c in cells], [np.ascontiguousarray(t, np.uint8) for t in res]
+    ng = len(go) - 1
+    if ng < 0 or len(w) != ng or len(ce) != 2 or len(tr) != 2:
+        raise ValueError("grp_off needs n_groups + 1 entries, width n_groups, cells and res two tracks (amino acids, 3Di)")
+    n_rows = int(go[-1]) if ng > 0 else 0
+    m = np.diff(go.astype(np.int64))
+    if len(ro) != n_rows + 1:
+        raise ValueError("res_off needs n_rows + 1 entries")
+    ok = ng == 0 or ((m > 0).all() and int(go[0]) == 0)      # the call refuses the rest itself
+    if ok and (any(len(c) != int((m * w.astype(np.int64)).sum()) for c in ce) or (n_rows and any(len(t) < int(ro[-1]) for t in tr))):
+        raise ValueError("cells / res do not hold what grp_off, width and res_off describe")
+    return go, w, ro, ce, tr, ng, n_rows, m, ok
+
+
+def msa_profile_align(grp_off, width, cells, res_off, res, S3, SA, gap_open, gap_ext, device=None, threads=1):
+    """UC-T/P, the alignment (uc_msa_profile_align / _dev): every row of every group against the leave-one-out profile of the group's MSA.  cells and
+    res: [amino acids, 3Di] as bytes (cells as msa_star lays them out), S3 / SA: 21 x 21 int8, [column letter][row letter].  Returns a dict: aligned,
+    score, qs, ts, qe, te per row, run_off [n_rows + 1], runs (length << 2 | op; 0 M, 1 I = column only, 2 D = residue only).  device as in msa_center; threads: the host twin's."""
+    go, w, ro, ce, tr, ng, n_rows, m, ok = _profile_shape(grp_off, width, cells, res_off, res)
+    s3, sa = np.ascontiguousarray(S3, np.int8).reshape(-1), np.ascontiguousarray(SA, np.int8).reshape(-1)
+    if len(s3) != 441 or len(sa) != 441:
+        raise ValueError("S3 and SA are 21 x 21")
+    cap = 0
+    if ok and ng:
+        ln = np.diff(ro.astype(np.int64))
+        cap = int(np.maximum(ln, 0).sum() + (m * w.astype(np.int64)).sum())
+    al = np.zeros(max(n_rows, 1), np.uint8)
+    sc, qs, ts, qe, te = (np.zeros(max(n_rows, 1), np.int32) for _ in range(5))
+    uo, runs, need = np.zeros(n_rows + 1, np.uint64), np.zeros(max(cap, 1), np.uint32), np.zeros(1, np.uint64)
+    args = [ng, go.ctypes.data, _ptr(w), _ptr(ce[0]), _ptr(ce[1]), ro.ctypes.data, _ptr(tr[0]), _ptr(tr[1]), s3.ctypes.data, sa.ctypes.data, gap_open, gap_ext,
+            al.ctypes.data, sc.ctypes.data, qs.ctypes.data, ts.ctypes.data, qe.ctypes.data, te.ctypes.data, uo.ctypes.data, runs.ctypes.data, cap, need.ctypes.data]
+    _check(lib().uc_msa_profile_align(*args, threads) if device is None else lib().uc_msa_profile_align_dev(device, *args))
+    return {"aligned": al[:n_rows], "score": sc[:n_rows], "qs": qs[:n_rows], "ts": ts[:n_rows], "qe": qe[:n_rows], "te": te[:n_rows], "run_off": uo,
+            "runs": runs[: int(need[0])].copy()}
+
+
+def msa_profile_layout(grp_off, width, cells, res_off, res, aligned, qs, ts, run_off, runs, device=None):
+    """UC-T/P, layout and compaction (uc_msa_profile_layout / _dev): the new MSA from msa_profile_align's alignments, UC-T/L with a virtual centre of
+    the old width, the columns without an amino acid dropped.  Returns a dict: width [n_groups], cells [amino acids, 3Di].  device as in msa_center."""
+    go, w, ro, ce, tr, ng, n_rows, m, ok = _profile_shape(grp_off, width, cells, res_off, res)
+    al, q, t = np.ascontiguousarray(aligned, np.uint8), np.ascontiguousarray(qs, np.int32), np.ascontiguousarray(ts, np.int32)
+    uo, ru = np.ascontiguousarray(run_off, np.uint64), np.ascontiguousarray(runs, np.uint32)
+    if any(len(x) != n_rows for x in (al, q, t)) or len(uo) != n_rows + 1 or (n_rows and int(uo[-1]) > len(ru)):
+        raise ValueError("array lengths do not match grp_off")
+    cap = 0
+    if ok and ng:      # rows x (width + every D run) per group
+        dl = np.where((ru & 3) == 2, ru >> 2, 0).astype(np.int64)
+        dcum = np.concatenate([[0], np.cumsum(dl)])
+        for g in range(ng):
+            b, e = int(go[g]), int(go[g + 1])
+            if 0 <= int(uo[b]) <= int(uo[e]) <= len(ru):
+                cap += (e - b) * (int(w[g]) + int(dcum[int(uo[e])] - dcum[int(uo[b])]))
+    nw, out, need = np.zeros(max(ng, 1), np.uint32), [np.zeros(max(cap, 1), np.uint8) for _ in range(2)], np.zeros(1, np.uint64)
+    args = [ng, go.ctypes.data, _ptr(w), _ptr(ce[0]), _ptr(ce[1]), ro.ctypes.data, _ptr(tr[0]), _ptr(tr[1]), _ptr(al), _ptr(q), _ptr(t), uo.ctypes.data, _ptr(ru),
+            nw.ctypes.data, out[0].ctypes.data, out[1].ctypes.data, cap, need.ctypes.data]
+    _check(lib().uc_msa_profile_layout(*args) if device is None else lib().uc_msa_profile_layout_dev(device, *args))
+    return {"width": nw[:ng], "cells": [o[: int(need[0])].copy() for o in out]}
+
+
+def tree(db, profile_dir, out_dir, threshold=50, aligner_options="", verbosity=1, device=-1, aligner="star", refine_iters=1):
     """== `unicore tree --no-inference -d threshold -o aligner_options <db> <profile_dir> <out_dir>` (uc_tree): a centre-star MSA of every gene
     file of a `profile` output on the engine's gapped stage, filtered and concatenated into out_dir/combined.fasta (+ .partitions, fasta/<gene>/*,
     tree.chk).  verbosity is Unicore's 0..4 scale.  UC_TREE_HOST=1 in the environment runs layout, rendering and filter through the host twins.
-    Returns the stats dict (counts and seconds per phase)."""
-    o, st = make_opts("", 1, verbosity, device), UcTreeStats()
-    _check(lib().uc_tree(db.encode(), profile_dir.encode(), out_dir.encode(), threshold, (aligner_options or "").encode(), C.byref(o), C.byref(st)))
+    Returns the stats dict (counts and seconds per phase).  aligner="profile" (uc_tree_refined, `-a profile --refine-iters refine_iters`): refine_iters
+    (1 .. 8) rounds of profile refinement (UC-T/P) follow the star MSA; the dict then also holds "refine".  With aligner="star" refine_iters is not read."""
+    if aligner not in ("star", "profile"):
+        raise ValueError("aligner is 'star' or 'profile'")
+    o = make_opts("", 1, verbosity, device)
+    if aligner == "profile":
+        if not 1 <= int(refine_iters) <= TREE_MAX_REFINE:
+            raise ValueError("refine_iters is 1 .. %d" % TREE_MAX_REFINE)
+        rs = UcTreeRefinedStats()
+        _check(lib().uc_tree_refined(db.encode(), profile_dir.encode(), out_dir.encode(), threshold, (aligner_options or "").encode(), int(refine_iters), C.byref(o), C.byref(rs)))
+        st = rs.tree
+    else:
+        st = UcTreeStats()
+        _check(lib().uc_tree(db.encode(), profile_dir.encode(), out_dir.encode(), threshold, (aligner_options or "").encode(), C.byref(o), C.byref(st)))
     d = {k: int(getattr(st, k)) for k, _ in UcTreeStats._fields_ if k != "seconds"}
     d["seconds"] = dict(zip(TREE_PHASES, st.seconds))
+    if aligner == "profile":
+        d["refine"] = {k: int(getattr(rs, k)) for k in ("n_rounds", "n_tasks", "n_cells", "n_rows_became_aligned", "n_rows_became_unaligned")}
+        d["refine"].update(width_before=list(rs.width_before)[: int(rs.n_rounds)], width_after=list(rs.width_after)[: int(rs.n_rounds)],
+                           seconds=dict(zip(TREE_REFINED_PHASES, rs.seconds)))
     return d
 
 

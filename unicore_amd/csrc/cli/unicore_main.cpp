@@ -235,7 +235,9 @@ void usage_tree(FILE *to) {
          "  <INPUT>   Input directory containing core structures (profile output)\n"
          "  <OUTPUT>  Output directory\n\n"
          "Options:\n"
-         "  -a, --aligner <ALIGNER>                  Multiple sequence aligner [star]; foldmason, mafft-linsi and mafft are external programs and are refused [default: star]\n"
+         "  -a, --aligner <ALIGNER>                  Multiple sequence aligner [star, profile]; profile refines the star alignment against its own column\n"
+         "                                           profile; foldmason, mafft-linsi and mafft are external programs and are refused [default: star]\n"
+         "      --refine-iters <N>                   Rounds of profile refinement of the profile aligner [1 - 8] [default: 1]\n"
          "  -t, --tree-builder <TREE_BUILDER>        Phylogenetic tree builder [nj, iqtree, fasttree, raxml-ng]; nj (neighbour joining, built in) writes\n"
          "                                           <OUTPUT>/nj.nwk; the others are external programs: parsed, not run [default: iqtree]\n"
          "  -o, --aligner-options <ALIGNER_OPTIONS>  Foldseek-style options for the gapped stage behind the star aligner, e.g. -o \"--gap-open 12\"\n"
@@ -319,8 +321,9 @@ int nj_infer(const std::string &msa, const std::string &out, const NjOptions &nj
 int tree_main(int argc, char **argv) {
     std::vector<std::string> pos;
     std::string aligner = "star", builder = "iqtree", aligner_options, tree_options;
-    bool no_inference = false;
+    bool no_inference = false, refine_given = false;
     uint32_t threshold = 50;      // arg_parser.rs:322
+    uint32_t refine_iters = 1;    // of the profile aligner
     int verbosity = 3, threads = 0;
     for (int i = 2; i < argc; i++) {
         std::string a = argv[i];
@@ -335,6 +338,13 @@ int tree_main(int argc, char **argv) {
             if (t > 100) clap_error_tree("invalid value '" + v + "' for '--threshold <THRESHOLD>': Threshold `" + v + "` is not in range 0 to 100");
             threshold = (uint32_t)t;
         };
+        auto parse_refine = [&](const std::string &v) {
+            if (v.empty() || v.find_first_not_of("0123456789") != std::string::npos)
+                clap_error_tree("invalid value '" + v + "' for '--refine-iters <N>': Not a number");
+            const long n = v.size() > 9 ? 9 : atol(v.c_str());
+            if (n < 1 || n > UC_TREE_MAX_REFINE) clap_error_tree("invalid value '" + v + "' for '--refine-iters <N>': `" + v + "` is not in range 1 to 8");
+            refine_iters = (uint32_t)n; refine_given = true;
+        };
         if (a == "-a" || a == "--aligner") aligner = value();
         else if (a.rfind("--aligner=", 0) == 0) aligner = a.substr(10);
         else if (a == "-t" || a == "--tree-builder") builder = value();
@@ -344,6 +354,8 @@ int tree_main(int argc, char **argv) {
         else if (a == "-p" || a == "--tree-options") tree_options = value();
         else if (a.rfind("--tree-options=", 0) == 0) tree_options = a.substr(15);
         else if (a == "-n" || a == "--no-inference") no_inference = true;
+        else if (a == "--refine-iters") parse_refine(value());
+        else if (a.rfind("--refine-iters=", 0) == 0) parse_refine(a.substr(15));
         else if (a == "-d" || a == "--threshold") parse_threshold(value());
         else if (a.rfind("--threshold=", 0) == 0) parse_threshold(a.substr(12));
         else if (a == "-c" || a == "--threads") threads = atoi(value().c_str());      // read by the bootstrap of nj alone
@@ -358,7 +370,9 @@ int tree_main(int argc, char **argv) {
     g_verbosity = verbosity;
     if (aligner == "foldmason" || aligner == "mafft" || aligner == "mafft-linsi")      // tree.rs:42-45: ERR_BINARY_NOT_FOUND in the reference
         error(ERR_GENERAL, "aligner " + aligner + " is an external program, which this build does not start; the built-in aligner is 'star'");
-    if (aligner != "star") error(ERR_GENERAL, "Unrecognized aligner");                  // tree.rs:118
+    const bool profile = aligner == "profile";
+    if (aligner != "star" && !profile) error(ERR_GENERAL, "Unrecognized aligner");      // tree.rs:118
+    if (refine_given && !profile) error(ERR_GENERAL, "--refine-iters belongs to the aligner 'profile'; the aligner '" + aligner + "' has no rounds");
     const bool nj = builder == "nj";
     if (!nj && builder != "iqtree" && builder != "fasttree" && builder != "raxml-ng") error(ERR_GENERAL, "Unrecognized tree builder");   // tree.rs:146
     const NjOptions nj_opts = nj ? nj_options_of(tree_options) : NjOptions();
@@ -369,7 +383,8 @@ int tree_main(int argc, char **argv) {
     o.threads = 1;
     o.verbosity = verbosity;
     o.device = -1;
-    int rc = uc_tree(pos[0].c_str(), pos[1].c_str(), pos[2].c_str(), threshold, aligner_options.c_str(), &o, nullptr);
+    int rc = profile ? uc_tree_refined(pos[0].c_str(), pos[1].c_str(), pos[2].c_str(), threshold, aligner_options.c_str(), refine_iters, &o, nullptr)
+                     : uc_tree(pos[0].c_str(), pos[1].c_str(), pos[2].c_str(), threshold, aligner_options.c_str(), &o, nullptr);
     if (rc != 0) error(ERR_GENERAL, std::string("tree failed with code ") + std::to_string(rc) + "\n" + uc_last_error());
     if (no_inference) return 0;      // tree.rs:135-137 skips the alignment when combined.fasta exists and infers all the same
     print_message("Inferring phylogenetic tree...", 3);      // tree.rs:150

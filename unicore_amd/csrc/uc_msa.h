@@ -67,4 +67,70 @@ void msa_filter_validate(const MsaFilterArgs &a, MsaFilterPlan &plan);
 void msa_filter_host(const MsaFilterArgs &a, const MsaFilterPlan &plan);
 void msa_filter_device(int device, const MsaFilterArgs &a, const MsaFilterPlan &plan);
 
+// ---- UC-T/P: one refinement round (uc_msa_profile_host.cpp, uc_msa_profile.hip).  Track 0 = amino acids, track 1 = 3Di.
+constexpr uint32_t MSA_PROFILE_MAX_ROWS = MSA_MAX_ROWS - 1;      // the device layout adds the virtual centre as one more row of a star call
+constexpr uint32_t MSA_PROFILE_CHUNK = 64;                       // columns a wave holds at a time: one per lane
+constexpr int32_t MSA_PROFILE_NEG = -(1 << 28);                  // E and F on the borders
+constexpr uint32_t MSA_PROFILE_A = 21;
+
+// the loader's mapping (letter_code of uc_options.cpp) without the library behind it: the host twin builds alone
+inline uint32_t msa_letter_code(uint8_t c) {
+    static const int8_t T[26] = {0, 20, 1, 2, 3, 4, 5, 6, 7, 20, 8, 9, 10, 11, 20, 12, 13, 14, 15, 16, 20, 17, 18, 20, 19, 20};
+    if (c >= 'a' && c <= 'z') c -= 32;
+    return c >= 'A' && c <= 'Z' ? (uint32_t)T[c - 'A'] : 20u;
+}
+// floor(n / d) for d > 0
+inline int32_t msa_floor_div(int32_t n, int32_t d) { const int32_t q = n / d; return (n % d != 0 && n < 0) ? q - 1 : q; }
+
+struct MsaProfileAlignArgs {
+    uint32_t n_groups;
+    const uint64_t *grp_off;
+    const uint32_t *width;        // n_groups: the current MSA
+    const uint8_t *cells[2];      // as MsaStarArgs::cells
+    const uint64_t *res_off;      // n_rows + 1
+    const uint8_t *res[2];        // the full rows as letters
+    const int8_t *S[2];           // [0] SA, [1] S3: 21 x 21, [column letter][row letter]
+    int32_t gap_open, gap_ext;
+    uint8_t *aligned;             // per row
+    int32_t *score, *qs, *ts, *qe, *te;
+    uint64_t *run_off;            // n_rows + 1
+    uint32_t *runs;
+    uint64_t runs_capacity;
+    uint64_t *need;               // nullable, 1: the runs of the call
+};
+struct MsaProfilePlan {
+    uint64_t n_rows = 0;
+    std::vector<uint64_t> cell_off, col_off;      // n_groups + 1: where a group's cells / columns start
+    std::vector<uint32_t> row_group;              // n_rows
+    uint64_t n_tasks = 0, n_cells = 0;            // rows of groups with two rows or more that have a residue and a column; width x length over them
+};
+void msa_profile_align_validate(const MsaProfileAlignArgs &a, MsaProfilePlan &plan);
+void msa_profile_align_host(const MsaProfileAlignArgs &a, const MsaProfilePlan &plan, uint32_t threads);      // the same answer for every thread count
+void msa_profile_align_device(int device, const MsaProfileAlignArgs &a, const MsaProfilePlan &plan);
+
+struct MsaProfileLayoutArgs {
+    uint32_t n_groups;
+    const uint64_t *grp_off;
+    const uint32_t *width;
+    const uint8_t *cells_in[2];   // read for the groups of one row only
+    const uint64_t *res_off;
+    const uint8_t *res[2];
+    const uint8_t *aligned;
+    const int32_t *qs, *ts;
+    const uint64_t *run_off;
+    const uint32_t *runs;
+    uint32_t *new_width;
+    uint8_t *cells[2];
+    uint64_t cells_capacity;      // per track
+    uint64_t *need;               // nullable, 1: cell bytes per track
+};
+struct MsaProfileLayoutPlan {
+    uint64_t n_rows = 0;
+    std::vector<uint64_t> cell_off;               // of cells_in
+    std::vector<uint64_t> bound;                  // n_groups: columns at most, width + every D run (a group of one row: its width)
+};
+void msa_profile_layout_validate(const MsaProfileLayoutArgs &a, MsaProfileLayoutPlan &plan);
+void msa_profile_layout_host(const MsaProfileLayoutArgs &a, const MsaProfileLayoutPlan &plan);
+void msa_profile_layout_device(int device, const MsaProfileLayoutArgs &a, const MsaProfileLayoutPlan &plan);
+
 }  // namespace uc

@@ -277,7 +277,12 @@ void append_fasta(std::string &out, const std::string &name, const uint8_t *seq,
     out += '>'; out += name; out += '\n'; out.append((const char *)seq, n); out += '\n';
 }
 
-void tree_files(const char *db_prefix, const char *profile_dir, const char *out_dir, uint32_t threshold, const char *aligner_options, const uc_opts *o, uc_tree_stats *st_out) {
+// refine_iters rounds of UC-T/P (uc_msa_profile_host.cpp, uc_msa_profile.hip) between the star MSA and the filter; 0: the star MSA as it is
+void tree_files(const char *db_prefix, const char *profile_dir, const char *out_dir, uint32_t threshold, const char *aligner_options, uint32_t refine_iters, const uc_opts *o,
+                uc_tree_stats *st_out, uc_tree_refined_stats *rst_out) {
+    if (refine_iters > UC_TREE_MAX_REFINE) fail(UC_ERR_ARGS, "tree: %u refinement rounds; at most %u", refine_iters, (unsigned)UC_TREE_MAX_REFINE);
+    uc_tree_refined_stats rst;
+    memset(&rst, 0, sizeof rst);
     if (threshold > 100) fail(UC_ERR_ARGS, "tree: threshold %u outside 0 .. 100", threshold);
     int verbosity = 3, device = -1, threads = 1;
     std::string data_dir;
@@ -300,11 +305,13 @@ void tree_files(const char *db_prefix, const char *profile_dir, const char *out_
         if (stat((out + "/combined.fasta").c_str(), &sb) == 0) {
             if (verbosity >= 3) { printf("Concatenated alignment file %s/combined.fasta already exists, skipping alignment step\n", out.c_str()); fflush(stdout); }
             if (st_out) *st_out = st;
+            if (rst_out) { rst.tree = st; *rst_out = rst; }
             return;
         }
     }
     g_verbosity = p.verbosity;
     finalize_params(p, data_dir);
+    if (refine_iters && (p.gap_ext < 0 || p.gap_open < p.gap_ext)) fail(UC_ERR_ARGS, "tree: gap open %d below gap extension %d; the profile rounds need open >= extension >= 0", p.gap_open, p.gap_ext);
     Timer t_all, t_part;
     auto lap = [&](int phase) { st.seconds[phase] += t_part.seconds(); t_part = Timer(); };
     make_dirs(out);
@@ -486,6 +493,60 @@ void tree_files(const char *db_prefix, const char *profile_dir, const char *out_
         MsaStarPlan sp;
         msa_star_validate(sa, sp);
         if (on_host) msa_star_host(sa, sp); else msa_star_device(E.device, sa, sp);
+        if (refine_iters) {      // ---- UC-T/P: every round realigns the rows against the profile of the others and lays the group out again
+            const uint64_t nr = r1 - r0;
+            std::vector<uint8_t> p_al(nr), was(nr);
+            std::vector<int32_t> p_sc(nr), p_qs(nr), p_ts(nr), p_qe(nr), p_te(nr);
+            std::vector<uint64_t> p_uo(nr + 1, 0);
+            std::vector<uint32_t> p_runs, nw(n);
+            std::vector<std::string> tsv(dump ? n : 0);
+            for (uint64_t r = 0; r < nr; r++) was[r] = aligned[r0 + r];      // the centre counts as aligned
+            for (uint32_t round = 0; round < refine_iters; round++) {
+                Timer t_r;
+                uint64_t cap = 0, wsum = 0;
+                for (uint32_t k = 0; k < n; k++) { for (uint64_t r = go[k]; r < go[k + 1]; r++) cap += width[k] + (ro[r + 1] - ro[r]); wsum += width[k]; }
+                p_runs.resize(std::max<uint64_t>(cap, 1));
+                const MsaProfileAlignArgs pa{n, go.data(), width.data(), {c_aa.data(), c_3di.data()}, ro.data(), {res_aa.data() + res_off[r0], res_3di.data() + res_off[r0]},
+                                             {p.SA, p.S3}, p.gap_open, p.gap_ext, p_al.data(), p_sc.data(), p_qs.data(), p_ts.data(), p_qe.data(), p_te.data(), p_uo.data(),
+                                             p_runs.data(), cap, nullptr};
+                MsaProfilePlan pp;
+                msa_profile_align_validate(pa, pp);
+                if (on_host) msa_profile_align_host(pa, pp, (uint32_t)threads); else msa_profile_align_device(E.device, pa, pp);
+                rst.seconds[0] += t_r.seconds();
+                Timer t_l;
+                uint64_t ccap = 0;
+                const MsaProfileLayoutArgs la{n, go.data(), width.data(), {c_aa.data(), c_3di.data()}, ro.data(), {res_aa.data() + res_off[r0], res_3di.data() + res_off[r0]},
+                                              p_al.data(), p_qs.data(), p_ts.data(), p_uo.data(), p_runs.data(), nw.data(), {nullptr, nullptr}, 0, nullptr};
+                MsaProfileLayoutPlan lp;
+                msa_profile_layout_validate(la, lp);
+                for (uint32_t k = 0; k < n; k++) ccap += (go[k + 1] - go[k]) * lp.bound[k];
+                std::vector<uint8_t> n_aa(std::max<uint64_t>(ccap, 1)), n_3di(std::max<uint64_t>(ccap, 1));
+                MsaProfileLayoutArgs lb = la;
+                lb.cells[0] = n_aa.data(); lb.cells[1] = n_3di.data(); lb.cells_capacity = ccap;
+                if (on_host) msa_profile_layout_host(lb, lp); else msa_profile_layout_device(E.device, lb, lp);
+                rst.seconds[1] += t_l.seconds();
+                rst.n_rounds = std::max<uint64_t>(rst.n_rounds, round + 1);
+                rst.n_tasks += pp.n_tasks; rst.n_cells += pp.n_cells;
+                rst.width_before[round] += wsum;
+                for (uint32_t k = 0; k < n; k++) {
+                    const bool single = go[k + 1] - go[k] == 1;
+                    rst.width_after[round] += nw[k];
+                    for (uint64_t r = go[k]; r < go[k + 1]; r++) {
+                        const uint8_t now = single ? was[r] : p_al[r];
+                        rst.n_rows_became_aligned += now && !was[r]; rst.n_rows_became_unaligned += !now && was[r];
+                        was[r] = now;
+                        if (dump) tsv[k] += std::to_string(round + 1) + "\t" + std::to_string(r - go[k]) + "\t" + std::to_string(p_sc[r]) + "\t" + std::to_string(p_qs[r]) + "\t" +
+                                            std::to_string(p_ts[r]) + "\n";
+                    }
+                }
+                width = nw; c_aa.swap(n_aa); c_3di.swap(n_3di);
+            }
+            for (uint32_t k = 0; k < n; k++) if (dump) write_file(out + "/fasta/" + genes[live[g0 + k]].name + "/refine.tsv", tsv[k]);
+            for (uint64_t r = 0; r < nr; r++) rst.tree.n_rows_unaligned += !was[r];
+            uint64_t nc = 0, ncell = 0;
+            for (uint32_t k = 0; k < n; k++) { nc += width[k]; ncell += (go[k + 1] - go[k]) * width[k]; }
+            keep.assign(std::max<uint64_t>(nc, 1), 0); f_aa.assign(std::max<uint64_t>(ncell, 1), 0);
+        }
         const MsaFilterArgs fa{n, go.data(), width.data(), c_aa.data(), threshold, keep.data(), fwidth.data(), f_aa.data()};
         MsaFilterPlan fp;
         msa_filter_validate(fa, fp);
@@ -557,7 +618,17 @@ void tree_files(const char *db_prefix, const char *profile_dir, const char *out_
     if (getenv("UC_TIMING"))
         fprintf(stderr, "unicore-cluster[timing]: tree (%s layout): read %.3f s, all-pairs scores %.3f s, centres %.3f s, centre alignments %.3f s, layout + render + filter %.3f s, "
                         "write %.3f s, total %.3f s\n", on_host ? "host" : "device", st.seconds[0], st.seconds[1], st.seconds[2], st.seconds[3], st.seconds[4], st.seconds[5], st.seconds[6]);
+    if (refine_iters) st.n_rows_unaligned = rst.tree.n_rows_unaligned;
+    rst.seconds[2] = rst.seconds[0] + rst.seconds[1];
+    if (refine_iters && verbosity >= 3) {
+        printf("%llu refinement rounds: %llu profile alignments over %llu cells, %llu rows became aligned, %llu unaligned\n", (unsigned long long)rst.n_rounds,
+               (unsigned long long)rst.n_tasks, (unsigned long long)rst.n_cells, (unsigned long long)rst.n_rows_became_aligned, (unsigned long long)rst.n_rows_became_unaligned);
+        fflush(stdout);
+    }
+    if (refine_iters && getenv("UC_TIMING"))
+        fprintf(stderr, "unicore-cluster[timing]: tree refinement (%s): profile DP + walk %.3f s, layout + compaction %.3f s\n", on_host ? "host" : "device", rst.seconds[0], rst.seconds[1]);
     if (st_out) *st_out = st;
+    if (rst_out) { rst.tree = st; *rst_out = rst; }
 }
 
 }  // namespace
@@ -632,6 +703,14 @@ int uc_msa_filter_dev(int32_t device, uint32_t n_groups, const uint64_t *grp_off
 int uc_tree(const char *db_prefix, const char *profile_dir, const char *out_dir, uint32_t threshold, const char *aligner_options, const uc_opts *o, uc_tree_stats *stats_out) {
     return guard([&] {
         if (!db_prefix || !profile_dir || !out_dir) fail(UC_ERR_ARGS, "tree: db_prefix, profile_dir and out_dir must not be NULL");
-        tree_files(db_prefix, profile_dir, out_dir, threshold, aligner_options, o, stats_out);
+        tree_files(db_prefix, profile_dir, out_dir, threshold, aligner_options, 0, o, stats_out, nullptr);
+    });
+}
+
+int uc_tree_refined(const char *db_prefix, const char *profile_dir, const char *out_dir, uint32_t threshold, const char *aligner_options, uint32_t refine_iters,
+                    const uc_opts *o, uc_tree_refined_stats *stats_out) {
+    return guard([&] {
+        if (!db_prefix || !profile_dir || !out_dir) fail(UC_ERR_ARGS, "tree: db_prefix, profile_dir and out_dir must not be NULL");
+        tree_files(db_prefix, profile_dir, out_dir, threshold, aligner_options, refine_iters, o, nullptr, stats_out);
     });
 }
