@@ -427,6 +427,74 @@ typedef struct uc_tree_refined_stats {
 int uc_tree_refined(const char *db_prefix, const char *profile_dir, const char *out_dir, uint32_t threshold, const char *aligner_options, uint32_t refine_iters,
                     const uc_opts *o, uc_tree_refined_stats *stats_out);
 
+/* ---- `unicore tree -a progressive` (rule UC-T/G): a progressive MSA.  The rows of a group are merged along a guide tree by
+ * profile-profile alignment; no residue is dropped and no column is empty.  Host functions need no device; the _dev siblings run the HIP kernels of
+ * uc_msa_progressive.hip and give the same bytes.  Track 0 is the amino acids, track 1 the 3Di letters; letters are coded as in uc_msa_profile_align.
+ * S3, SA: 21 x 21 within -48 .. 48, [column letter][row letter], side a giving the column letter.  UC_ERR_ARGS everywhere: gap_open < gap_ext or
+ * gap_ext < 0, a group of more than 8192 rows, malformed offsets, a matrix entry outside -48 .. 48.
+ * uc_msa_self_scores: self[r] = sum over the row's residues of SA[a][a] + S3[d][d].
+ * uc_msa_guide (UC-T/G/T): scores as uc_msa_center takes them (row i as query), self per row.  D receives, group after group, m x m doubles:
+ *   den = min(self(i), self(j)); D = 1 where den <= 0, else 1 - (double)S / (double)den, clamped below at 0.  merges receives m - 1 pairs (a, b) of
+ *   group-local node ids per group, group g's at word 2 (grp_off[g] - g): the records of uc_nj_join over D in order (join_a is the a side; record k
+ *   creates node m + k), then (root_node[0], root_node[1]), then (that node, root_node[2]).  m = 2: (0, 1) without the join; m = 1: nothing.  The _dev
+ *   sibling runs uc_nj_join_dev for groups of 256 rows or more; the join is bit-identical, so no result depends on it.
+ * uc_msa_merge (UC-T/G/M): n_tasks independent merges.  Task k joins a (ma x Wa) with b (mb x Wb); a0 / a1 (b0 / b1) hold the sides' cells on the two
+ *   tracks, task after task, m x W bytes row-major; a cell is `-` or a letter and the tracks agree on gaps.  Per track cnt[column][letter] counts a
+ *   side's rows; s(i, j) = floor(sum over tracks, x, y of cntA[i][x] cntB[j][y] S[x][y] / (ma mb)).  H(i, 0) = H(0, j) = 0, E = F = -2^28 on the
+ *   borders; H = max(H(i-1, j-1) + s, F, E) without a floor at 0, F(i, j) = max(H(i-1, j) - open, F(i-1, j) - ext) (a's column alone, op I),
+ *   E(i, j) = max(H(i, j-1) - open, E(i, j-1) - ext) (b's column alone, op D).  The end cell (ie, je) is taken over i = Wa or j = Wb, the corners
+ *   (Wa, 0) and (0, Wb) included: largest H, then smallest j, then smallest i.  The walk (E6's preferences) ends at (is, js), one of them 0; runs are
+ *   `length << 2 | op` (0 M, 1 I, 2 D) at run_off[k] .. run_off[k + 1].  The merged node, (ma + mb) x width[k] with a's rows first, at cells0 / cells1,
+ *   tasks back to back: a[0 .. is) or b[0 .. js), the path, a[ie .. Wa) or b[je .. Wb).  A side of width 0: no DP, score and positions 0, the other
+ *   side's columns.  need_out[2] (nullable): runs and cell bytes per track; Wa + Wb words and (ma + mb) (Wa + Wb) bytes per task always suffice.
+ *   UC_ERR_ARGS also: ma or mb 0, ma + mb > 8192, Wa Wb >= 2^31, (Wa + Wb) max(open, 96) >= 2^27, ceil(Wa / chunk) (Wb + chunk - 1) chunk >= 2^31
+ *   (the score and decision bytes of a task as the kernels lay them out, an implementation limit on top of the rule's two; the twin refuses it too).
+ * uc_msa_progressive: the MSA of every group along its merge list (laid out as uc_msa_guide writes it; taken as an input, so that a caller may force a
+ *   tree).  A leaf is its row's residues.  Merges run by level: a level is every merge whose two children exist.  width[g] and group g's m_g x width[g]
+ *   cells, rows in file order.  The sum of a group's residues times its rows always suffices as capacity.  UC_ERR_ARGS also: a merge list that is not a
+ *   tree over the group (a child that does not exist yet or is used twice); a merge whose two sides, at the widths they have when their level is reached,
+ *   break the width limits of uc_msa_merge (checked on the host before the level runs, by twin and device alike).
+ * uc_msa_progressive_geometry: chunk = a's columns a wave holds at a time (wider tasks run chunk after chunk, *cap receives 0); task_bytes_per_cell =
+ *   bytes of the score and decision buffers per DP cell. */
+typedef struct uc_msa_progressive_stats {
+    uint64_t n_merges, n_levels;         /* merges run; levels over all groups of the call */
+    uint64_t n_launches;                 /* kernel launches of the device side (0 from the host twin): 5 per batch of a level, beside one rocPRIM scan */
+    uint64_t n_cells;                    /* DP cells, Wa x Wb summed over the merges */
+} uc_msa_progressive_stats;
+int uc_msa_self_scores(uint64_t n_rows, const uint64_t *res_off, const uint8_t *res0, const uint8_t *res1, const int8_t *S3, const int8_t *SA, int64_t *self);
+int uc_msa_guide(uint32_t n_groups, const uint64_t *grp_off, const int32_t *scores, const int64_t *self, double *D, uint32_t *merges);
+int uc_msa_guide_dev(int32_t device, uint32_t n_groups, const uint64_t *grp_off, const int32_t *scores, const int64_t *self, double *D, uint32_t *merges);
+int uc_msa_merge(uint32_t n_tasks, const uint32_t *ma, const uint32_t *mb, const uint32_t *Wa, const uint32_t *Wb, const uint8_t *a0, const uint8_t *a1, const uint8_t *b0,
+                 const uint8_t *b1, const int8_t *S3, const int8_t *SA, int32_t gap_open, int32_t gap_ext, int32_t *score, int32_t *is, int32_t *js, int32_t *ie, int32_t *je,
+                 uint64_t *run_off, uint32_t *runs, uint64_t runs_capacity, uint32_t *width, uint8_t *cells0, uint8_t *cells1, uint64_t cells_capacity, uint64_t *need_out,
+                 uint32_t threads);
+int uc_msa_merge_dev(int32_t device, uint32_t n_tasks, const uint32_t *ma, const uint32_t *mb, const uint32_t *Wa, const uint32_t *Wb, const uint8_t *a0, const uint8_t *a1,
+                     const uint8_t *b0, const uint8_t *b1, const int8_t *S3, const int8_t *SA, int32_t gap_open, int32_t gap_ext, int32_t *score, int32_t *is, int32_t *js, int32_t *ie,
+                     int32_t *je, uint64_t *run_off, uint32_t *runs, uint64_t runs_capacity, uint32_t *width, uint8_t *cells0, uint8_t *cells1, uint64_t cells_capacity,
+                     uint64_t *need_out);
+int uc_msa_progressive(uint32_t n_groups, const uint64_t *grp_off, const uint64_t *res_off, const uint8_t *res0, const uint8_t *res1, const uint32_t *merges, const int8_t *S3,
+                       const int8_t *SA, int32_t gap_open, int32_t gap_ext, uint32_t *width, uint8_t *cells0, uint8_t *cells1, uint64_t cells_capacity, uint64_t *need_out,
+                       uc_msa_progressive_stats *stats_out, uint32_t threads);
+int uc_msa_progressive_dev(int32_t device, uint32_t n_groups, const uint64_t *grp_off, const uint64_t *res_off, const uint8_t *res0, const uint8_t *res1, const uint32_t *merges,
+                           const int8_t *S3, const int8_t *SA, int32_t gap_open, int32_t gap_ext, uint32_t *width, uint8_t *cells0, uint8_t *cells1, uint64_t cells_capacity,
+                           uint64_t *need_out, uc_msa_progressive_stats *stats_out);
+int uc_msa_progressive_geometry(uint32_t *chunk, uint32_t *cap, uint32_t *task_bytes_per_cell);
+/* == `unicore tree --no-inference -a progressive`: uc_tree with the progressive MSA in the star MSA's place.  The all-pairs scores are the pass uc_tree
+ * runs for its centres; self scores, D, the guide trees (UC-N/J) and the merges follow; filter, concatenation and files are uc_tree's.  The merges take
+ * the matrices and gaps of aligner_options (gap open >= gap extension >= 0) and run on o->device level by level over all genes, in batches of whole
+ * tasks under UC_TREE_BUDGET_BYTES (no result depends on it); UC_TREE_HOST=1 runs the host twins (the pair scores need the device either way);
+ * UC_TREE_DUMP=1 also writes fasta/<gene>/guide.tsv: a line `#D\ti\tj\t%.17g` per pair, then a line `k\ta\tb` per merge. */
+#define UC_TREE_PROGRESSIVE_NPHASE 3
+typedef struct uc_tree_progressive_stats {
+    uc_tree_stats tree;                  /* of the whole call; n_rows_unaligned is 0: every residue is in the MSA */
+    uint64_t n_groups_aligned;           /* genes with a row */
+    uint64_t n_merges, n_levels, n_launches, n_cells;      /* as uc_msa_progressive_stats; a caterpillar tree of m rows gives m - 1 levels */
+    uint64_t width_before, width_after;  /* root widths summed over the genes, before and after the filter */
+    double seconds[UC_TREE_PROGRESSIVE_NPHASE];      /* host wall: [0] self scores + guide trees, [1] merges, [2] both */
+} uc_tree_progressive_stats;
+int uc_tree_progressive(const char *db_prefix, const char *profile_dir, const char *out_dir, uint32_t threshold, const char *aligner_options, const uc_opts *o,
+                        uc_tree_progressive_stats *stats_out);
+
 /* ---- the built-in tree builder `nj` (rule UC-N): pairwise protein distances over an aligned FASTA and neighbour joining (Saitou-Nei
  * with the Studier-Keppler criterion), the inference step of `unicore tree -t nj` and `unicore gene-tree -t nj` (tree.rs:139-161 and genetree.rs hand it
  * to an external program).  Every output is defined bit for bit; every host function (no device needed) has a _dev sibling that runs the HIP kernels

@@ -60,6 +60,19 @@ class UcTreeRefinedStats(C.Structure):
 TREE_REFINED_PHASES = ("profile_dp_walk", "layout_compaction", "total")
 
 
+class UcMsaProgressiveStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("n_merges", "n_levels", "n_launches", "n_cells")]
+
+
+class UcTreeProgressiveStats(C.Structure):
+    _fields_ = [("tree", UcTreeStats)] + [(n, C.c_uint64) for n in ("n_groups_aligned", "n_merges", "n_levels", "n_launches", "n_cells", "width_before", "width_after")] + [
+        ("seconds", C.c_double * 3)]
+
+
+TREE_PROGRESSIVE_PHASES = ("guide", "merges", "total")
+MSA_PROGRESSIVE_MAX_ROWS = 8192      # == MSA_PROG_MAX_ROWS
+
+
 class UcNjStats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("n_rows", "n_columns", "n_pairs_incomparable", "n_pairs_capped", "n_lengths_clamped")] + [("seconds", C.c_double * 5)]
 
@@ -103,6 +116,8 @@ SYMBOLS = (
     "uc_profile_count", "uc_profile_count_dev", "uc_profile",
     "uc_msa_center", "uc_msa_center_dev", "uc_msa_star", "uc_msa_star_dev", "uc_msa_filter", "uc_msa_filter_dev", "uc_tree",
     "uc_msa_profile_align", "uc_msa_profile_align_dev", "uc_msa_profile_layout", "uc_msa_profile_layout_dev", "uc_msa_profile_geometry", "uc_tree_refined",
+    "uc_msa_self_scores", "uc_msa_guide", "uc_msa_guide_dev", "uc_msa_merge", "uc_msa_merge_dev", "uc_msa_progressive", "uc_msa_progressive_dev",
+    "uc_msa_progressive_geometry", "uc_tree_progressive",
     "uc_nj_counts", "uc_nj_counts_dev", "uc_nj_distances", "uc_nj_join", "uc_nj_join_dev", "uc_nj_newick", "uc_nj_geometry", "uc_tree_infer",
     "uc_nj_boot_columns", "uc_nj_boot_counts", "uc_nj_boot_counts_dev", "uc_nj_join_batch", "uc_nj_join_batch_dev", "uc_nj_support", "uc_nj_newick_support",
     "uc_nj_boot_geometry", "uc_tree_infer_boot",
@@ -201,6 +216,17 @@ def lib():
     L.uc_msa_profile_layout_dev.argtypes = [i32] + L.uc_msa_profile_layout.argtypes
     L.uc_msa_profile_geometry.argtypes = [vp, vp, vp]
     L.uc_tree_refined.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, u32, C.c_char_p, u32, C.POINTER(UcOpts), C.POINTER(UcTreeRefinedStats)]
+    L.uc_msa_self_scores.argtypes = [u64] + [vp] * 6
+    L.uc_msa_guide.argtypes = [u32] + [vp] * 5
+    L.uc_msa_guide_dev.argtypes = [i32] + L.uc_msa_guide.argtypes
+    L.uc_msa_merge.argtypes = [u32] + [vp] * 10 + [i32, i32] + [vp] * 7 + [u64, vp, vp, vp, u64, vp]
+    L.uc_msa_merge_dev.argtypes = [i32] + L.uc_msa_merge.argtypes
+    L.uc_msa_merge.argtypes = L.uc_msa_merge.argtypes + [u32]
+    L.uc_msa_progressive.argtypes = [u32] + [vp] * 7 + [i32, i32, vp, vp, vp, u64, vp, C.POINTER(UcMsaProgressiveStats)]
+    L.uc_msa_progressive_dev.argtypes = [i32] + L.uc_msa_progressive.argtypes
+    L.uc_msa_progressive.argtypes = L.uc_msa_progressive.argtypes + [u32]
+    L.uc_msa_progressive_geometry.argtypes = [vp, vp, vp]
+    L.uc_tree_progressive.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, u32, C.c_char_p, C.POINTER(UcOpts), C.POINTER(UcTreeProgressiveStats)]
     L.uc_nj_counts.argtypes = [u32, u64, vp, u32, vp, vp]
     L.uc_nj_counts_dev.argtypes = [i32] + L.uc_nj_counts.argtypes
     L.uc_nj_distances.argtypes = [vp, vp, u32, u32, vp]
@@ -522,15 +548,128 @@ def msa_profile_layout(grp_off, width, cells, res_off, res, aligned, qs, ts, run
     return {"width": nw[:ng], "cells": [o[: int(need[0])].copy() for o in out]}
 
 
+def msa_progressive_geometry():
+    """The progressive DP kernel's geometry (uc_msa_progressive_geometry): {"chunk": a's columns a wave holds at a time, "cap": the widest side the kernel
+    serves (0: no cap), "task_bytes_per_cell": bytes of the score and decision buffers per DP cell}."""
+    a, b, c = C.c_uint32(), C.c_uint32(), C.c_uint32()
+    _check(lib().uc_msa_progressive_geometry(C.byref(a), C.byref(b), C.byref(c)))
+    return {"chunk": a.value, "cap": b.value, "task_bytes_per_cell": c.value}
+
+
+def msa_self_scores(res_off, res, S3, SA):
+    """uc_msa_self_scores (host only): per row the sum over its residues of SA[a][a] + S3[d][d], int64.  res: [amino acids, 3Di]."""
+    ro, tr = np.ascontiguousarray(res_off, np.uint64), [np.ascontiguousarray(t, np.uint8) for t in res]
+    s3, sa = np.ascontiguousarray(S3, np.int8).reshape(-1), np.ascontiguousarray(SA, np.int8).reshape(-1)
+    if len(s3) != 441 or len(sa) != 441 or len(tr) != 2 or len(ro) < 1:
+        raise ValueError("S3 and SA are 21 x 21, res two tracks, res_off n_rows + 1 entries")
+    n = len(ro) - 1
+    if n and any(len(t) < int(ro[-1]) for t in tr):
+        raise ValueError("res_off reaches beyond res")
+    out = np.zeros(max(n, 1), np.int64)
+    _check(lib().uc_msa_self_scores(n, ro.ctypes.data, _ptr(tr[0]), _ptr(tr[1]), s3.ctypes.data, sa.ctypes.data, out.ctypes.data))
+    return out[:n]
+
+
+def msa_guide(grp_off, scores, self_scores, device=None):
+    """UC-T/G/T (uc_msa_guide / uc_msa_guide_dev): the guide tree of every group from its packed triangle of pair scores (as msa_center takes it) and
+    the rows' self scores.  Returns a dict: D (list, per group an m x m fp64 matrix), merges (list, per group an (m - 1) x 2 uint32 array of node
+    pairs (a, b); merge k creates node m + k).  device as in msa_center."""
+    go, sc, se = np.ascontiguousarray(grp_off, np.uint64), np.ascontiguousarray(scores, np.int32), np.ascontiguousarray(self_scores, np.int64)
+    ng = len(go) - 1
+    if ng < 0:
+        raise ValueError("grp_off needs n_groups + 1 entries")
+    m = np.diff(go.astype(np.int64))
+    ok = ng == 0 or ((m > 0).all() and int(go[0]) == 0 and (m <= MSA_PROGRESSIVE_MAX_ROWS).all())      # the call refuses the rest itself
+    n_rows = int(go[-1]) if ng > 0 and ok else 0
+    if ok and ng and (len(sc) != int((m * (m - 1) // 2).sum()) or len(se) != n_rows):
+        raise ValueError("scores holds the triangles and self_scores one entry per row")
+    D = np.zeros(max(int((m * m).sum()) if ok and ng else 0, 1), np.float64)
+    mg = np.zeros(max(2 * (n_rows - ng), 1), np.uint32)
+    args = [ng, go.ctypes.data, _ptr(sc), _ptr(se), D.ctypes.data, mg.ctypes.data]
+    _check(lib().uc_msa_guide(*args) if device is None else lib().uc_msa_guide_dev(device, *args))
+    outD, outM, d0 = [], [], 0
+    for g in range(ng):
+        k, b = int(m[g]), int(go[g])
+        outD.append(D[d0:d0 + k * k].reshape(k, k).copy()); d0 += k * k
+        outM.append(mg[2 * (b - g):2 * (b - g) + 2 * (k - 1)].reshape(k - 1, 2).copy())
+    return {"D": outD, "merges": outM}
+
+
+def msa_merge(ma, mb, Wa, Wb, a, b, S3, SA, gap_open, gap_ext, device=None, threads=1):
+    """UC-T/G/M (uc_msa_merge / uc_msa_merge_dev): a batch of independent profile-profile merges.  ma, mb, Wa, Wb per task; a and b: [amino acids, 3Di],
+    each the sides' cells task after task (m x W bytes row-major, `-` or a letter).  Returns a dict: score, is, js, ie, je, width per task, run_off
+    [n_tasks + 1], runs (length << 2 | op; 0 M, 1 I = a's column alone, 2 D = b's column alone), cell_off [n_tasks + 1], cells [amino acids, 3Di]
+    (task k: (ma + mb) x width[k] bytes at cell_off[k]).  device as in msa_center; threads: the host twin's."""
+    A_, B_, WA, WB = (np.ascontiguousarray(x, np.uint32) for x in (ma, mb, Wa, Wb))
+    ca, cb = [np.ascontiguousarray(x, np.uint8) for x in a], [np.ascontiguousarray(x, np.uint8) for x in b]
+    s3, sa = np.ascontiguousarray(S3, np.int8).reshape(-1), np.ascontiguousarray(SA, np.int8).reshape(-1)
+    n = len(A_)
+    if len(s3) != 441 or len(sa) != 441 or len(ca) != 2 or len(cb) != 2 or any(len(x) != n for x in (B_, WA, WB)):
+        raise ValueError("S3 and SA are 21 x 21, a and b two tracks, ma, mb, Wa and Wb one entry per task")
+    i64 = lambda x: x.astype(np.int64)
+    if any(len(c) != int((i64(A_) * i64(WA)).sum()) for c in ca) or any(len(c) != int((i64(B_) * i64(WB)).sum()) for c in cb):
+        raise ValueError("a / b do not hold what ma, mb, Wa and Wb describe")
+    rcap, ccap = int((i64(WA) + i64(WB)).sum()), int(((i64(A_) + i64(B_)) * (i64(WA) + i64(WB))).sum())
+    sc, i0, j0, ie, je = (np.zeros(max(n, 1), np.int32) for _ in range(5))
+    uo, runs, width = np.zeros(n + 1, np.uint64), np.zeros(max(rcap, 1), np.uint32), np.zeros(max(n, 1), np.uint32)
+    out, need = [np.zeros(max(ccap, 1), np.uint8) for _ in range(2)], np.zeros(2, np.uint64)
+    args = [n, _ptr(A_), _ptr(B_), _ptr(WA), _ptr(WB), _ptr(ca[0]), _ptr(ca[1]), _ptr(cb[0]), _ptr(cb[1]), s3.ctypes.data, sa.ctypes.data, gap_open, gap_ext,
+            sc.ctypes.data, i0.ctypes.data, j0.ctypes.data, ie.ctypes.data, je.ctypes.data, uo.ctypes.data, runs.ctypes.data, rcap, width.ctypes.data,
+            out[0].ctypes.data, out[1].ctypes.data, ccap, need.ctypes.data]
+    _check(lib().uc_msa_merge(*args, threads) if device is None else lib().uc_msa_merge_dev(device, *args))
+    co = np.concatenate([[0], np.cumsum((i64(A_) + i64(B_)) * i64(width[:n]))]).astype(np.uint64)
+    return {"score": sc[:n], "is": i0[:n], "js": j0[:n], "ie": ie[:n], "je": je[:n], "width": width[:n], "run_off": uo, "runs": runs[: int(need[0])].copy(),
+            "cell_off": co, "cells": [o[: int(need[1])].copy() for o in out]}
+
+
+def msa_progressive(grp_off, res_off, res, merges, S3, SA, gap_open, gap_ext, device=None, threads=1):
+    """UC-T/G (uc_msa_progressive / uc_msa_progressive_dev): the progressive MSA of every group along its merge list.  res: [amino acids, 3Di] on the
+    offsets res_off; merges: per group an (m - 1) x 2 array of node pairs as msa_guide returns them (any tree over the group may be forced).  Returns a
+    dict: width [n_groups], cells [amino acids, 3Di] (group g: m_g x width[g] bytes, rows in file order), stats.  device as in msa_center."""
+    go, ro = np.ascontiguousarray(grp_off, np.uint64), np.ascontiguousarray(res_off, np.uint64)
+    tr = [np.ascontiguousarray(t, np.uint8) for t in res]
+    s3, sa = np.ascontiguousarray(S3, np.int8).reshape(-1), np.ascontiguousarray(SA, np.int8).reshape(-1)
+    ng = len(go) - 1
+    if ng < 0 or len(s3) != 441 or len(sa) != 441 or len(tr) != 2 or len(merges) != ng:
+        raise ValueError("grp_off needs n_groups + 1 entries, S3 and SA are 21 x 21, res two tracks, merges one list per group")
+    m = np.diff(go.astype(np.int64))
+    ok = ng == 0 or ((m > 0).all() and int(go[0]) == 0)      # the call refuses the rest itself
+    n_rows = int(go[-1]) if ng > 0 and ok else 0
+    if len(ro) != n_rows + 1 and ok:
+        raise ValueError("res_off needs n_rows + 1 entries")
+    parts = [np.ascontiguousarray(x, np.uint32).reshape(-1) for x in merges]
+    if ok and any(len(x) != 2 * (int(k) - 1) for x, k in zip(parts, m)):
+        raise UcError(UC_ERR_ARGS, "progressive MSA: a group's merge list holds m - 1 pairs")
+    mg = np.concatenate(parts + [np.zeros(1, np.uint32)])
+    cap = 0
+    if ok and ng and (np.diff(ro.astype(np.int64)) >= 0).all() and int(ro[0]) == 0:
+        if any(len(t) < int(ro[-1]) for t in tr):
+            raise ValueError("res_off reaches beyond res")
+        cap = int(sum(int(m[g]) * (int(ro[int(go[g + 1])]) - int(ro[int(go[g])])) for g in range(ng)))
+    width, out, need, st = np.zeros(max(ng, 1), np.uint32), [np.zeros(max(cap, 1), np.uint8) for _ in range(2)], np.zeros(1, np.uint64), UcMsaProgressiveStats()
+    args = [ng, go.ctypes.data, ro.ctypes.data, _ptr(tr[0]), _ptr(tr[1]), mg.ctypes.data, s3.ctypes.data, sa.ctypes.data, gap_open, gap_ext, width.ctypes.data,
+            out[0].ctypes.data, out[1].ctypes.data, cap, need.ctypes.data, C.byref(st)]
+    _check(lib().uc_msa_progressive(*args, threads) if device is None else lib().uc_msa_progressive_dev(device, *args))
+    return {"width": width[:ng], "cells": [o[: int(need[0])].copy() for o in out], "stats": {k: int(getattr(st, k)) for k, _ in UcMsaProgressiveStats._fields_}}
+
+
 def tree(db, profile_dir, out_dir, threshold=50, aligner_options="", verbosity=1, device=-1, aligner="star", refine_iters=1):
     """== `unicore tree --no-inference -d threshold -o aligner_options <db> <profile_dir> <out_dir>` (uc_tree): a centre-star MSA of every gene
     file of a `profile` output on the engine's gapped stage, filtered and concatenated into out_dir/combined.fasta (+ .partitions, fasta/<gene>/*,
     tree.chk).  verbosity is Unicore's 0..4 scale.  UC_TREE_HOST=1 in the environment runs layout, rendering and filter through the host twins.
     Returns the stats dict (counts and seconds per phase).  aligner="profile" (uc_tree_refined, `-a profile --refine-iters refine_iters`): refine_iters
     (1 .. 8) rounds of profile refinement (UC-T/P) follow the star MSA; the dict then also holds "refine".  With aligner="star" refine_iters is not read."""
-    if aligner not in ("star", "profile"):
-        raise ValueError("aligner is 'star' or 'profile'")
+    if aligner not in ("star", "profile", "progressive"):
+        raise ValueError("aligner is 'star', 'profile' or 'progressive'")
     o = make_opts("", 1, verbosity, device)
+    if aligner == "progressive":      # uc_tree_progressive, `-a progressive` (UC-T/G): the dict then also holds "progressive"
+        ps = UcTreeProgressiveStats()
+        _check(lib().uc_tree_progressive(db.encode(), profile_dir.encode(), out_dir.encode(), threshold, (aligner_options or "").encode(), C.byref(o), C.byref(ps)))
+        d = {k: int(getattr(ps.tree, k)) for k, _ in UcTreeStats._fields_ if k != "seconds"}
+        d["seconds"] = dict(zip(TREE_PHASES, ps.tree.seconds))
+        d["progressive"] = {k: int(getattr(ps, k)) for k, _ in UcTreeProgressiveStats._fields_ if k not in ("tree", "seconds")}
+        d["progressive"]["seconds"] = dict(zip(TREE_PROGRESSIVE_PHASES, ps.seconds))
+        return d
     if aligner == "profile":
         if not 1 <= int(refine_iters) <= TREE_MAX_REFINE:
             raise ValueError("refine_iters is 1 .. %d" % TREE_MAX_REFINE)

@@ -236,7 +236,8 @@ void usage_tree(FILE *to) {
          "  <OUTPUT>  Output directory\n\n"
          "Options:\n"
          "  -a, --aligner <ALIGNER>                  Multiple sequence aligner [star, profile]; profile refines the star alignment against its own column\n"
-         "                                           profile; foldmason, mafft-linsi and mafft are external programs and are refused [default: star]\n"
+         "                                           profile; progressive merges the rows along a guide tree by profile-profile alignment and keeps every residue;\n"
+         "                                           foldmason, mafft-linsi and mafft are external programs and are refused [default: star]\n"
          "      --refine-iters <N>                   Rounds of profile refinement of the profile aligner [1 - 8] [default: 1]\n"
          "  -t, --tree-builder <TREE_BUILDER>        Phylogenetic tree builder [nj, iqtree, fasttree, raxml-ng]; nj (neighbour joining, built in) writes\n"
          "                                           <OUTPUT>/nj.nwk; the others are external programs: parsed, not run [default: iqtree]\n"
@@ -371,7 +372,8 @@ int tree_main(int argc, char **argv) {
     if (aligner == "foldmason" || aligner == "mafft" || aligner == "mafft-linsi")      // tree.rs:42-45: ERR_BINARY_NOT_FOUND in the reference
         error(ERR_GENERAL, "aligner " + aligner + " is an external program, which this build does not start; the built-in aligner is 'star'");
     const bool profile = aligner == "profile";
-    if (aligner != "star" && !profile) error(ERR_GENERAL, "Unrecognized aligner");      // tree.rs:118
+    const bool progressive = aligner == "progressive";
+    if (aligner != "star" && !profile && !progressive) error(ERR_GENERAL, "Unrecognized aligner");      // tree.rs:118
     if (refine_given && !profile) error(ERR_GENERAL, "--refine-iters belongs to the aligner 'profile'; the aligner '" + aligner + "' has no rounds");
     const bool nj = builder == "nj";
     if (!nj && builder != "iqtree" && builder != "fasttree" && builder != "raxml-ng") error(ERR_GENERAL, "Unrecognized tree builder");   // tree.rs:146
@@ -383,7 +385,8 @@ int tree_main(int argc, char **argv) {
     o.threads = 1;
     o.verbosity = verbosity;
     o.device = -1;
-    int rc = profile ? uc_tree_refined(pos[0].c_str(), pos[1].c_str(), pos[2].c_str(), threshold, aligner_options.c_str(), refine_iters, &o, nullptr)
+    int rc = progressive ? uc_tree_progressive(pos[0].c_str(), pos[1].c_str(), pos[2].c_str(), threshold, aligner_options.c_str(), &o, nullptr)
+           : profile ? uc_tree_refined(pos[0].c_str(), pos[1].c_str(), pos[2].c_str(), threshold, aligner_options.c_str(), refine_iters, &o, nullptr)
                      : uc_tree(pos[0].c_str(), pos[1].c_str(), pos[2].c_str(), threshold, aligner_options.c_str(), &o, nullptr);
     if (rc != 0) error(ERR_GENERAL, std::string("tree failed with code ") + std::to_string(rc) + "\n" + uc_last_error());
     if (no_inference) return 0;      // tree.rs:135-137 skips the alignment when combined.fasta exists and infers all the same

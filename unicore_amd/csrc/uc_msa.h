@@ -133,4 +133,78 @@ void msa_profile_layout_validate(const MsaProfileLayoutArgs &a, MsaProfileLayout
 void msa_profile_layout_host(const MsaProfileLayoutArgs &a, const MsaProfileLayoutPlan &plan);
 void msa_profile_layout_device(int device, const MsaProfileLayoutArgs &a, const MsaProfileLayoutPlan &plan);
 
+// ---- UC-T/G: the progressive MSA (uc_msa_progressive_host.cpp, uc_msa_progressive.hip).  Track 0 = amino acids, track 1 = 3Di; side a gives the column letter.
+constexpr uint32_t MSA_PROG_MAX_ROWS = 8192;                  // ma mb 96 < 2^31 for ma + mb <= 8192
+constexpr uint32_t MSA_PROG_CHUNK = 64;                       // a's columns a wave holds at a time: one per lane
+constexpr int32_t MSA_PROG_NEG = MSA_PROFILE_NEG;
+constexpr uint32_t MSA_PROG_NO_NODE = 0xffffffffu;
+
+struct MsaProgStats { uint64_t n_merges, n_levels, n_launches, n_cells; };
+
+// the guide tree: D (n_groups blocks of m x m doubles) and the merge list (group g: m_g - 1 pairs at 2 (grp_off[g] - g)) from the packed triangles and self scores
+struct MsaGuideArgs {
+    uint32_t n_groups;
+    const uint64_t *grp_off;
+    const int32_t *scores;        // as MsaCenterArgs::scores
+    const int64_t *self;          // per row
+    double *D;                    // group g: m_g x m_g at the sum of the squares before it
+    uint32_t *merges;             // 2 (n_rows - n_groups)
+};
+void msa_guide_validate(const MsaGuideArgs &a, std::vector<uint64_t> &tri_off);
+// device < -1: the host join for every group; otherwise the device join (bit-identical) for the groups of MSA_GUIDE_DEV_ROWS rows or more
+constexpr uint32_t MSA_GUIDE_DEV_ROWS = 256;
+void msa_guide_run(const MsaGuideArgs &a, const std::vector<uint64_t> &tri_off, bool on_device, int device);
+void msa_self_scores(uint64_t n_rows, const uint64_t *res_off, const uint8_t *res0, const uint8_t *res1, const int8_t *SA, const int8_t *S3, int64_t *self);
+
+// a batch of independent merges: task k joins a (ma x Wa) and b (mb x Wb); the sides' cells lie task after task, m x W bytes each, row-major
+struct MsaMergeArgs {
+    uint32_t n_tasks;
+    const uint32_t *ma, *mb, *Wa, *Wb;
+    const uint8_t *a[2], *b[2];
+    const int8_t *S[2];           // [0] SA, [1] S3
+    int32_t gap_open, gap_ext;
+    int32_t *score, *is, *js, *ie, *je;      // per task
+    uint64_t *run_off;            // n_tasks + 1
+    uint32_t *runs;
+    uint64_t runs_capacity;
+    uint32_t *width;              // per task: the merged width
+    uint8_t *cells[2];            // task k: (ma + mb) x width[k], tasks back to back
+    uint64_t cells_capacity;      // per track
+    uint64_t *need;               // nullable, 2: runs and cell bytes per track
+};
+struct MsaMergePlan {
+    std::vector<uint64_t> a_off, b_off;      // n_tasks + 1
+    uint64_t n_cells = 0;                    // DP cells
+};
+void msa_merge_validate(const MsaMergeArgs &a, MsaMergePlan &plan);
+void msa_merge_host(const MsaMergeArgs &a, const MsaMergePlan &plan, uint32_t threads);      // the same answer for every thread count
+void msa_merge_device(int device, const MsaMergeArgs &a, const MsaMergePlan &plan);
+// the limits of one merge, shared by both calls (UC_ERR_ARGS)
+void msa_merge_check_widths(uint64_t Wa, uint64_t Wb, int32_t gap_open, const char *what, uint64_t k);
+
+struct MsaProgressiveArgs {
+    uint32_t n_groups;
+    const uint64_t *grp_off;
+    const uint64_t *res_off;      // n_rows + 1
+    const uint8_t *res[2];
+    const uint32_t *merges;       // as MsaGuideArgs::merges
+    const int8_t *S[2];
+    int32_t gap_open, gap_ext;
+    uint32_t *width;              // n_groups
+    uint8_t *cells[2];            // group g: m_g x width[g], rows in file order
+    uint64_t cells_capacity;
+    uint64_t *need;               // nullable, 1
+    MsaProgStats *stats;          // nullable
+};
+struct MsaProgMerge { uint32_t group, a, b, node; };      // group-local node ids
+struct MsaProgressivePlan {
+    uint64_t n_rows = 0;
+    std::vector<std::vector<MsaProgMerge>> levels;       // every merge whose children exist after the levels before it
+    std::vector<uint64_t> node_off;                      // n_groups + 1: group g has 2 m_g - 1 nodes
+    std::vector<uint32_t> rows;                          // per node: its row count
+};
+void msa_progressive_validate(const MsaProgressiveArgs &a, MsaProgressivePlan &plan);
+void msa_progressive_host(const MsaProgressiveArgs &a, const MsaProgressivePlan &plan, uint32_t threads);
+void msa_progressive_device(int device, const MsaProgressiveArgs &a, const MsaProgressivePlan &plan);
+
 }  // namespace uc

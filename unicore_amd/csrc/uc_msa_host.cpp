@@ -230,7 +230,7 @@ struct Gene {
 };
 
 // the *.txt files of the profile directory in ascending file-name byte order (tree.rs:63-67)
-std::vector<Gene> read_genes(const std::string &dir, const std::unordered_map<std::string_view, uint32_t> &id_of) {
+std::vector<Gene> read_genes(const std::string &dir, const std::unordered_map<std::string_view, uint32_t> &id_of, uint32_t max_rows = MSA_MAX_ROWS) {
     DIR *d = opendir(dir.c_str());
     if (!d) fail(UC_ERR_IO, "cannot open directory %s", dir.c_str());
     std::vector<std::string> files;
@@ -267,7 +267,7 @@ std::vector<Gene> read_genes(const std::string &dir, const std::unordered_map<st
             G.species.emplace_back(fld[1]);
             p = e + 1;
         }
-        if (G.seq.size() > MSA_MAX_ROWS) fail(UC_ERR_ARGS, "%s: %zu rows; a group holds at most %u", path.c_str(), G.seq.size(), MSA_MAX_ROWS);
+        if (G.seq.size() > max_rows) fail(UC_ERR_ARGS, "%s: %zu rows; a group holds at most %u", path.c_str(), G.seq.size(), max_rows);
         genes.push_back(std::move(G));
     }
     return genes;
@@ -278,8 +278,11 @@ void append_fasta(std::string &out, const std::string &name, const uint8_t *seq,
 }
 
 // refine_iters rounds of UC-T/P (uc_msa_profile_host.cpp, uc_msa_profile.hip) between the star MSA and the filter; 0: the star MSA as it is
+// progressive: UC-T/G (uc_msa_progressive_host.cpp, uc_msa_progressive.hip) in the star MSA's place
 void tree_files(const char *db_prefix, const char *profile_dir, const char *out_dir, uint32_t threshold, const char *aligner_options, uint32_t refine_iters, const uc_opts *o,
-                uc_tree_stats *st_out, uc_tree_refined_stats *rst_out) {
+                uc_tree_stats *st_out, uc_tree_refined_stats *rst_out, bool progressive = false, uc_tree_progressive_stats *pst_out = nullptr) {
+    uc_tree_progressive_stats pst;
+    memset(&pst, 0, sizeof pst);
     if (refine_iters > UC_TREE_MAX_REFINE) fail(UC_ERR_ARGS, "tree: %u refinement rounds; at most %u", refine_iters, (unsigned)UC_TREE_MAX_REFINE);
     uc_tree_refined_stats rst;
     memset(&rst, 0, sizeof rst);
@@ -306,12 +309,14 @@ void tree_files(const char *db_prefix, const char *profile_dir, const char *out_
             if (verbosity >= 3) { printf("Concatenated alignment file %s/combined.fasta already exists, skipping alignment step\n", out.c_str()); fflush(stdout); }
             if (st_out) *st_out = st;
             if (rst_out) { rst.tree = st; *rst_out = rst; }
+            if (pst_out) { pst.tree = st; *pst_out = pst; }
             return;
         }
     }
     g_verbosity = p.verbosity;
     finalize_params(p, data_dir);
     if (refine_iters && (p.gap_ext < 0 || p.gap_open < p.gap_ext)) fail(UC_ERR_ARGS, "tree: gap open %d below gap extension %d; the profile rounds need open >= extension >= 0", p.gap_open, p.gap_ext);
+    if (progressive && (p.gap_ext < 0 || p.gap_open < p.gap_ext)) fail(UC_ERR_ARGS, "tree: gap open %d below gap extension %d; the progressive aligner needs open >= extension >= 0", p.gap_open, p.gap_ext);
     Timer t_all, t_part;
     auto lap = [&](int phase) { st.seconds[phase] += t_part.seconds(); t_part = Timer(); };
     make_dirs(out);
@@ -327,7 +332,7 @@ void tree_files(const char *db_prefix, const char *profile_dir, const char *out_
     {
         std::unordered_map<std::string_view, uint32_t> id_of;
         for (uint32_t i = 0; i < H.n; i++) id_of[H.names[i]] = i;      // a later entry of the same name replaces the earlier one (a HashMap insert)
-        genes = read_genes(profile_dir, id_of);
+        genes = read_genes(profile_dir, id_of, progressive ? MSA_PROG_MAX_ROWS : MSA_MAX_ROWS);
     }
     const uint32_t ng_all = (uint32_t)genes.size();
     Engine E(p, device);
@@ -367,6 +372,7 @@ void tree_files(const char *db_prefix, const char *profile_dir, const char *out_
 
     // ---- UC-T/C: all pairs of every group, scores only, batched over whole groups under the byte budget; then the centres
     std::vector<uint32_t> centre(ng, 0);
+    std::vector<int32_t> tri_all;      // progressive: every group's triangle, groups back to back
     {
         const uint64_t max_pairs = std::max<uint64_t>(budget / 64, 1);      // a pair of sw_batch: ids, plan and three results on both sides
         std::vector<PairIn> pairs;
@@ -394,16 +400,17 @@ void tree_files(const char *db_prefix, const char *profile_dir, const char *out_
             if (np) E.sw_batch(0, pairs, score.data(), nullptr, nullptr);
             st.seconds[1] += t_dp.seconds();
             st.n_pairs_scored += np;
+            if (progressive) tri_all.insert(tri_all.end(), score.begin(), score.begin() + np);
             Timer t_c;
             const MsaCenterArgs ca{g1 - g0, off.data(), score.data(), centre.data() + g0};
             std::vector<uint64_t> tri;
             msa_center_validate(ca, tri);
-            if (on_host) msa_center_host(ca, tri); else msa_center_device(E.device, ca, tri);
+            if (!progressive) { if (on_host) msa_center_host(ca, tri); else msa_center_device(E.device, ca, tri); }      // progressive: the triangle feeds the guide trees, no centre
             st.seconds[2] += t_c.seconds();
             if (dump)
                 for (uint32_t g = g0; g < g1; g++) {
                     const uint64_t m = grp_off[g + 1] - grp_off[g];
-                    std::string txt = "#centre\t" + std::to_string(centre[g]) + "\n";
+                    std::string txt = progressive ? std::string() : "#centre\t" + std::to_string(centre[g]) + "\n";
                     uint64_t k = tri[g - g0];
                     for (uint64_t i = 0; i < m; i++)
                         for (uint64_t j = i + 1; j < m; j++, k++) txt += std::to_string(i) + "\t" + std::to_string(j) + "\t" + std::to_string(score[k]) + "\n";
@@ -419,7 +426,7 @@ void tree_files(const char *db_prefix, const char *profile_dir, const char *out_
     std::vector<uint8_t> aligned(n_rows, 0);
     std::vector<uint64_t> run_off(n_rows + 1, 0);
     std::vector<uint32_t> runs;
-    {
+    if (!progressive) {
         std::vector<uint64_t> want;      // centre sequence << 32 | member sequence
         for (uint32_t g = 0; g < ng; g++) {
             const uint64_t b = grp_off[g], c = row_seq[b + centre[g]];
@@ -469,6 +476,53 @@ void tree_files(const char *db_prefix, const char *profile_dir, const char *out_
         for (uint64_t k = run_off[grp_off[g]]; k < run_off[grp_off[g + 1]]; k++) if ((runs[k] & 3u) == 2u) w += runs[k] >> 2;
         bound[g] = w;
     }
+    // ---- UC-T/G: self scores, guide trees and the merges of all genes together, level by level
+    std::vector<uint32_t> pg_width(progressive ? ng : 0);
+    std::vector<uint8_t> pg_cells[2];
+    std::vector<uint64_t> pg_cell_off((size_t)ng + 1, 0);
+    if (progressive && ng) {
+        lap(0);      // the guide trees and the merges are booked with layout + render + filter, not with reading
+        Timer t_g;
+        std::vector<int64_t> self(n_rows);
+        msa_self_scores(n_rows, res_off.data(), res_aa.data(), res_3di.data(), p.SA, p.S3, self.data());
+        uint64_t nd = 0;
+        for (uint32_t g = 0; g < ng; g++) { const uint64_t m = grp_off[g + 1] - grp_off[g]; nd += m * m; }
+        std::vector<double> Dm(nd);
+        std::vector<uint32_t> merges(std::max<uint64_t>(2 * (n_rows - ng), 1));
+        const MsaGuideArgs ga{ng, grp_off.data(), tri_all.data(), self.data(), Dm.data(), merges.data()};
+        std::vector<uint64_t> tri;
+        msa_guide_validate(ga, tri);
+        msa_guide_run(ga, tri, !on_host, E.device);
+        pst.seconds[0] = t_g.seconds();
+        if (dump) {
+            uint64_t d0 = 0;
+            char num[64];
+            for (uint32_t g = 0; g < ng; g++) {
+                const uint64_t m = grp_off[g + 1] - grp_off[g];
+                std::string txt;
+                for (uint64_t i = 0; i < m; i++)
+                    for (uint64_t j = i + 1; j < m; j++) { snprintf(num, sizeof num, "%.17g", Dm[d0 + i * m + j]); txt += "#D\t" + std::to_string(i) + "\t" + std::to_string(j) + "\t" + num + "\n"; }
+                const uint32_t *mg = merges.data() + 2 * (grp_off[g] - g);
+                for (uint64_t k = 0; k + 1 < m; k++) txt += std::to_string(k) + "\t" + std::to_string(mg[2 * k]) + "\t" + std::to_string(mg[2 * k + 1]) + "\n";
+                write_file(out + "/fasta/" + genes[live[g]].name + "/guide.tsv", txt);
+                d0 += m * m;
+            }
+        }
+        Timer t_m;
+        uint64_t cap = 0;
+        for (uint32_t g = 0; g < ng; g++) cap += (grp_off[g + 1] - grp_off[g]) * (res_off[grp_off[g + 1]] - res_off[grp_off[g]]);
+        pg_cells[0].resize(std::max<uint64_t>(cap, 1)); pg_cells[1].resize(std::max<uint64_t>(cap, 1));
+        MsaProgStats ps{0, 0, 0, 0};
+        const MsaProgressiveArgs pa{ng, grp_off.data(), res_off.data(), {res_aa.data(), res_3di.data()}, merges.data(), {p.SA, p.S3}, p.gap_open, p.gap_ext, pg_width.data(),
+                                    {pg_cells[0].data(), pg_cells[1].data()}, cap, nullptr, &ps};
+        MsaProgressivePlan pp;
+        msa_progressive_validate(pa, pp);
+        if (on_host) msa_progressive_host(pa, pp, (uint32_t)threads); else msa_progressive_device(E.device, pa, pp);
+        pst.seconds[1] = t_m.seconds();
+        pst.n_groups_aligned = ng; pst.n_merges = ps.n_merges; pst.n_levels = ps.n_levels; pst.n_launches = ps.n_launches; pst.n_cells = ps.n_cells;
+        for (uint32_t g = 0; g < ng; g++) { bound[g] = pg_width[g]; pg_cell_off[g + 1] = pg_cell_off[g] + (grp_off[g + 1] - grp_off[g]) * pg_width[g]; }
+        lap(4);
+    }
     struct Kept { uint32_t gene; uint32_t fw; std::vector<uint8_t> cells; };      // the filtered amino-acid rows of a group that kept a column
     std::vector<Kept> kept;
     lap(0);
@@ -490,9 +544,15 @@ void tree_files(const char *db_prefix, const char *profile_dir, const char *out_
         const MsaStarArgs sa = star_args(n, go.data(), centre.data() + g0, 2, ro.data(), res_aa.data() + res_off[r0], res_3di.data() + res_off[r0], qs.data() + r0, ts.data() + r0,
                                          uo.data(), runs.data() + run_off[r0], aligned.data() + r0, width.data(), col.data(), cnt.data(), cols, c_aa.data(), c_3di.data(), cells,
                                          nullptr);
-        MsaStarPlan sp;
-        msa_star_validate(sa, sp);
-        if (on_host) msa_star_host(sa, sp); else msa_star_device(E.device, sa, sp);
+        if (progressive) {      // the roots as they are
+            for (uint32_t k = 0; k < n; k++) width[k] = pg_width[g0 + k];
+            const uint64_t nb = pg_cell_off[g1] - pg_cell_off[g0];
+            if (nb) { memcpy(c_aa.data(), pg_cells[0].data() + pg_cell_off[g0], nb); memcpy(c_3di.data(), pg_cells[1].data() + pg_cell_off[g0], nb); }
+        } else {
+            MsaStarPlan sp;
+            msa_star_validate(sa, sp);
+            if (on_host) msa_star_host(sa, sp); else msa_star_device(E.device, sa, sp);
+        }
         if (refine_iters) {      // ---- UC-T/P: every round realigns the rows against the profile of the others and lays the group out again
             const uint64_t nr = r1 - r0;
             std::vector<uint8_t> p_al(nr), was(nr);
@@ -627,8 +687,18 @@ void tree_files(const char *db_prefix, const char *profile_dir, const char *out_
     }
     if (refine_iters && getenv("UC_TIMING"))
         fprintf(stderr, "unicore-cluster[timing]: tree refinement (%s): profile DP + walk %.3f s, layout + compaction %.3f s\n", on_host ? "host" : "device", rst.seconds[0], rst.seconds[1]);
+    pst.seconds[2] = pst.seconds[0] + pst.seconds[1];
+    pst.width_before = st.n_columns; pst.width_after = st.n_columns_kept;
+    if (progressive && verbosity >= 3) {
+        printf("progressive MSA: %llu merges in %llu levels, %llu kernel launches, %llu cells\n", (unsigned long long)pst.n_merges, (unsigned long long)pst.n_levels,
+               (unsigned long long)pst.n_launches, (unsigned long long)pst.n_cells);
+        fflush(stdout);
+    }
+    if (progressive && getenv("UC_TIMING"))
+        fprintf(stderr, "unicore-cluster[timing]: tree progressive (%s): self scores + guide trees %.3f s, merges %.3f s\n", on_host ? "host" : "device", pst.seconds[0], pst.seconds[1]);
     if (st_out) *st_out = st;
     if (rst_out) { rst.tree = st; *rst_out = rst; }
+    if (pst_out) { pst.tree = st; *pst_out = pst; }
 }
 
 }  // namespace
@@ -712,5 +782,13 @@ int uc_tree_refined(const char *db_prefix, const char *profile_dir, const char *
     return guard([&] {
         if (!db_prefix || !profile_dir || !out_dir) fail(UC_ERR_ARGS, "tree: db_prefix, profile_dir and out_dir must not be NULL");
         tree_files(db_prefix, profile_dir, out_dir, threshold, aligner_options, refine_iters, o, nullptr, stats_out);
+    });
+}
+
+int uc_tree_progressive(const char *db_prefix, const char *profile_dir, const char *out_dir, uint32_t threshold, const char *aligner_options, const uc_opts *o,
+                        uc_tree_progressive_stats *stats_out) {
+    return guard([&] {
+        if (!db_prefix || !profile_dir || !out_dir) fail(UC_ERR_ARGS, "tree: db_prefix, profile_dir and out_dir must not be NULL");
+        tree_files(db_prefix, profile_dir, out_dir, threshold, aligner_options, 0, o, nullptr, nullptr, true, stats_out);
     });
 }
